@@ -16,8 +16,12 @@ seed-1337 default init (the reference does the same when 
 shard across ranks with no data-path collective ("weak" scaling): the only collectives are the RCCL probe, the timing
 barrier and a MAX / SUM of scalars at the end.
 
-One JSON line is printed by rank 0.
+A plain run sets up, checks one encode + decode for losslessness, warms up, times the K steps, writes the last step's outputs
+(--dump-outputs DIR) and prints one JSON line from rank 0 with the headline alone:
   value                 pixels of all ranks x K / max-over-ranks time of the K steps, inputs and outputs RESIDENT in HBM
+  ms_per_step           the max-over-ranks time of the K steps / K
+Everything below is measured only with --full (as every run did before that option existed):
+  enc_mpix_s, dec_mpix_s  encode and decode timed apart
   value_pcie_inclusive  the same steps with H2D of the uint8 RGB, D2H of the containers (encode) and H2D of the containers,
                         D2H of the RGB (decode) inside the timed region, pinned host buffers (SURVEY.md 8(d)'s wording),
                         transfers overlapped with compute on their own HIP streams; value_pcie_serial: not overlapped
@@ -29,6 +33,8 @@ One JSON line is printed by rank 0.
                         informational legs, N = 1 only, outside the timed region
   cpu_baseline          the CPU oracle in the reference's structure on the host cores, bounded sample; .torch_cpu: the same path
                         on plain PyTorch CPU ops (one image)
+  n1_companion          N > 1: rank 0's solo run of the same per-GPU batch (efficiency_like_for_like)
+The --no-* options below trim a --full run.
 """
 from __future__ import annotations
 
@@ -67,6 +73,8 @@ MAC_PER_BAND = (352 * 48 + 30976 + 5280, 352 * 72 + 30976 + 5280, 352 * 120 + 30
 IMAGE_4K_MODES = ("xrans128", "xrans64", "xrans32", "rans128", "rans64", "rans32", "wrans14", "xrans14")   # configs[3] leg: every mode gets its Delta bpp; the headline is the fastest within 0.001 bpp
 IMAGE_4K_HEADLINE = "xrans128"       # ... which tests/test_hip_parity.py::test_4k_image_oracle_parity checks against the oracle (the leg says if another mode won)
 LARGE_AC_BATCH = 512                 # the batch at which the reference-format container is also measured (untimed leg): >= 1536 streams in flight
+DUMP_SAMPLE = 1 << 22                # --dump-outputs: values kept of a larger output (16 MB as float32; two such arrays stay under 64 MB)
+DUMP_SEED = 20240607                 # ... at these seeded positions
 
 
 def parse_args(argv=None):
@@ -78,6 +86,13 @@ def parse_args(argv=None):
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=768)
     ap.add_argument("--container", default=DEFAULT_CONTAINER, help="auto (rANS xwide v4 streams, their number per image from the image size: default_container()), rans<M> / wrans<M> / xrans<M> (M streams of 64 / 128 / 256 lanes per image) or ac (torchac-compatible)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: encode / decode apart, the PCIe-inclusive legs, the profiled kernel "
+                         "timings (roofline, coder), the reference-format container and north-star check, the informational legs, the CPU baselines "
+                         "and, at N > 1, rank 0's solo companion run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's batch) to DIR/<name>.npy in float32 / float64: "
+                         "the decoded RGB and the container bytes (a fixed, seeded sample of each when larger than DUMP_SAMPLE values) and the segment lengths")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-torch-cpu", action="store_true", help="skip the PyTorch-CPU run of one image inside cpu_baseline (10-25 s)")
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed informational legs (profiling runs)")
@@ -129,6 +144,29 @@ def level_positions(H, W, lvl):
 def make_batch(B, H, W, seed0):
     import numpy as np
     return np.stack([np.random.default_rng(seed0 + i).integers(0, 256, size=(3, H, W), dtype=np.uint8) for i in range(B)])
+
+
+def dump_outputs(out_dir, rec, cont, seg):
+    """--dump-outputs: what a caller of the timed step receives from its last run -- the decoded RGB (decode) and the containers with their
+    segment lengths (encode) -- as .npy in float32 / float64, so that two builds can be compared output for output.  An output of more than
+    DUMP_SAMPLE values is sampled at DUMP_SEED's sorted positions (with replacement); the container bytes are image by image the first
+    seg.sum() bytes of its row (what llicti_amd.codec.container_to_bytestream_list reads), concatenated."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(flat):
+        if flat.size <= DUMP_SAMPLE:
+            return flat
+        return flat[np.sort(rng.integers(0, flat.size, size=DUMP_SAMPLE))]
+    seg_h = seg.cpu().numpy()
+    cont_h = cont.cpu().numpy()
+    used = np.concatenate([cont_h[b, :int(n)] for b, n in enumerate(seg_h.sum(axis=1))])
+    files = {"decoded_rgb": sample(rec.cpu().numpy().reshape(-1)).astype(np.float32),
+             "container_bytes": sample(used).astype(np.float32),
+             "segment_lengths": seg_h.astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def _latest_profile_json(name):
@@ -890,7 +928,7 @@ def main(argv=None):
     # BEFORE the process group forms -- the other ranks sit in the rendezvous and have not touched their GPUs -- so that the line can say
     # efficiency_like_for_like = value / (N x this) without mixing batch size or container with rank count.
     n1_companion = None
-    if world > 1 and rank == 0 and not args.no_n1_companion:
+    if world > 1 and rank == 0 and args.full and not args.no_n1_companion:
         n1_companion = solo_companion(torch, dev, B, H, W, args)
     rccl_ranks = 1
     if world > 1:
@@ -970,8 +1008,10 @@ def main(argv=None):
             fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / n
-    t_enc = timed(enc, max(1, min(3, args.steps)))
-    t_dec = timed(dec, max(1, min(3, args.steps)))
+    t_enc = t_dec = None
+    if args.full:
+        t_enc = timed(enc, max(1, min(3, args.steps)))
+        t_dec = timed(dec, max(1, min(3, args.steps)))
 
     # ---- the timed region: K steps, inputs / outputs resident in HBM
     barrier()
@@ -983,10 +1023,12 @@ def main(argv=None):
     barrier()
     elapsed = time.perf_counter() - t0
     codec.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec, cont, seg)
 
     elapsed_pcie = elapsed_pcie_serial = None
     pcie_spread, pcie_trace = None, None
-    if not args.no_pcie_legs:
+    if args.full and not args.no_pcie_legs:
         # ---- the same steps with the PCIe transfers inside (pinned host buffers): never `value`, reported beside it
         rgb_pin = torch.from_numpy(rgb_h).pin_memory()
         cont_pin = torch.empty((B, stride), dtype=torch.uint8).pin_memory()
@@ -1050,31 +1092,32 @@ def main(argv=None):
         del rgb_pin, cont_pin, seg_pin, rec_pin, last, pipe, pcie_pipeline
 
     # ---- dominant-kernel timing with HIP events on the launch stream, in extra (untimed) profiled steps
-    codec.set_profiling(True)
     cnn_ms, cnn_launches, call_ms = 0.0, 0, 0.0
     kernel_ms = {}                                   # per kernel group, encode and decode pass (HIP events around the launches)
     cnn_level_ms = [0.0] * 5                         # band-CNN time per level (both passes)
-    for name, fn in (("encode", enc), ("decode", dec)):
-        fn()
-        torch.cuda.synchronize()
-        ms, n = codec.last_timing()
-        cat, per = codec.last_timing_detail()
-        cnn_ms += ms[1]
-        cnn_launches += n
-        call_ms += ms[0]
-        kernel_ms[name] = {k: round(v, 3) for k, v in cat.items() if v > 0}
-        kernel_ms[name]["call"] = round(ms[0], 3)
-        for l, t in enumerate(codec.last_cnn_level_ms()):
-            cnn_level_ms[l] += t
-    codec.set_profiling(False)
+    if args.full:
+        codec.set_profiling(True)
+        for name, fn in (("encode", enc), ("decode", dec)):
+            fn()
+            torch.cuda.synchronize()
+            ms, n = codec.last_timing()
+            cat, per = codec.last_timing_detail()
+            cnn_ms += ms[1]
+            cnn_launches += n
+            call_ms += ms[0]
+            kernel_ms[name] = {k: round(v, 3) for k, v in cat.items() if v > 0}
+            kernel_ms[name]["call"] = round(ms[0], 3)
+            for l, t in enumerate(codec.last_cnn_level_ms()):
+                cnn_level_ms[l] += t
+        codec.set_profiling(False)
     assert abs(sum(MAC_PER_BAND) - MAC_PER_POSITION) == 0
 
     # ---- untimed: the reference-format (torchac-compatible) container on rank 0's batch -- Delta bpp of the timed container is
-    #      measured against it in EVERY line (meets_north_star); its first image is compared with the CPU oracle below
+    #      measured against it in EVERY --full line (meets_north_star); its first image is compared with the CPU oracle below
     legs_out = {}
     cont_ac0 = seg_ac0 = None
     ac_bytes = None
-    if rank == 0 and not args.no_ac_leg:
+    if rank == 0 and args.full and not args.no_ac_leg:
         r_ac, cont2, seg2 = Legs(torch, codec, dev).run(rgb, MODE_AC, reps=1, keep=True)
         ac_bytes = r_ac["bytes"]
         seg_ac0 = seg2[0].cpu().numpy()
@@ -1084,7 +1127,7 @@ def main(argv=None):
         del cont2, seg2
         codec._ws = None
     # ---- untimed informational legs (rank 0, N = 1 only, like cpu_baseline)
-    extras = (world == 1) and not args.no_extras and not args.no_ac_leg
+    extras = args.full and (world == 1) and not args.no_extras and not args.no_ac_leg
     if extras:
         legs = Legs(torch, codec, dev)
         # (2) rANS streams per image: speed against container overhead
@@ -1186,11 +1229,11 @@ def main(argv=None):
     # whole job: time = MAX over ranks, bytes / pixels = SUM over ranks (the only collectives of the run)
     coll_dev = dev if (world == 1 or args.backend == "nccl") else "cpu"
     agg = shard.aggregate(elapsed, total_bytes, B * H * W, device=coll_dev)
-    have_pcie = elapsed_pcie is not None
-    agg_pcie = shard.aggregate(elapsed_pcie if have_pcie else 1.0, 0, B * H * W, device=coll_dev)
-    agg_pcie_serial = shard.aggregate(elapsed_pcie_serial if have_pcie else 1.0, 0, B * H * W, device=coll_dev)
-    # per-rank detail (one small all_gather): own time of the timed steps, own pipelined PCIe-inclusive step, physical device
-    per = shard.gather_per_rank([elapsed, elapsed_pcie if have_pcie else elapsed, float(shard.device_identity(dev)), float(local_dev),
+    have_pcie = elapsed_pcie is not None              # the same on every rank (same arguments): the collectives below match
+    agg_pcie = shard.aggregate(elapsed_pcie, 0, B * H * W, device=coll_dev) if have_pcie else None
+    agg_pcie_serial = shard.aggregate(elapsed_pcie_serial, 0, B * H * W, device=coll_dev) if have_pcie else None
+    # per-rank detail (one small all_gather): own time of the timed steps, own pipelined PCIe-inclusive step (0: not measured), physical device
+    per = shard.gather_per_rank([elapsed, elapsed_pcie if have_pcie else 0.0, float(shard.device_identity(dev)), float(local_dev),
                                  float(-1 if numa["numa_node"] is None else numa["numa_node"]), float(numa["cpus_bound"])], device=coll_dev)
     idents = [int(p[2]) for p in per]
     per_rows, straggler = shard.per_rank_report([p[0] for p in per], [p[1] for p in per], B * H * W, args.steps, idents, [int(p[3]) for p in per],
@@ -1228,50 +1271,53 @@ def main(argv=None):
             "rccl_ranks": rccl_ranks, "ranks": world, "backend": (args.backend if world > 1 else None),
             "distinct_devices": n_distinct, "shared_gpu": bool(shared_gpu),
             "per_rank": per_rows, "straggler_ratio": straggler,
-            "n1_companion": n1_companion,
-            "efficiency_like_for_like": (round(value / (world * n1_companion["value"]), 4) if n1_companion and n1_companion.get("value") else None),
-            "efficiency_is": ("value / (N x n1_companion.value): rank 0 ALONE on its GPU, the same per-GPU batch and container, timed in this very run before the process "
-                              "group formed -- the driver's own N = 1 point is another batch size (24 against 32 at N = 8)" if world > 1 else None),
-            "value_is": "HBM-resident: inputs and containers in HBM when the timed region starts (the task's bench contract: a PCIe-inclusive rate is "
-                        "never `value`).  SURVEY 8(d)'s wording -- H2D of the RGB and D2H of the streams inside -- is value_pcie_inclusive, beside it",
-            "value_resident": round(value, 3),
-            "value_pcie_inclusive": round(agg_pcie["pixels"] / agg_pcie["elapsed_s"] / 1e6, 3) if have_pcie else None,
-            "value_pcie_serial": round(agg_pcie_serial["pixels"] / agg_pcie_serial["elapsed_s"] / 1e6, 3) if have_pcie else None,
-            "pcie_inclusive_repeats_mpix_s": pcie_spread, "pcie_pipeline_trace": pcie_trace,
-            "pcie_note": "same step with H2D of RGB + D2H of containers (encode) and H2D of containers + D2H of RGB (decode) inside "
-                         "the timed region, pinned host buffers, whole container stride copied; value_pcie_inclusive: transfers on their own "
-                         "HIP streams, double buffered, overlapped with compute (decode of step k-1 behind encode of step k), steady state = (long run - short run) / extra steps; value_pcie_serial: "
-                         "transfer, compute, transfer one after the other",
-            "enc_mpix_s": round(B * H * W / t_enc / 1e6, 3), "dec_mpix_s": round(B * H * W / t_dec / 1e6, 3),
             "bpp": round(agg["bpp"], 4),
-            "roofline": {"bound": "mfma", "kernel": "band_params_kernel<0|1|2> (fp32 MFMA 16x16x4)",
-                         "achieved": round(achieved, 3), "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_FP32_MATRIX_TFLOPS, 4), "traffic": pmc_traffic("band_params_kernel"),
-                         "frac_is": "from HIP events around the launches of one profiled encode + decode of THIS run (llicti_last_timing_detail): the events are "
-                                    "release points, so each span holds its launch's write-back and dispatch gap (~40 us of ~700) -- a few percent below frac_rocprof",
-                         "frac_rocprof": (lambda r: round(flops / (r["cnn_ms_per_step"] * 1e-3) / 1e12 / PEAK_FP32_MATRIX_TFLOPS, 4) if r and (B, H, W) == (24, 512, 768) else None)(cnn_rocprof()),
-                         "rocprof": cnn_rocprof(),
-                         "launches": cnn_launches, "kernel_ms_per_step": round(cnn_ms, 3),
-                         "call_ms_profiled": round(call_ms, 3),
-                         "flop_per_step": flops,
-                         # the WHOLE path against the MFMA roof (the step's algorithmic FLOP / the timed step)
-                         "whole_path_frac": round(flops / (elapsed / args.steps) / 1e12 / PEAK_FP32_MATRIX_TFLOPS, 4),
-                         "cnn_tflops_per_level": {f"level{l}": round(2.0 * MAC_PER_POSITION * level_positions(H, W, l) * B * 2 / (cnn_level_ms[l] * 1e-3) / 1e12, 2)
-                                                  for l in range(5) if cnn_level_ms[l] > 0},
-                         "kernel_ms": kernel_ms},
-            # "the coder itself is integer / latency-bound: report symbols/s" -- the step's coded symbols (3 colour channels of every
-            # pixel but the raw DC band) over the entropy coder's own kernels of the profiled encode / decode (HIP events around the launches)
-            "coder": (lambda nsym, e, d: {
-                "symbols_per_step": nsym,
-                "encode_gsym_s": round(nsym / ((e.get("rans_encode", 0.0) + e.get("ac", 0.0)) * 1e-3) / 1e9, 3) if (e.get("rans_encode", 0.0) + e.get("ac", 0.0)) > 0 else None,
-                "decode_gsym_s": round(nsym / ((d.get("rans_stage", 0.0) + d.get("rans_tail", 0.0) + d.get("ac", 0.0)) * 1e-3) / 1e9, 3)
-                                 if (d.get("rans_stage", 0.0) + d.get("rans_tail", 0.0) + d.get("ac", 0.0)) > 0 else None,
-                "encode_with_pairs_gsym_s": round(nsym / ((e.get("rans_encode", 0.0) + e.get("ac", 0.0) + e.get("cdf_pairs", 0.0)) * 1e-3) / 1e9, 3)
-                                            if (e.get("rans_encode", 0.0) + e.get("ac", 0.0) + e.get("cdf_pairs", 0.0)) > 0 else None,
-                "what": "encode: the rANS / range-coder kernel alone (its (c_low, c_high) pairs come from cdf_pairs_kernel: the second figure has both); decode: the "
-                        "stage launches + the tail -- the decoder evaluates the mixture CDF inside its symbol search, so this is search + coder"})(
-                3 * (H * W - (H // 32) * (W // 32)) * B, kernel_ms.get("encode", {}), kernel_ms.get("decode", {})),
         }
+        if args.full:
+            out.update({
+                "n1_companion": n1_companion,
+                "efficiency_like_for_like": (round(value / (world * n1_companion["value"]), 4) if n1_companion and n1_companion.get("value") else None),
+                "efficiency_is": ("value / (N x n1_companion.value): rank 0 ALONE on its GPU, the same per-GPU batch and container, timed in this very run before the process "
+                                  "group formed -- `bench.py --gpus 1` times another batch size (24 against 32 at N = 8)" if world > 1 else None),
+                "value_is": "HBM-resident: inputs and containers in HBM when the timed region starts (a PCIe-inclusive rate is "
+                            "never `value`).  SURVEY 8(d)'s wording -- H2D of the RGB and D2H of the streams inside -- is value_pcie_inclusive, beside it",
+                "value_resident": round(value, 3),
+                "value_pcie_inclusive": round(agg_pcie["pixels"] / agg_pcie["elapsed_s"] / 1e6, 3) if have_pcie else None,
+                "value_pcie_serial": round(agg_pcie_serial["pixels"] / agg_pcie_serial["elapsed_s"] / 1e6, 3) if have_pcie else None,
+                "pcie_inclusive_repeats_mpix_s": pcie_spread, "pcie_pipeline_trace": pcie_trace,
+                "pcie_note": "same step with H2D of RGB + D2H of containers (encode) and H2D of containers + D2H of RGB (decode) inside "
+                             "the timed region, pinned host buffers, whole container stride copied; value_pcie_inclusive: transfers on their own "
+                             "HIP streams, double buffered, overlapped with compute (decode of step k-1 behind encode of step k), steady state = (long run - short run) / extra steps; value_pcie_serial: "
+                             "transfer, compute, transfer one after the other",
+                "enc_mpix_s": round(B * H * W / t_enc / 1e6, 3), "dec_mpix_s": round(B * H * W / t_dec / 1e6, 3),
+                "roofline": {"bound": "mfma", "kernel": "band_params_kernel<0|1|2> (fp32 MFMA 16x16x4)",
+                             "achieved": round(achieved, 3), "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_FP32_MATRIX_TFLOPS, 4), "traffic": pmc_traffic("band_params_kernel"),
+                             "frac_is": "from HIP events around the launches of one profiled encode + decode of THIS run (llicti_last_timing_detail): the events are "
+                                        "release points, so each span holds its launch's write-back and dispatch gap (~40 us of ~700) -- a few percent below frac_rocprof",
+                             "frac_rocprof": (lambda r: round(flops / (r["cnn_ms_per_step"] * 1e-3) / 1e12 / PEAK_FP32_MATRIX_TFLOPS, 4) if r and (B, H, W) == (24, 512, 768) else None)(cnn_rocprof()),
+                             "rocprof": cnn_rocprof(),
+                             "launches": cnn_launches, "kernel_ms_per_step": round(cnn_ms, 3),
+                             "call_ms_profiled": round(call_ms, 3),
+                             "flop_per_step": flops,
+                             # the WHOLE path against the MFMA roof (the step's algorithmic FLOP / the timed step)
+                             "whole_path_frac": round(flops / (elapsed / args.steps) / 1e12 / PEAK_FP32_MATRIX_TFLOPS, 4),
+                             "cnn_tflops_per_level": {f"level{l}": round(2.0 * MAC_PER_POSITION * level_positions(H, W, l) * B * 2 / (cnn_level_ms[l] * 1e-3) / 1e12, 2)
+                                                      for l in range(5) if cnn_level_ms[l] > 0},
+                             "kernel_ms": kernel_ms},
+                # "the coder itself is integer / latency-bound: report symbols/s" -- the step's coded symbols (3 colour channels of every
+                # pixel but the raw DC band) over the entropy coder's own kernels of the profiled encode / decode (HIP events around the launches)
+                "coder": (lambda nsym, e, d: {
+                    "symbols_per_step": nsym,
+                    "encode_gsym_s": round(nsym / ((e.get("rans_encode", 0.0) + e.get("ac", 0.0)) * 1e-3) / 1e9, 3) if (e.get("rans_encode", 0.0) + e.get("ac", 0.0)) > 0 else None,
+                    "decode_gsym_s": round(nsym / ((d.get("rans_stage", 0.0) + d.get("rans_tail", 0.0) + d.get("ac", 0.0)) * 1e-3) / 1e9, 3)
+                                     if (d.get("rans_stage", 0.0) + d.get("rans_tail", 0.0) + d.get("ac", 0.0)) > 0 else None,
+                    "encode_with_pairs_gsym_s": round(nsym / ((e.get("rans_encode", 0.0) + e.get("ac", 0.0) + e.get("cdf_pairs", 0.0)) * 1e-3) / 1e9, 3)
+                                                if (e.get("rans_encode", 0.0) + e.get("ac", 0.0) + e.get("cdf_pairs", 0.0)) > 0 else None,
+                    "what": "encode: the rANS / range-coder kernel alone (its (c_low, c_high) pairs come from cdf_pairs_kernel: the second figure has both); decode: the "
+                            "stage launches + the tail -- the decoder evaluates the mixture CDF inside its symbol search, so this is search + coder"})(
+                    3 * (H * W - (H // 32) * (W // 32)) * B, kernel_ms.get("encode", {}), kernel_ms.get("decode", {})),
+            })
         if ac_bytes is not None:
             fx, fx_path = _latest_profile_json("bpp_delta_fixtures.json")
             ac_bpp = legs_out["ac_container"]["bpp"]
@@ -1316,7 +1362,7 @@ def main(argv=None):
             out["north_star_check"]["natural_like_budget_bpp"] = nl["bpp_delta_budget_image0"]
             out["north_star_check"]["natural_like_ok"] = ok_nl
             out["meets_north_star"] = bool(out["meets_north_star"] and ok_nl)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb, bl = cpu_baseline(H, W)
             if cont_ac0 is not None:
                 # the same image through the HIP path (reference-format container) must give the oracle's bytes

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""rocprofv3 *_kernel_stats.csv of `bench.py --steps S --warmup W --no-cpu-baseline --no-extras --no-pcie-legs [--no-ac-leg]` -> the band-CNN time
+"""rocprofv3 *_kernel_stats.csv of `bench.py --full --steps S --warmup W --no-cpu-baseline --no-extras --no-pcie-legs [--no-ac-leg]` -> the band-CNN time
 per step (encode + decode pass), for bench.py's `roofline.frac_rocprof`.  The run holds (1 check + W warm-up + 3 + 3 timed halves ... ) encode /
 decode pairs; their number is taken from the trace itself: every pass has exactly 15 band-CNN launches and one lift (encode) or unlift (decode).
 Usage: python tools/cnn_rocprof.py <..._kernel_stats.csv> <out.json> "<command>" """
