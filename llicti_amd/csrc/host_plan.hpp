@@ -135,15 +135,18 @@ static int rans_byte0(int M, int Q);
 static int rans_pad_hi(int M, int Q);
 
 // Ms: B stream counts (rANS containers: the images of a call may have different ones -- every header carries its own -- so that larger images
-// get more streams and a stage launch does not wait for its largest image), or nullptr = ME's count for every image.
+// get more streams and a stage launch does not wait for its largest image), each | 0x1000 if that image is "auto" (ME then has 0x1000 if any
+// image is), or nullptr = ME's count and kind for every image.  Fixed and "auto" xwide images may share a call: a fixed one has Mlo = 0.
 static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, int n_cu = 256, int tile_rows = 0, bool force_ragged = false,
                        const int *Ms = nullptr)
 {
     const int Q = 1 << ((ME >> 8) & 3);
-    const bool autoM = (ME & 0x1000) != 0;      // LLICTI_MODE_RANS_X_AUTO: the counts are the size rule's (Mlo); the encoder picks per image in [rans_auto_min, rans_auto_hi]
-    int M = ME & 0xFF;
-    if (Ms && M > 0) { M = 0; for (int b = 0; b < B; ++b) M = std::max(M, Ms[b]); }
-    if (autoM) M = rans_auto_hi(M);
+    const bool per_image = Ms && (ME & 0xFF) > 0;
+    auto m_of = [&](int b) -> int { return per_image ? (Ms[b] & 0xFF) : (ME & 0xFF); };
+    // LLICTI_MODE_RANS_X_AUTO: the count is the size rule's (Mlo); the encoder picks per image in [rans_auto_min, rans_auto_hi]
+    auto auto_of = [&](int b) -> bool { return ((per_image ? Ms[b] : ME) & 0x1000) != 0; };
+    int M = 0;
+    for (int b = 0; b < B; ++b) M = std::max(M, auto_of(b) ? rans_auto_hi(m_of(b)) : m_of(b));
     p.B = B; p.ME = ME; p.M = M; p.Q = Q;
     p.uniform = !force_ragged;
     for (int b = 1; b < B; ++b) if (Hs[b] != Hs[0] || Ws[b] != Ws[0]) p.uniform = false;
@@ -156,7 +159,6 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     p.key.clear();
     p.key.reserve(3 + 4 * (size_t)B);
     p.key.push_back(ME); p.key.push_back(B); p.key.push_back(tile_rows * 2 + (force_ragged ? 1 : 0));
-    auto m_of = [&](int b) -> int { return (Ms && (ME & 0xFF) > 0) ? Ms[b] : (ME & 0xFF); };
     // images: sizes, header constants, placement (mixed sizes: planes / fplanes blocks start at multiples of 64 elements; equal sizes: tightly
     // packed, [B][3][H][W] -- what the division form of the band CNN and the AC container's kernels index)
     p.img.assign(B, ImgGeo{});
@@ -175,11 +177,11 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
         if ((ig.plane & 3) || (ig.rgb_off & 3)) p.vec_ok = false;
         p.rgb_bytes = std::max(p.rgb_bytes, (size_t)(ig.rgb_off + 3 * ig.plane));
         p.max_plane = std::max(p.max_plane, ig.plane);
-        ig.Mlo = autoM ? m_of(b) : 0;
-        ig.M = autoM ? rans_auto_hi(ig.Mlo) : m_of(b);
+        ig.Mlo = auto_of(b) ? m_of(b) : 0;
+        ig.M = auto_of(b) ? rans_auto_hi(ig.Mlo) : m_of(b);
         ig.byte0 = ig.M ? rans_byte0(ig.M, Q) : LLICTI_NLEVELS;
         ig.padint = pad_int(ig.H, ig.W) | ((ig.M ? rans_pad_hi(ig.M, Q) : 0) << 10);      // the header's int16 pad field (xwide v4: its high bits carry the stream count; an "auto" encode writes the count it picked)
-        p.key.push_back(ig.H); p.key.push_back(ig.W); p.key.push_back(ig.rgb_off); p.key.push_back(m_of(b));
+        p.key.push_back(ig.H); p.key.push_back(ig.W); p.key.push_back(ig.rgb_off); p.key.push_back(per_image ? Ms[b] : (ME & 0xFF));
     }
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
@@ -390,15 +392,19 @@ static int check_dims_v(int B, const int *Hs, const int *Ws)
 static size_t plan_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes, int n_modes)
 {
     if (check_dims_v(B, Hs, Ws) || !modes || (n_modes != 1 && n_modes != B)) return 0;
-    const int ME = mode_streams(modes[0]);
+    int ME = mode_streams(modes[0]);
     if (ME < 0) return 0;
     std::vector<int> Ms;
-    if (n_modes == B && B > 1)
+    if (n_modes == B && B > 1) {
+        bool any_auto = false;
         for (int b = 0; b < B; ++b) {
             const int MEb = mode_streams(modes[b]);
-            if (MEb < 0 || (MEb >> 8) != (ME >> 8) || ((MEb & 0xFF) == 0) != ((ME & 0xFF) == 0)) return 0;      // (one lane kind per call -- and all "auto" or none)
-            Ms.push_back(MEb & 0xFF);
+            if (MEb < 0 || ((MEb >> 8) & 3) != ((ME >> 8) & 3) || ((MEb & 0xFF) == 0) != ((ME & 0xFF) == 0)) return 0;      // (one lane kind per call; fixed and "auto" counts may mix)
+            Ms.push_back(MEb & 0x10FF);
+            any_auto = any_auto || (MEb & 0x1000);
         }
+        if (any_auto) ME |= 0x1000;
+    }
     Plan p, q;
     build_plan(p, B, Hs, Ws, nullptr, ME, 256, 0, false, Ms.empty() ? nullptr : Ms.data());
     build_plan(q, B, Hs, Ws, nullptr, ME, 256, 0, true, Ms.empty() ? nullptr : Ms.data());      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)

@@ -720,8 +720,9 @@ struct PlanUse {
     ~PlanUse() { if (pd && hipEventRecord(pd->blk.done, s) == hipSuccess) { pd->blk.used = true; pd->blk.done_stream = s; } }
 };
 
-// modes: one container mode for the call (n_modes = 1) or one per image (n_modes = B: rANS containers of ONE lane kind whose stream counts may differ);
-// -> ME of the call (the lane kind, with the first image's count) and, for per-image counts, Ms
+// modes: one container mode for the call (n_modes = 1) or one per image (n_modes = B: rANS containers of ONE lane kind whose stream counts may differ,
+// fixed and "auto" xwide counts mixed); -> ME of the call (the lane kind, with the first image's count, | 0x1000 if any image is "auto") and, for
+// per-image modes, Ms (count | 0x1000 for an "auto" image: build_plan)
 static int resolve_modes(const char *who, const int *modes, int n_modes, int B, int *ME_out, std::vector<int> &Ms)
 {
     Ms.clear();
@@ -730,16 +731,18 @@ static int resolve_modes(const char *who, const int *modes, int n_modes, int B, 
     if (ME0 < 0) return fail(LLICTI_EINVAL, "%s: unknown mode 0x%x", who, modes[0]);
     *ME_out = ME0;
     if (n_modes == 1) return 0;
-    bool differ = false;
+    bool differ = false, any_auto = false;
     for (int b = 0; b < B; ++b) {
         const int ME = mode_streams(modes[b]);
         if (ME < 0) return fail(LLICTI_EINVAL, "%s: unknown mode 0x%x of image %d", who, modes[b], b);
-        if ((ME >> 8) != (ME0 >> 8) || ((ME & 0xFF) == 0) != ((ME0 & 0xFF) == 0))
+        if (((ME >> 8) & 3) != ((ME0 >> 8) & 3) || ((ME & 0xFF) == 0) != ((ME0 & 0xFF) == 0))
             return fail(LLICTI_EINVAL, "%s: the images of one call share a container kind (reference format, or rANS streams of one lane count); image %d differs", who, b);
-        Ms.push_back(ME & 0xFF);
+        Ms.push_back(ME & 0x10FF);
         differ = differ || ME != ME0;
+        any_auto = any_auto || (ME & 0x1000);
     }
     if (!differ) Ms.clear();
+    else if (any_auto) *ME_out |= 0x1000;      // (the call runs the encoder's stream-count pick; images with Mlo = 0 keep their fixed count)
     return 0;
 }
 

@@ -1798,8 +1798,9 @@ __global__ __launch_bounds__(256) void rans_pack_kernel(const uint8_t *__restric
     const StreamRef sr_ = sref[blockIdx.x];
     const int b = sr_.b, m = sr_.m, M = image_stream_count(ssum, iv, desc, B, sr_.b, sr_.M), s0 = sr_.sbase;      // (s0 + k: stream k of this image)
     const int hdr_bytes = iv[b].hdr_bytes;
-    if (ssum && m == 0 && threadIdx.x == 0) {
+    if (ssum && iv[b].Mlo && m == 0 && threadIdx.x == 0) {
         // "auto": the header was written before the count was picked -- the pad field's bits 10 .. 15 say how many streams the image has
+        // (an image of a fixed count in the same call, Mlo = 0, keeps the field header_write_kernel wrote: 64 / 128 streams have codes of their own there)
         uint8_t *oh = out + (long)b * out_stride;
         const int pf = (iv[b].padint & 0x3FF) | (M << 10);              // (auto counts are <= 32: the field holds them as they are)
         oh[15] = (uint8_t)(pf & 0xFF); oh[16] = (uint8_t)((pf >> 8) & 0xFF);

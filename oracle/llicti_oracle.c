@@ -147,6 +147,13 @@ void orc_cdf_row(const float *par, int clr, float yv, float cov, int minv, int m
     for (int i = 0; i < Lp; ++i) row[i] = cdf_entry(&m, i, Lp, minv, maxv);
 }
 
+void orc_cdf_rows(const float *par, int clr, const float *yv, const float *cov, long n, int minv, int maxv, uint16_t *rows)
+{
+    const int Lp = maxv - minv + 2;
+#pragma omp parallel for schedule(static) num_threads(nthreads())
+    for (long r = 0; r < n; ++r) orc_cdf_row(par + r * ORC_NPAR, clr, yv[r], cov[r], minv, maxv, rows + r * Lp);
+}
+
 float orc_cdf_float(const float *par, int clr, float yv, float cov, float pt)
 {
     mix_t m;

@@ -83,6 +83,8 @@ void orc_selfinfo(const float *fplanes, int H, int W, int lvl, int band, const f
  * (cross-channel mean update, LLICTI_nets.py:389-392); row gets Lp = maxv-minv+2 uint16 entries. */
 void orc_cdf_row(const float *par, int clr, float yv, float cov, int minv, int maxv, uint16_t *row);
 /* float mixture CDF at one sample point, before integerisation (for tolerance checks) */
+/* orc_cdf_row for n positions: par [n][60], yv / cov [n], rows [n][maxv - minv + 2] */
+void orc_cdf_rows(const float *par, int clr, const float *yv, const float *cov, long n, int minv, int maxv, uint16_t *rows);
 float orc_cdf_float(const float *par, int clr, float yv, float cov, float pt);
 float orc_erfc(float x);        /* the spec's erfc, exported for unit tests */
 

@@ -161,6 +161,18 @@ def cdf_row(par, clr, yv, cov, minv, maxv):
     return row
 
 
+def cdf_rows(par, clr, yv, cov, minv, maxv):
+    """cdf_row of n positions at once: par [n, 60], yv / cov [n] (fp32) -> uint16 [n, maxv - minv + 2]."""
+    par = np.ascontiguousarray(par, dtype=np.float32).reshape(-1, 60)
+    yv = np.ascontiguousarray(yv, dtype=np.float32).ravel()
+    cov = np.ascontiguousarray(cov, dtype=np.float32).ravel()
+    n = par.shape[0]
+    assert yv.size == n and cov.size == n
+    rows = np.empty((n, maxv - minv + 2), np.uint16)
+    lib().orc_cdf_rows(_p(par), clr, _p(yv), _p(cov), C.c_long(n), minv, maxv, _p(rows))
+    return rows
+
+
 def cdf_float(par, clr, yv, cov, pt):
     par = np.ascontiguousarray(par, dtype=np.float32)
     return float(lib().orc_cdf_float(_p(par), clr, C.c_float(yv), C.c_float(cov), C.c_float(pt)))

@@ -48,3 +48,40 @@ def xwide_stream_header(stream: bytes):
     v = int.from_bytes(stream[:nbytes], "little")
     f9 = (v >> (top - 9)) & 0x1FF
     return f9 & 0xFF, f9 >> 8, top - 9
+
+
+# Shapes whose band grids put the band CNN's input halo exactly on the last row / column its fast staging path accepts (h - 2, w - 2) and on the
+# first one it refuses (h - 1, w - 1), for every tile form, at both parities of the level grid (tile_edge_classes): the tile-edge sweep of
+# tests/test_ref64_cpu.py and tests/test_hip_tile_edges.py.  Found by a greedy search over H in 64..200, W in 64..260.
+SWEEP_SHAPES = [(H, W) for H in (67, 68, 69, 70) for W in (133, 134, 195, 196)]
+TILE_ROWS = (16, 8, 4)            # the band CNN's tile forms (rows; 32 columns each)
+
+
+def tile_edge_classes(H, W, levels=(0, 1, 2)):
+    """Set of (TH, row class, column class, Hl & 1, Wl & 1) the band CNN's tiles of an H x W image fall into at the given levels.  A tile of TH rows
+    stages rows ty TH - 2 .. ty TH + TH + 1 and columns 32 tx - 2 .. 32 tx + 33 of the band grid h x w (llicti_amd/csrc/band_cnn.hpp); the
+    fast path takes it if they lie inside the grid and end at h - 2 / w - 2 at the latest.  Row class: "fast" (ends at h - 2: the last tile
+    accepted) or "border" (ends at h - 1: the first refused); column class: "fast_edge", "border_edge" or "interior" (a fast column range ending
+    before w - 2).  Tiles of no class (ending elsewhere) are not counted."""
+    out = set()
+    for lvl in levels:
+        st = 1 << lvl
+        Hl, Wl = -(-H // st), -(-W // st)
+        h, w = (Hl + 1) // 2, (Wl + 1) // 2
+        for TH in TILE_ROWS:
+            for ty in range(-(-h // TH)):
+                i0, i1 = ty * TH - 2, ty * TH + TH + 1
+                rc = "fast" if (i0 >= 0 and i1 == h - 2) else "border" if i1 == h - 1 else None
+                if rc is None:
+                    continue
+                for tx in range(-(-w // 32)):
+                    j0, j1 = 32 * tx - 2, 32 * tx + 33
+                    cc = "fast_edge" if (j0 >= 0 and j1 == w - 2) else "border_edge" if j1 == w - 1 else "interior" if (j0 >= 0 and j1 < w - 2) else None
+                    if cc is not None:
+                        out.add((TH, rc, cc, Hl & 1, Wl & 1))
+    return out
+
+
+def all_tile_edge_classes():
+    return {(TH, rc, cc, ph, pw) for TH in TILE_ROWS for rc in ("fast", "border") for cc in ("fast_edge", "border_edge", "interior")
+            for ph in (0, 1) for pw in (0, 1)}

@@ -2147,10 +2147,11 @@ def test_mixed_size_entry_points_reject_misuse(torch_mod, codecs):
     assert np.array_equal(rec.cpu().numpy(), _flat(rgbs))
 
 
-def test_mixed_size_batch_stream_count_per_image(torch_mod, codecs, oracle_weights):
+def test_mixed_size_batch_stream_count_per_image_fixed_and_auto(torch_mod, codecs, oracle_weights):
     """llicti_encode_images_vm / llicti_decode_images_vm: one container mode PER IMAGE -- rANS streams of one lane kind whose COUNT differs from image
     to image (every header carries its own): image b's bytes are those of its own single-image encode in modes[b] and the oracle's; lossless on a
-    poisoned workspace; container "auto" gives each image a count from its own size; lane kinds must not be mixed, nor the reference format with rANS."""
+    poisoned workspace; container "auto" gives each image a count from its own size, and "auto" counts may share a call with fixed xwide ones;
+    lane kinds must not be mixed, nor the reference format with rANS."""
     from llicti_amd import _lib
     from llicti_amd.codec import MODE_AC, MODE_RANS, container_to_bytestream_list
     from oracle import oracle as orc
@@ -2180,8 +2181,9 @@ def test_mixed_size_batch_stream_count_per_image(torch_mod, codecs, oracle_weigh
         c.encode_v(flat, Hs, Ws, [MODE_RANS(2, wide=2)] * 5 + [MODE_RANS(2, wide=1)])
     with pytest.raises(_lib.LlictiError):
         c.encode_v(flat, Hs, Ws, [MODE_RANS(2)] * 5 + [MODE_AC])
-    # container "auto" on a batch at the reference's eval-set sizes: each image's count from its own size, streams of about equal length, and with
-    # the "auto" ENCODER modes mixed with fixed ones refused (all of a call or none)
+    # container "auto" on a batch at the reference's eval-set sizes: each image's count from its own size, streams of about equal length; and the
+    # "auto" ENCODER modes mixed with fixed xwide counts in one call (what container "auto" gives a >= 4.3 MP image beside smaller ones): each
+    # image's container is its own single-image one and the oracle's, and the batch decodes losslessly
     import json
     import os
     from conftest import GOLDEN
@@ -2192,8 +2194,20 @@ def test_mixed_size_batch_stream_count_per_image(torch_mod, codecs, oracle_weigh
     assert all(m == MODE_RANS_AUTO(image_streams(h, w)) for m, (h, w) in zip(bm, sh))
     per = [h * w / m for m, (h, w) in zip(Mb, sh)]
     assert max(per) / min(per) < 1.35                                  # about equally long streams (one count for all: 2.2)
-    with pytest.raises(_lib.LlictiError):
-        c.encode_v(flat, Hs, Ws, [MODE_RANS_AUTO(2)] * 5 + [MODE_RANS(2, wide=2)])
+    mix = [MODE_RANS_AUTO(2)] * 5 + [MODE_RANS(2, wide=2)]
+    cont, seg = c.encode_v(flat, Hs, Ws, mix)
+    c.check()
+    cont_h, seg_h = cont.cpu().numpy(), seg.cpu().numpy()
+    for b, rgb in enumerate(rgbs):
+        c1, s1 = c.encode(_dev(torch, rgb[None]), mode=mix[b])
+        n = int(seg_h[b].sum())
+        assert np.array_equal(seg_h[b], s1[0].cpu().numpy()) and np.array_equal(cont_h[b, :n], c1[0, :n].cpu().numpy()), ("mix", b)
+        if b in (0, 5):
+            assert container_to_bytestream_list(cont_h[b], seg_h[b]) == orc.encode_image_rans(rgb, W_o, 2, 2, auto=b < 5), ("mix", b)
+    c.poison_workspace()
+    rec = c.decode_v(cont, seg, Hs, Ws, c.container_modes(cont))
+    c.check()
+    assert np.array_equal(rec.cpu().numpy(), _flat(rgbs)), "mix"
     with pytest.raises(_lib.LlictiError):
         c.decode_v(cont, seg, Hs, Ws, [MODE_RANS_AUTO(2)] * 6)         # an encoder's mode: a decoder takes the container's own
     c.check()
