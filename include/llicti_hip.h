@@ -77,8 +77,17 @@ const char *llicti_version(void);
 int llicti_create(llicti_ctx **ctx, int device);
 int llicti_destroy(llicti_ctx *ctx);
 
-/* Upload one band network in canonical packed form (host pointers, float32):
- *   w0 [352][K0] (K0 = 48 / 72 / 120), b0 [352], w1 [352][88], b1 [352], w2 [60][88], b2 [60].
+/* Model shape of the context: head = channels per head (chs[0]), nlevels = wavelet levels.  This build runs exactly the reference's two
+ * configurations: (88, 5) = configs/llicti_A.json, the default of a new context, and (60, 2) = configs/llicti_B.json.  Anything else is
+ * LLICTI_EINVAL.  Changing the shape drops the context's weights (llicti_set_band_weights again) and cached plans.  Under config B the container
+ * has 4 + 9 x 2 = 22 segments (the DC band is level 1's x00), the level-indexed entry points take lvl 0 .. 1, and the whole-batch calls take
+ * LLICTI_MODE_AC and LLICTI_MODE_RANS_X(1 .. 18) / LLICTI_MODE_RANS_X_AUTO(1 .. 13) (LLICTI_EINVAL otherwise) on images of at most 1020
+ * pixels per side (the header stores level 1's grid in one byte each).  A context refuses the other model's containers (LLICTI_EFORMAT per
+ * image): config B's reference-format header has byte 0 = 2 (its number of scales), its xwide v4 header byte 0 = 0xE9. */
+int llicti_set_model(llicti_ctx *ctx, int head, int nlevels);
+
+/* Upload one band network in canonical packed form (host pointers, float32), for the context's model (head h = 88 or 60):
+ *   w0 [4h][K0] (K0 = 48 / 72 / 120), b0 [4h], w1 [4h][h], b1 [4h], w2 [60][h], b2 [60].
  * Replaces LLICTIEntropyModel4.__init__ / load_state_dict for the eval path
  * (LLICTI_nets.py:651-675, :695-712; agents/base.py:51-76). */
 int llicti_set_band_weights(llicti_ctx *ctx, int band, int K0, const float *w0, const float *b0,
@@ -194,6 +203,10 @@ size_t llicti_workspace_bytes_v(int B, const int *Hs, const int *Ws, int mode);
 size_t llicti_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes);      /* one mode per image, see llicti_encode_images_vm */
 /* Upper bound of the container size of ONE image: the minimum out_stride / in_stride. */
 size_t llicti_max_container_bytes(int H, int W);
+/* The same two sizes for the context's model (llicti_set_model; the functions above size config A): modes holds one mode (n_modes = 1) or
+ * one per image (n_modes = B). */
+size_t llicti_workspace_bytes_ctx(const llicti_ctx *ctx, int B, const int *Hs, const int *Ws, const int *modes, int n_modes);
+size_t llicti_max_container_bytes_ctx(const llicti_ctx *ctx, int H, int W);
 
 int llicti_encode_images(llicti_ctx *ctx, const uint8_t *d_rgb, int B, int H, int W, int mode,
                          void *d_workspace, size_t workspace_bytes,

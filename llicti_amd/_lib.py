@@ -47,6 +47,9 @@ _SIGS = {
     "llicti_create": (_i, [C.POINTER(_vp), _i]),
     "llicti_destroy": (_i, [_vp]),
     "llicti_set_band_weights": (_i, [_vp, _i, _i] + [_vp] * 6),
+    "llicti_set_model": (_i, [_vp, _i, _i]),
+    "llicti_workspace_bytes_ctx": (_sz, [_vp, _i, _vp, _vp, _vp, _i]),
+    "llicti_max_container_bytes_ctx": (_sz, [_vp, _i, _i]),
     "llicti_level_geom": (_i, [_i, _i, _i, _i] + [C.POINTER(_i)] * 8),
     "llicti_lift_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "llicti_unlift_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -174,6 +174,7 @@ class LLICTIAgent:
             self.test_logger(rate1_list)
             self._log_image(idx, H, W, bpsp, enc_time, dec_time, maxx_abserr)
         else:
+            nbytes = nbytes + [0] * (54 - len(nbytes))          # (config B: 27 lengths; the record is config A's 54 wide)
             self._records.append([float(idx), float(H), float(W), float(enc_time), float(dec_time), float(maxx_abserr)] + [float(n) for n in nbytes])
         return r
 
@@ -191,7 +192,7 @@ class LLICTIAgent:
             for row in sorted(rec.tolist(), key=lambda r: r[0]):
                 idx, H, W = int(row[0]), int(row[1]), int(row[2])
                 lens = [int(v) for v in row[6:]]
-                rate1_list = [[n * 8 / (3 * H * W) * 3 for n in lens[9 * k:9 * k + 9]] for k in range(6)]    # CompressionRLossList on the lengths
+                rate1_list = [[n * 8 / (3 * H * W) * 3 for n in lens[9 * k:9 * k + 9]] for k in range(1 + len(self.config.dwtlevels))]    # CompressionRLossList on the lengths
                 self.test_logger(rate1_list)
                 bpsp = sum(lens) * 8 / (3 * H * W)
                 self._log_image(idx, H, W, bpsp, row[3], row[4], row[5])

@@ -1,9 +1,12 @@
 """python -m llicti_amd.cli encode IN.(png|ppm|jpg) OUT.llic [--container ac|auto|rans<M>|wrans<M>|xrans<M>] [--checkpoint model_best.pth.tar]
-   python -m llicti_amd.cli decode IN.llic OUT.(png|ppm)
+                                [--config llicti_B.json]
+   python -m llicti_amd.cli decode IN.llic OUT.(png|ppm) [--checkpoint model_best.pth.tar] [--config llicti_B.json]
    python -m llicti_amd.cli info   IN.llic
 
 File-level front end of the MI355X hot path (needs a GPU: there is no CPU fallback).  Without a checkpoint the
-seed-1337 default init is used, as the reference does when `model_best.pth.tar` is missing (agents/base.py:78-80)."""
+seed-1337 default init is used, as the reference does when `model_best.pth.tar` is missing (agents/base.py:78-80).  --config names the
+reference's JSON file the model was trained with (configs/llicti_A.json -- the default -- or llicti_B.json): as the reference's README says,
+compress and decompress with the json file that was used to train the model."""
 from __future__ import annotations
 
 import argparse
@@ -13,12 +16,16 @@ import time
 import numpy as np
 
 
-def _model(container, checkpoint):
+def _model(container, checkpoint, config_path=None):
     import torch
-    from .config import default_config
+    from .config import default_config, load_json
     from .graphs.models.LLICTI_nets import LLICTI
     torch.manual_seed(1337)
-    model = LLICTI(default_config(container=container)).to("cuda:0").eval()
+    cfg = default_config(container=container)
+    if config_path:
+        cfg.update(load_json(config_path))          # the model's keys of the JSON file; the container stays the command line's
+        cfg["container"] = container
+    model = LLICTI(cfg).to("cuda:0").eval()
     if checkpoint:
         from .weights import load_reference_state_dict
         load_reference_state_dict(model, torch.load(checkpoint, map_location="cuda:0")["state_dict"])
@@ -29,8 +36,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="llicti_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("encode"); e.add_argument("src"); e.add_argument("dst")
-    e.add_argument("--container", default="ac"); e.add_argument("--checkpoint", default=None)
+    e.add_argument("--container", default="ac"); e.add_argument("--checkpoint", default=None); e.add_argument("--config", default=None)
     d = sub.add_parser("decode"); d.add_argument("src"); d.add_argument("dst"); d.add_argument("--checkpoint", default=None)
+    d.add_argument("--config", default=None)
     i = sub.add_parser("info"); i.add_argument("src")
     a = ap.parse_args(argv)
     from . import fileio
@@ -44,7 +52,7 @@ def main(argv=None):
         return 0
     if a.cmd == "encode":
         rgb = fileio.read_image(a.src)
-        model, torch = _model(a.container, a.checkpoint)
+        model, torch = _model(a.container, a.checkpoint, a.config)
         x = torch.from_numpy(rgb.astype(np.float32) / np.float32(255)).unsqueeze(0).to("cuda:0")
         t0 = time.time()
         bl, _ = model.compress(x)
@@ -55,7 +63,7 @@ def main(argv=None):
         print(f"{a.src} -> {a.dst}: {rgb.shape[2]}x{rgb.shape[1]}, {n} bytes, {8.0 * n / (rgb.shape[1] * rgb.shape[2]):.4f} bpp, {dt:.3f} s")
         return 0
     bl = fileio.read_llic(a.src)
-    model, torch = _model("ac", a.checkpoint)
+    model, torch = _model("ac", a.checkpoint, a.config)
     t0 = time.time()
     x = model.decompres(bl, torch.device("cuda:0"))
     torch.cuda.synchronize()

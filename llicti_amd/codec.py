@@ -17,8 +17,11 @@ import torch
 from . import _lib
 from .weights import pack_state_dict
 
-NSEG = 49
-MODE_AC = 0                      # the reference's container: 45 torchac-algorithm streams per image
+NSEG = 49                        # segment lengths per image in the C-ABI: config A's 4 + 45 (config B uses the first 4 + 18, the rest are 0)
+MODE_AC = 0                      # the reference's container: 45 torchac-algorithm streams per image (config B: 18)
+MODELS = {88: 5, 60: 2}          # head width -> wavelet levels: config A, config B (configs/llicti_{A,B}.json)
+B_MAX_STREAMS = 18               # config B: xwide streams per image (one per container segment; 9 x 2 levels)
+B_MAX_AUTO = 13                  # ... and the largest size-rule count of its "auto" mode (auto_counts(13)[-1] = 18)
 
 
 # ---- container "auto": a PURE FUNCTION OF THE IMAGE'S SIZE (round 6).  Round 5's rule also looked at the batch size, the compute-unit count and -- through a
@@ -41,7 +44,7 @@ def last_stage_bits(seg_len, H, W):
     return 8.0 * float(seg_len[NSEG - 1]) / max(1, (H // 2) * (W // 2))
 
 
-def image_streams(H, W):
+def image_streams(H, W, nlevels=5):
     """xwide v4 streams of an H x W image in container "auto" -- a function of the size alone.  Two limits.  BYTES: M streams cost about
     STREAM_BYTES_BUDGETED M over the ideal code length, the reference format's terminations AC_TERMINATION_BYTES, and the north star's 0.001 bpp
     are H W / 8000 bytes (tests/test_oracle_golden.py::test_auto_container_budget_by_size holds the oracle's sizes against it).  PAYLOAD: a
@@ -49,6 +52,12 @@ def image_streams(H, W):
     fits (auto_container falls back to one 64-lane stream or the reference format).  More than 32 streams come as 64 or 128 (two / four per
     container segment behind a table of their lengths)."""
     nc_last = (H // 2) * (W // 2)                 # coded positions of level 0, band x10
+    if nlevels != 5:
+        # config B: AC_TERMINATION_BYTES is 24 bytes of range-coder terminations for config A's 45 streams less 1.5 bytes by which the two
+        # formats' tables differ (its comment above); config B's reference format has 9 L = 18 streams, so 24 * 18 / 45 = 9.6 bytes of
+        # terminations, less the same 1.5.  The count stays within B_MAX_AUTO.
+        budget = H * W / 8000.0 + (AC_TERMINATION_BYTES + 1.5) * 9 * nlevels / 45 - 1.5
+        return max(0, min(int(budget / STREAM_BYTES_BUDGETED), nc_last // XWIDE_MIN_SHARE, B_MAX_AUTO))
     budget = H * W / 8000.0 + AC_TERMINATION_BYTES
     m = min(int(budget / STREAM_BYTES_BUDGETED), nc_last // XWIDE_MIN_SHARE)
     if m > 32:
@@ -59,12 +68,14 @@ def image_streams(H, W):
     return max(0, m)
 
 
-def image_mode(H, W, mixed=False):
+def image_mode(H, W, mixed=False, nlevels=5):
     """ENCODER mode of ONE image in container "auto": MODE_RANS_AUTO(image_streams(H, W)) -- xwide v4 streams, their count picked by the encoder from
     the image itself: what its size gives, a third more where the last stage's symbols are expensive (an xwide stream costs ~2.5 bytes there instead
     of ~4.5), half where the last stage is too cheap to fill the streams' payloads; an image too small for one xwide stream gets a 64-lane stream
     (from ~45x45 pixels) or -- only where the call holds images of one size (`mixed` False) -- the reference format."""
-    m = image_streams(H, W)
+    m = image_streams(H, W, nlevels)
+    if nlevels != 5:            # config B: xwide streams or the reference format only
+        return MODE_RANS_AUTO(m) if m >= 1 else (MODE_RANS(1, wide=2) if mixed else MODE_AC)
     if m > 32:
         return MODE_RANS(m, wide=2)             # (64 / 128 streams: very large images; the count is the size rule's)
     if m >= 1:
@@ -80,19 +91,19 @@ def auto_container(H, W):
     return name_of_mode(image_mode(H, W))
 
 
-def auto_modes(sizes):
+def auto_modes(sizes, nlevels=5):
     """Container modes of the images of ONE call ([(H, W), ...]) in container "auto": each image's own (image_mode) -- xwide streams, their number per image
     a function of its size -- unless one of them is too small for an xwide stream: the images of a call share a lane kind, so then every image of the
     call gets one 64-lane stream (the reference format, where all are that small and of one size).  What an image of a call of EQUAL sizes gets depends
     on its size alone; in a call of mixed sizes a tiny neighbour (below ~90x90 pixels) can push an image to the 64-lane kind -- the reference's test set
     has no such image (tests/golden/eval_shapes.json: 321x481 is its smallest)."""
     mixed = len(set(sizes)) > 1
-    modes = [image_mode(h, w, mixed) for h, w in sizes]
+    modes = [image_mode(h, w, mixed, nlevels) for h, w in sizes]
     if all(_mode_wide(m) == 2 for m in modes if m != MODE_AC) and MODE_AC not in modes:
         return modes
     if all(m == MODE_AC for m in modes):
         return modes
-    return [MODE_RANS(1)] * len(sizes)
+    return [MODE_RANS(1, wide=2 if nlevels != 5 else 0)] * len(sizes)
 
 
 def MODE_RANS(M=8, wide=False):
@@ -156,6 +167,14 @@ def mode_of_header(hdr, pad=None) -> int:
     u = 0 if pad is None else (int(pad) >> 10) & 0x3F
     if byte0 == 5:
         return MODE_AC
+    if byte0 == 2:              # config B's reference format (2 scales): its pad field has 4 bits
+        if pad is not None and int(pad) >> 4:
+            raise ValueError(f"pad field 0x{int(pad):04x} of a 2-level container has bits above its 4 pad flags")
+        return MODE_AC
+    if byte0 == 0xE9:           # config B's xwide v4 streams (llicti_amd/csrc/host_plan.hpp: rans_byte0): the count as in 0xE8, pad bits 4 .. 9 zero
+        if pad is None or not (1 <= u <= 34) or (int(pad) & 0x3F0):
+            raise ValueError(f"container tag 0xe9 (config B, xwide v4) needs its stream count in the pad field and pad bits 4 .. 9 clear")
+        return MODE_RANS(u if u <= 32 else {33: 64, 34: 128}[u], wide=2)
     if (byte0 & 0x88) == 0x88:          # rANS: bits 5,4,2,1,0 = v; bit 6 clear: M = v + 1; set: v = 0, 1 -> 64, 128 streams, 2 .. 15 -> v - 1 wide streams,
         v = (((byte0 >> 4) & 3) << 3) | (byte0 & 7)       # 16 -> xwide streams in the v4 layout, their count in the pad field's high bits
         if (byte0 >> 6) & 1:
@@ -231,6 +250,17 @@ class HipCodec:
         self._ws_grown = False
         self._mc = {}
         self.have_weights = False
+        self.head, self.nlevels = 88, 5             # config A until set_model()
+
+    def set_model(self, head, nlevels):
+        """Model shape of the context (llicti_set_model): (88, 5) = config A, (60, 2) = config B.  A change drops the weights."""
+        if (int(head), int(nlevels)) == (self.head, self.nlevels):
+            return
+        _lib.check(self.L.llicti_set_model(self.ctx, int(head), int(nlevels)))
+        self.head, self.nlevels = int(head), int(nlevels)
+        self.have_weights = False
+        self._ws_need.clear()
+        self._mc.clear()
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -247,6 +277,9 @@ class HipCodec:
     def load_state_dict(self, sd):
         """Reference-keyed state_dict (or the canonical packed dict) -> device."""
         packed = sd if (isinstance(sd, dict) and 0 in sd) else pack_state_dict(sd)
+        head = int(packed[0].get("head", 88))
+        if head != self.head:
+            raise ValueError(f"weights with {head}-wide heads for a context of {self.head}-wide ones: set_model({head}, {MODELS.get(head)}) first")
         for b in range(3):
             d = packed[b]
             _lib.check(self.L.llicti_set_band_weights(self.ctx, b, int(d["K0"]), _ptr(d["w0"]), _ptr(d["b0"]),
@@ -292,10 +325,10 @@ class HipCodec:
         return out
 
     def forward_selfinfo(self, rgb):
-        """LLICTI.forward: list of 5 tensors [B, 9, h, w] (scale 0 first; channel 3*band + colour)."""
+        """LLICTI.forward: list of L tensors [B, 9, h, w] (L = 5 / 2 levels for config A / B; scale 0 first; channel 3*band + colour)."""
         fplanes = self.lift_train(rgb)
         res = []
-        for lvl in range(5):
+        for lvl in range(self.nlevels):
             bands = [self.selfinfo(fplanes, self.band_params(fplanes, lvl, b), lvl, b) for b in range(3)]
             res.append(torch.cat(bands, dim=1))
         return res
@@ -366,7 +399,8 @@ class HipCodec:
         if n is None:
             if len(self._ws_need) > 256:
                 self._ws_need.clear()
-            n = self._ws_need[key] = int(self.L.llicti_workspace_bytes(B, H, W, mode))
+            Hs, Ws, m = (C.c_int * B)(*([H] * B)), (C.c_int * B)(*([W] * B)), (C.c_int * 1)(mode)
+            n = self._ws_need[key] = int(self.L.llicti_workspace_bytes_ctx(self.ctx, B, Hs, Ws, m, 1))      # (the context's model)
         return self._workspace_of(n)
 
     @staticmethod
@@ -386,15 +420,15 @@ class HipCodec:
         if n is None:
             if len(self._ws_need) > 256:
                 self._ws_need.clear()
-            n = int(self.L.llicti_workspace_bytes_v(len(Hs), _ptr(Hs), _ptr(Ws), one)) if per is None else \
-                int(self.L.llicti_workspace_bytes_vm(len(Hs), _ptr(Hs), _ptr(Ws), _ptr(per)))
+            n = int(self.L.llicti_workspace_bytes_ctx(self.ctx, len(Hs), _ptr(Hs), _ptr(Ws), (C.c_int * 1)(one), 1)) if per is None else \
+                int(self.L.llicti_workspace_bytes_ctx(self.ctx, len(Hs), _ptr(Hs), _ptr(Ws), _ptr(per), len(Hs)))
             self._ws_need[key] = n
         return self._workspace_of(n)
 
     def max_container_bytes(self, H, W):
         n = self._mc.get((H, W))
         if n is None:
-            n = int(self.L.llicti_max_container_bytes(H, W))
+            n = int(self.L.llicti_max_container_bytes_ctx(self.ctx, H, W))
             if n == 0:
                 _lib.check(_lib.EINVAL)
             if len(self._mc) > 1024:
@@ -549,27 +583,35 @@ class HipCodec:
 
 
 # ---------------------------------------------------------------------- container <-> bytestream_list
-def container_to_bytestream_list(buf: np.ndarray, seg_len: np.ndarray):
-    """Flat container of one image -> the reference's list of 6 lists x 9 `bytes`
-    (LLICTI_nets.py:352-354, :411; loggers/rate.py:133 needs 9 entries per row)."""
+def levels_of_header(byte0) -> int:
+    """Wavelet levels of the model that wrote a container, from its header byte 0: 2 (config B: 2 scales, or its xwide tag 0xE9), else 5."""
+    return 2 if int(byte0) in (2, 0xE9) else 5
+
+
+def container_to_bytestream_list(buf: np.ndarray, seg_len: np.ndarray, nlevels=None):
+    """Flat container of one image -> the reference's list of 1 + L lists x 9 `bytes` (L = 5 / 2 levels for config A / B, by default read
+    from the header) (LLICTI_nets.py:352-354, :411; loggers/rate.py:133 needs 9 entries per row)."""
+    L = levels_of_header(buf[0]) if nlevels is None else int(nlevels)
     segs, pos = [], 0
-    for n in seg_len:
+    for n in seg_len[:4 + 9 * L]:
         segs.append(bytes(buf[pos:pos + int(n)]))
         pos += int(n)
     em = b""
     bl = [[segs[0], segs[1], segs[2], segs[3], em, em, em, em, em]]
-    for s in range(5):
+    for s in range(L):
         bl.append(segs[4 + 9 * s: 4 + 9 * (s + 1)])
     return bl
 
 
 def bytestream_list_to_container(bl):
-    if len(bl) != 6 or any(len(r) != 9 for r in bl):
-        raise ValueError("bytestream_list must be 6 lists of 9 byte strings")
+    """-> (flat container, seg_len int32 [NSEG]): a config-B list (3 rows) leaves the lengths past its 22 segments 0."""
+    if len(bl) not in (6, 3) or any(len(r) != 9 for r in bl):
+        raise ValueError("bytestream_list must be 6 (config A) or 3 (config B) lists of 9 byte strings")
     segs = list(bl[0][:4])
-    for s in range(1, 6):
+    for s in range(1, len(bl)):
         segs += list(bl[s])
-    seg_len = np.array([len(s) for s in segs], dtype=np.int32)
+    seg_len = np.zeros(NSEG, dtype=np.int32)
+    seg_len[:len(segs)] = [len(s) for s in segs]
     return np.frombuffer(b"".join(segs), dtype=np.uint8).copy(), seg_len
 
 

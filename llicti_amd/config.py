@@ -40,13 +40,34 @@ def load_json(path):
         return Config(json.load(f))
 
 
+# configs/llicti_B.json: the reference's second configuration -- the one its README trains with -- differs from A in the model's shape only
+CONFIG_B = dict(CONFIG_A, chs=[60, 1, 1, 1, 1], dwtlevels=[0, 1], useprevlevNN=[False, True])
+_SHAPE = ("dwtlevels", "useprevlevNN")
+
+
+def model_shape(config):
+    """(head width, levels) of a supported config: (88, 5) for config A, (60, 2) for config B (check_supported first)."""
+    return int(config["chs"][0]), len(config["dwtlevels"])
+
+
 def check_supported(config):
-    """The HIP kernels implement exactly the released configuration (config A).  Anything else the
-    reference's constructor would accept is rejected loudly instead of being silently mis-coded."""
+    """The HIP kernels implement exactly the reference's two configurations: A (configs/llicti_A.json: 88-wide heads, 5 levels) and B
+    (configs/llicti_B.json: 60-wide heads, 2 levels).  Anything else the reference's constructor would accept is rejected loudly instead of
+    being silently mis-coded."""
     for k in _CHECKED:
+        if k in _SHAPE:
+            continue
         have = config[k] if k in config else None
         if have != CONFIG_A[k]:
-            raise NotImplementedError(f"config.{k}={have!r}: the MI355X hot path implements configs/llicti_A.json "
+            raise NotImplementedError(f"config.{k}={have!r}: the MI355X hot path implements configs/llicti_A.json and llicti_B.json "
                                       f"only ({k}={CONFIG_A[k]!r})")
-    if int(config["chs"][0]) != 88:
-        raise NotImplementedError("config.chs[0] must be 88")
+    shape = (int(config["chs"][0]) if "chs" in config else None,
+             list(config["dwtlevels"]) if "dwtlevels" in config else None,
+             list(config["useprevlevNN"]) if "useprevlevNN" in config else None)
+    for ref in (CONFIG_A, CONFIG_B):
+        if shape == (ref["chs"][0], ref["dwtlevels"], ref["useprevlevNN"]):
+            return
+    if shape[0] != 88 and shape[0] != 60:
+        raise NotImplementedError(f"config.chs[0]={shape[0]!r}: the hot path runs 88-wide heads (config A) or 60-wide heads (config B)")
+    raise NotImplementedError(f"config (chs[0], dwtlevels, useprevlevNN) = {shape!r}: the MI355X hot path implements exactly config A "
+                              f"(88, [0, 1, 2, 3, 4], [F, T, T, T, T]) and config B (60, [0, 1], [F, T])")

@@ -69,19 +69,23 @@ constexpr int prio_step(int before, int after, int total)
 // call with equal sizes runs.  RAGGED = true (llicti_encode_images_v / _decode_images_v with mixed sizes): the launch walks a TILE LIST --
 // tiles[t] = (image, tile row << 16 | tile column), image-major -- and takes each image's geometry and placement from gv[image]; the same
 // fmaf chain per position, so the outputs of an image do not depend on what else is in the batch.
-template <int BAND, int TH = kTileHMax, bool RAGGED = false>
-__global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const float *__restrict__ fplanes, Geom g,
-                                                                  const float *__restrict__ wpack,
-                                                                  float *__restrict__ params, int tiles_x, int tiles_y, int n_tiles,
-                                                                  const Geom *__restrict__ gv, const TileRef *__restrict__ tiles)
+// HW: channels per head -- 88 (config A; band_params_kernel) or 60 (config B; band_params_h60_kernel).  The two kernels are thin wrappers of this
+// body: what differs is the number of 16-row tiles (6 / 4), of k-steps of layers 1 and 2 (22 / 15), and A's 4x4x1 remainder of layer 0.
+template <int BAND, int TH, bool RAGGED, int HW>
+__device__ __forceinline__ void band_params_body(const float *__restrict__ fplanes, Geom g, const float *__restrict__ wpack,
+                                                 float *__restrict__ params, int tiles_x, int tiles_y, int n_tiles,
+                                                 const Geom *__restrict__ gv, const TileRef *__restrict__ tiles)
 {
+    using HD = HeadDef<HW>;
+    constexpr int kMT = HD::mt, kKS1 = HD::ks1, kMT0 = HD::mt0;     // (shadow config A's constants of cnn_pack.hpp)
+    constexpr bool kRem = HD::rem;
     using GEO = CnnGeo<TH>;
     constexpr int kCnnThreads = GEO::kThreads, kTileH = TH, kInRows = GEO::kInRows, kInPlane = GEO::kInPlane, kPP = GEO::kPP;
     constexpr int K0 = (BAND == 0) ? 48 : (BAND == 1) ? 72 : 120;
     constexpr int NK0 = K0 / 4;
     constexpr int NPL = 3 * (BAND + 1);          // staged input planes: (x00 | x11 | x01) x (Y, Co, Cg)
     constexpr int kMfmaL0 = kMT * NK0 * kNT, kMfmaT12 = (kKS1 + 4) * kNT, kMfmaTile = kMfmaL0 + kMT * kMfmaT12;   // MFMAs of a wave per tile (approx.)
-    using PO = PackOff<K0>;
+    using PO = PackOff<K0, HW>;
     static_assert(kKTab<BAND, TH>.n == NK0, "k-step table");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *lds_in = lds + PO::total;
@@ -265,10 +269,10 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
 #pragma unroll
             for (int n = 0; n < kNT; ++n) a0[T][n] = bv;
         }
-#if CNN_REM4X4
+        if constexpr (kRem) {
 #pragma unroll
-        for (int n = 0; n < kNT; ++n) a0[5][n] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };     // [0], [1] are written after layer 0; [2], [3] never read
-#endif
+            for (int n = 0; n < kNT; ++n) a0[5][n] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };     // [0], [1] are written after layer 0; [2], [3] never read
+        }
 #if CNN_PREFETCH_L0
         {
             float a_c[kMT0], b_c[kNT];
@@ -279,7 +283,8 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
             const int rsub = lane & 3, rcg = lane >> 5, rpix = 4 * ((lane >> 2) & 7) + rsub;
             const float *rb_base = lds_cur + ((wave * kNT) >> 1) * kInPitch + rpix;
             const float *ra_base = lds + PO::w0r + (4 * rcg + rsub) * 4;
-            f32x4 dR = *reinterpret_cast<const f32x4 *>(lds + PO::bias0r + 4 * rcg);
+            f32x4 dR = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+            if constexpr (kRem) dR = *reinterpret_cast<const f32x4 *>(lds + PO::bias0r + 4 * rcg);
             f32x4 ar_c;
             float br_c[4];
 #endif
@@ -291,9 +296,11 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
 #pragma unroll
                 for (int T = 0; T < kMT0; ++T) a_c[T] = lds[PO::w0 + (T * NK0 + 0) * 64 + lane];
 #if CNN_REM4X4
-                ar_c = *reinterpret_cast<const f32x4 *>(ra_base);
+                if constexpr (kRem) {
+                    ar_c = *reinterpret_cast<const f32x4 *>(ra_base);
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) br_c[kk] = rb_base[U + (S == 1 ? kk : kk * kInPitch)];
+                    for (int kk = 0; kk < 4; ++kk) br_c[kk] = rb_base[U + (S == 1 ? kk : kk * kInPitch)];
+                }
 #endif
             }
             static_for<NK0>([&](auto tc) {
@@ -313,12 +320,15 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
 #pragma unroll
                     for (int T = 0; T < kMT0; ++T) a_n[T] = CNN_EXP_NO_WFRAG ? a_c[T] : lds[PO::w0 + (T * NK0 + t + 1) * 64 + lane];
 #if CNN_REM4X4
-                    ar_n = CNN_EXP_NO_WFRAG ? ar_c : *reinterpret_cast<const f32x4 *>(ra_base + (t + 1) * 32);
+                    if constexpr (kRem) {
+                        ar_n = CNN_EXP_NO_WFRAG ? ar_c : *reinterpret_cast<const f32x4 *>(ra_base + (t + 1) * 32);
 #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) br_n[kk] = rb_base[U + (S == 1 ? kk : kk * kInPitch)];
+                        for (int kk = 0; kk < 4; ++kk) br_n[kk] = rb_base[U + (S == 1 ? kk : kk * kInPitch)];
+                    }
 #endif
                 }
 #if CNN_REM4X4
+                if constexpr (kRem) {
                 // the four 4x4x1 steps of this k-step form ONE dependent chain (k order is the spec): they are spread between
                 // the ten independent 16x16x4 MFMAs so that none waits for its predecessor
                 // (scheduler fences pin the order: left alone, the machine scheduler clusters the 4x4x1s)
@@ -335,12 +345,14 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
                 __builtin_amdgcn_sched_barrier(0);
                 a0[4][0] = MFMA4(a_c[4], b_c[0], a0[4][0]); a0[4][1] = MFMA4(a_c[4], b_c[1], a0[4][1]);
                 dR = MFMA1(ar_c[3], br_c[3], dR);
-#else
+                } else
+#endif
+                {
 #pragma unroll
                 for (int T = 0; T < kMT0; ++T)
 #pragma unroll
                     for (int n = 0; n < kNT; ++n) a0[T][n] = MFMA4(a_c[T], b_c[n], a0[T][n]);
-#endif
+                }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (t + 1 < NK0) {
 #pragma unroll
@@ -348,9 +360,11 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
 #pragma unroll
                     for (int n = 0; n < kNT; ++n) b_c[n] = b_n[n];
 #if CNN_REM4X4
-                    ar_c = ar_n;
+                    if constexpr (kRem) {
+                        ar_c = ar_n;
 #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) br_c[kk] = br_n[kk];
+                        for (int kk = 0; kk < 4; ++kk) br_c[kk] = br_n[kk];
+                    }
 #endif
                 }
             });
@@ -358,6 +372,7 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
             // hand the 8 channels to layer 1 in ITS operand layout: k-step 20 + r of layer 1 wants channel 80 + 4 r + q of pixel
             // 16 n + px in lane (q, px) = register q of lane 32 r + 16 n + px here.  a0[5][n][0..1] are exactly those operands
             // (a0[5][n][2..3] would be k-steps 22, 23: not used, 88 = 22 x 4).
+            if constexpr (kRem) {
             dR = relu4(dR);
 #pragma unroll
             for (int n = 0; n < kNT; ++n)
@@ -370,6 +385,7 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
                     const float t3 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(dR[3])));
                     a0[5][n][r] = (q == 0) ? t0 : (q == 1) ? t1 : (q == 2) ? t2 : t3;
                 }
+            }
 #endif
         }
 #else
@@ -417,8 +433,9 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
             constexpr int T = decltype(Tc)::value;
             if constexpr (CNN_PRIO && prio_step(kMfmaL0 + T * kMfmaT12, kMfmaL0 + (T + 1) * kMfmaT12, kMfmaTile) >= 0)
                 __builtin_amdgcn_s_setprio(prio_step(kMfmaL0 + T * kMfmaT12, kMfmaL0 + (T + 1) * kMfmaT12, kMfmaTile));
-            if constexpr (T == 2 && CNN_STAGE_SITES > 2) stage_next(2);
-            if constexpr (T == 4 && CNN_STAGE_SITES > 2) stage_next(3);
+            // (sites 2 and 3 at a third and two thirds of the tiles: T = 2, 4 of config A's six, T = 1, 2 of config B's four -- every site must come)
+            if constexpr (T == kMT / 3 && CNN_STAGE_SITES > 2) stage_next(2);
+            if constexpr (T == 2 * kMT / 3 && CNN_STAGE_SITES > 2) stage_next(3);
             f32x4 a1[kNT];
             {
                 const f32x4 bv = *reinterpret_cast<const f32x4 *>(lds + PO::bias1 + (T * 4 + q) * 4);
@@ -496,5 +513,23 @@ __global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const
         }
         cur ^= 1;
     }
+}
+
+template <int BAND, int TH = kTileHMax, bool RAGGED = false>
+__global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_kernel(const float *__restrict__ fplanes, Geom g,
+                                                                  const float *__restrict__ wpack,
+                                                                  float *__restrict__ params, int tiles_x, int tiles_y, int n_tiles,
+                                                                  const Geom *__restrict__ gv, const TileRef *__restrict__ tiles)
+{
+    band_params_body<BAND, TH, RAGGED, kHead>(fplanes, g, wpack, params, tiles_x, tiles_y, n_tiles, gv, tiles);
+}
+// config B (60-wide heads): its own kernel name, so that the per-kernel statistics of config A's CNN stay what they are
+template <int BAND, int TH = kTileHMax, bool RAGGED = false>
+__global__ __launch_bounds__(CnnGeo<TH>::kThreads) void band_params_h60_kernel(const float *__restrict__ fplanes, Geom g,
+                                                                      const float *__restrict__ wpack,
+                                                                      float *__restrict__ params, int tiles_x, int tiles_y, int n_tiles,
+                                                                      const Geom *__restrict__ gv, const TileRef *__restrict__ tiles)
+{
+    band_params_body<BAND, TH, RAGGED, kHeadB>(fplanes, g, wpack, params, tiles_x, tiles_y, n_tiles, gv, tiles);
 }
 

@@ -17,6 +17,7 @@ constexpr ConvDef kConvs[3][3] = {
 constexpr int kHead = 88;          // channels per head (configs/llicti_A.json chs[0])
 constexpr int kMT = 6;             // 16-row MFMA tiles per head (88 -> 96, rows >= 88 are zero)
 constexpr int kKS1 = 22;           // k-steps of the 88-deep layers (88 / 4)
+constexpr int kHeadB = 60;         // channels per head of configs/llicti_B.json (chs[0]): 4 tiles (60 -> 64, rows >= 60 are zero), 15 k-steps
 #ifndef CNN_NT
 #define CNN_NT 2
 #endif
@@ -65,6 +66,21 @@ constexpr int kParamStride = LLICTI_PARAM_STRIDE;
 static_assert(!CNN_REM4X4 || (CNN_PREFETCH_L0 && CNN_NT == 2), "the 4x4x1 remainder path is written for the prefetching, NT = 2 form");
 constexpr int kMT0 = CNN_REM4X4 ? 5 : 6;        // 16-row tiles of LAYER 0
 
+// The shape of one head of width HW (88: config A, 60: config B).  Config A's values are the constants above; only A has the 4x4x1
+// remainder path (its channels 80..87), a 60-wide head is four whole 16-row tiles in every layer.
+template <int HW> struct HeadDef {
+    static_assert(HW == kHead || HW == kHeadB, "head width: 88 (config A) or 60 (config B)");
+    static constexpr int head = HW;
+    static constexpr int mt = (HW + 15) / 16;                    // 16-row MFMA tiles of layers 0 and 1: 6 / 4
+    static constexpr int ks1 = HW / 4;                           // k-steps of layers 1 and 2: 22 / 15
+    static constexpr bool rem = HW == kHead && CNN_REM4X4;
+    static constexpr int mt0 = rem ? kMT0 : mt;                  // 16-row tiles of LAYER 0
+};
+static_assert(HeadDef<kHead>::mt == kMT && HeadDef<kHead>::ks1 == kKS1 && HeadDef<kHead>::mt0 == kMT0, "config A's head shape");
+static constexpr int head_mt(int hw) { return (hw + 15) / 16; }
+static constexpr bool head_rem(int hw) { return hw == kHead && CNN_REM4X4; }
+static constexpr int head_mt0(int hw) { return head_rem(hw) ? kMT0 : head_mt(hw); }
+
 
 // Per (band, head) weight pack, in MFMA-fragment order so that the LDS image is lane-linear:
 //   bias0 [6][4][4]            acc init of tile T, lane group q, reg r  = b0[16T + 4r + q]
@@ -78,68 +94,81 @@ constexpr int kMT0 = CNN_REM4X4 ? 5 : 6;        // 16-row tiles of LAYER 0
 // chan(T, rho) = 16T + 4(rho&3) + (rho>>2): this row permutation makes the accumulator registers of one
 // layer line up, untouched, as the B operand of the next layer's MFMAs in natural channel order
 // (C/D layout of v_mfma_f32_16x16x4_f32: col = lane&15, row = 4(lane>>4) + reg).
-static constexpr int rem_floats(int K0) { return CNN_REM4X4 ? K0 * 8 + 8 : 0; }
-static constexpr int pack_floats(int K0) { return 96 + kMT0 * (K0 / 4) * 64 + rem_floats(K0) + 96 + kMT * kKS1 * 64 + 16 + kKS1 * 64; }
+// A 60-wide head (config B) has the same pack with 4 tiles and 15 k-steps and no remainder part (bias0 / bias1 [4][4][4]).
+static constexpr int rem_floats(int K0, int hw = kHead) { return head_rem(hw) ? K0 * 8 + 8 : 0; }
+static constexpr int pack_floats(int K0, int hw = kHead)
+{
+    return 16 * head_mt(hw) + head_mt0(hw) * (K0 / 4) * 64 + rem_floats(K0, hw) + 16 * head_mt(hw) + head_mt(hw) * (hw / 4) * 64 + 16 + (hw / 4) * 64;
+}
 
-template <int K0>
+template <int K0, int HW = kHead>
 struct PackOff {
+    using HD = HeadDef<HW>;
     static constexpr int bias0 = 0;
-    static constexpr int w0 = 96;
-    static constexpr int w0r = w0 + kMT0 * (K0 / 4) * 64;        // [K0/4][8][4]
-    static constexpr int bias0r = w0r + (CNN_REM4X4 ? K0 * 8 : 0);
-    static constexpr int bias1 = w0 + kMT0 * (K0 / 4) * 64 + rem_floats(K0);
-    static constexpr int w1 = bias1 + 96;
-    static constexpr int bias2 = w1 + kMT * kKS1 * 64;
+    static constexpr int w0 = 16 * HD::mt;
+    static constexpr int w0r = w0 + HD::mt0 * (K0 / 4) * 64;        // [K0/4][8][4]
+    static constexpr int bias0r = w0r + (HD::rem ? K0 * 8 : 0);
+    static constexpr int bias1 = w0 + HD::mt0 * (K0 / 4) * 64 + rem_floats(K0, HW);
+    static constexpr int w1 = bias1 + 16 * HD::mt;
+    static constexpr int bias2 = w1 + HD::mt * HD::ks1 * 64;
     static constexpr int w2 = bias2 + 16;
-    static constexpr int total = w2 + kKS1 * 64;
+    static constexpr int total = w2 + HD::ks1 * 64;
+    static_assert(total == pack_floats(K0, HW), "pack size");
 };
-static constexpr int cnn_lds_bytes(int band, int TH = kTileHMax)
+// config B at 16 rows: 49 KB of weights (band 2) + the same input tiles as A -- 117 KB, one workgroup per compute unit like A's 148 KB
+static constexpr int cnn_lds_bytes(int band, int TH = kTileHMax, int hw = kHead)
 {
     const int K0 = band == 0 ? 48 : band == 1 ? 72 : 120;
-    return (pack_floats(K0) + 2 * 3 * (band + 1) * (TH + 4) * kInPitch) * 4;     // weights + double-buffered input tile
+    return (pack_floats(K0, hw) + 2 * 3 * (band + 1) * (TH + 4) * kInPitch) * 4;     // weights + double-buffered input tile
 }
 
 
-// host: canonical arrays -> fragment-ordered pack of one band (4 heads)
-static void pack_band(int K0, const float *w0, const float *b0, const float *w1, const float *b1,
+// host: canonical arrays -> fragment-ordered pack of one band (4 heads of width hw: w0 [4 hw][K0], w1 [4 hw][hw], w2 [60][hw])
+static void pack_band(int K0, int hw, const float *w0, const float *b0, const float *w1, const float *b1,
                       const float *w2, const float *b2, std::vector<float> &out)
 {
-    const int NK0 = K0 / 4;
-    const int total = pack_floats(K0);
+    const int NK0 = K0 / 4, MT = head_mt(hw), MT0 = head_mt0(hw), KS1 = hw / 4;
+    const bool rem = head_rem(hw);
+    const int total = pack_floats(K0, hw);
     out.assign((size_t)4 * total, 0.0f);
     for (int hd = 0; hd < 4; ++hd) {
         float *p = out.data() + (size_t)hd * total;
-        float *bias0 = p, *W0 = p + 96, *W0r = W0 + kMT0 * NK0 * 64, *bias0r = W0r + (CNN_REM4X4 ? K0 * 8 : 0);
-        float *bias1 = W0 + kMT0 * NK0 * 64 + rem_floats(K0), *W1 = bias1 + 96;
-        float *bias2 = W1 + kMT * kKS1 * 64, *W2 = bias2 + 16;
-        for (int T = 0; T < kMT; ++T)
+        float *bias0 = p, *W0 = p + 16 * MT, *W0r = W0 + MT0 * NK0 * 64, *bias0r = W0r + (rem ? K0 * 8 : 0);
+        float *bias1 = W0 + MT0 * NK0 * 64 + rem_floats(K0, hw), *W1 = bias1 + 16 * MT;
+        float *bias2 = W1 + MT * KS1 * 64, *W2 = bias2 + 16;
+        for (int T = 0; T < MT; ++T)
             for (int q = 0; q < 4; ++q)
                 for (int r = 0; r < 4; ++r) {
                     const int cl = 16 * T + 4 * r + q;
-                    bias0[(T * 4 + q) * 4 + r] = (cl < kHead) ? b0[hd * kHead + cl] : 0.0f;
-                    bias1[(T * 4 + q) * 4 + r] = (cl < kHead) ? b1[hd * kHead + cl] : 0.0f;
+                    bias0[(T * 4 + q) * 4 + r] = (cl < hw) ? b0[hd * hw + cl] : 0.0f;
+                    bias1[(T * 4 + q) * 4 + r] = (cl < hw) ? b1[hd * hw + cl] : 0.0f;
                 }
-        for (int T = 0; T < kMT; ++T)
+        for (int T = 0; T < MT; ++T)
             for (int l = 0; l < 64; ++l) {
                 const int rho = l & 15, q = l >> 4;
                 const int cl = 16 * T + 4 * (rho & 3) + (rho >> 2);
-                if (T < kMT0)
+                if (T < MT0)
                     for (int t = 0; t < NK0; ++t)
-                        W0[(T * NK0 + t) * 64 + l] = (cl < kHead) ? w0[(size_t)(hd * kHead + cl) * K0 + 4 * t + q] : 0.0f;
-                for (int t = 0; t < kKS1; ++t)
-                    W1[(T * kKS1 + t) * 64 + l] = (cl < kHead) ? w1[(size_t)(hd * kHead + cl) * kHead + 4 * t + q] : 0.0f;
+                        W0[(T * NK0 + t) * 64 + l] = (cl < hw) ? w0[(size_t)(hd * hw + cl) * K0 + 4 * t + q] : 0.0f;
+                for (int t = 0; t < KS1; ++t)
+                    W1[(T * KS1 + t) * 64 + l] = (cl < hw) ? w1[(size_t)(hd * hw + cl) * hw + 4 * t + q] : 0.0f;
             }
-        if (CNN_REM4X4) {
+        if (rem) {
             for (int t = 0; t < NK0; ++t)
                 for (int c = 0; c < 8; ++c)
-                    for (int kk = 0; kk < 4; ++kk) W0r[(t * 8 + c) * 4 + kk] = w0[(size_t)(hd * kHead + 80 + c) * K0 + 4 * t + kk];
-            for (int c = 0; c < 8; ++c) bias0r[c] = b0[hd * kHead + 80 + c];
+                    for (int kk = 0; kk < 4; ++kk) W0r[(t * 8 + c) * 4 + kk] = w0[(size_t)(hd * hw + 80 + c) * K0 + 4 * t + kk];
+            for (int c = 0; c < 8; ++c) bias0r[c] = b0[hd * hw + 80 + c];
         }
         for (int q = 0; q < 4; ++q)
             for (int r = 0; r < 4; ++r) bias2[q * 4 + r] = (4 * q + r < 15) ? b2[hd * 15 + 4 * q + r] : 0.0f;
         for (int l = 0; l < 64; ++l) {
             const int o = l & 15, q = l >> 4;
-            for (int t = 0; t < kKS1; ++t) W2[t * 64 + l] = (o < 15) ? w2[(size_t)(hd * 15 + o) * kHead + 4 * t + q] : 0.0f;
+            for (int t = 0; t < KS1; ++t) W2[t * 64 + l] = (o < 15) ? w2[(size_t)(hd * 15 + o) * hw + 4 * t + q] : 0.0f;
         }
     }
+}
+static void pack_band(int K0, const float *w0, const float *b0, const float *w1, const float *b1,
+                      const float *w2, const float *b2, std::vector<float> &out)
+{
+    pack_band(K0, kHead, w0, b0, w1, b1, w2, b2, out);
 }

@@ -22,32 +22,35 @@ __global__ void header_write_kernel(const uint8_t *__restrict__ rgb, const int32
         o[15] = (uint8_t)(padint & 0xFF); o[16] = (uint8_t)((padint >> 8) & 0xFF);                         // :349
         int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
         sl[0] = 3; sl[1] = 12; sl[2] = 2; sl[3] = 3 * h4 * w4;
+        for (int k = ig.nseg; k < LLICTI_NSEG; ++k) sl[k] = 0;                  // (a model of fewer levels: the segments it does not have)
     }
+    const int dcs = ig.dcs;                                                      // the last level's x00 (32 for 5 levels)
     for (int t = threadIdx.x; t < 3 * h4 * w4; t += blockDim.x) {                                        // :248-252, :350
         const int c = t / (h4 * w4), r = t - c * h4 * w4, i = r / w4, j = r - i * w4;
-        o[17 + t] = rgb[ig.rgb_off + c * plane + (long)(32 * i) * W + 32 * j];
+        o[17 + t] = rgb[ig.rgb_off + c * plane + (long)(dcs * i) * W + dcs * j];
     }
 }
 
-// encode: copy the 45 slots of image b behind its header, tightly; seg_len[b][4..48]
+// encode: copy the 45 slots of image b behind its header, tightly; seg_len[b][4..48].  st0: the model's first stage (host_plan.hpp: first_stage;
+// 0 for 5 levels) -- stage st0 + x is segment 4 + x.
 __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ slots, const long *__restrict__ slot_off,
                                                    const int32_t *__restrict__ slot_len, int B, int hdr_bytes,
                                                    uint8_t *__restrict__ out, long out_stride, int32_t *__restrict__ seg_len,
-                                                   int32_t *status)
+                                                   int32_t *status, int st0)
 {
-    const int st = blockIdx.x, b = blockIdx.y;
+    const int st = st0 + blockIdx.x, b = blockIdx.y;
     // slot index: streams are stored stage-major, image-minor (see build_plan)
     long dst = hdr_bytes;
-    for (int k = 0; k < st; ++k) dst += slot_len[(long)k * B + b];
+    for (int k = st0; k < st; ++k) dst += slot_len[(long)k * B + b];
     const int n = slot_len[(long)st * B + b];
     if (dst + n > out_stride) { if (threadIdx.x == 0) atomicExch(&status[0], LLICTI_ENOSPACE); return; }
     const uint8_t *src = slots + slot_off[(long)st * B + b];
     uint8_t *o = out + (long)b * out_stride + dst;
     block_copy_bytes(o, src, n);
-    if (threadIdx.x == 0) seg_len[(long)b * LLICTI_NSEG + 4 + st] = n;
+    if (threadIdx.x == 0) seg_len[(long)b * LLICTI_NSEG + 4 + st - st0] = n;
 }
 
-// decode: parse + validate header, min/max -> minmax[b][4], DC band -> planes at stride 32
+// decode: parse + validate header, min/max -> minmax[b][4], DC band -> planes at the DC stride (32 for 5 levels)
 __global__ void header_read_kernel(const uint8_t *__restrict__ in, long in_stride, const int32_t *__restrict__ seg_len,
                                    const ImgGeo *__restrict__ iv, int16_t *__restrict__ planes,
                                    float *__restrict__ fplanes, int32_t *__restrict__ minmax, int32_t *status)
@@ -64,7 +67,7 @@ __global__ void header_read_kernel(const uint8_t *__restrict__ in, long in_strid
     __shared__ unsigned long long sh_tot;
     if (threadIdx.x == 0) { sh_bad = 0; sh_tot = 0ull; }
     __syncthreads();
-    if (threadIdx.x < LLICTI_NSEG) {               // the 49 lengths in parallel (one thread walking them was most of this kernel's 70 us)
+    if ((int)threadIdx.x < ig.nseg) {              // the 49 lengths in parallel (one thread walking them was most of this kernel's 70 us; config B: its 22)
         const int v = sl[threadIdx.x];
         if (v < 0 || v > in_stride) atomicOr(&sh_bad, 1);
         atomicAdd(&sh_tot, (unsigned long long)((v < 0) ? 0 : v));
@@ -95,32 +98,33 @@ __global__ void header_read_kernel(const uint8_t *__restrict__ in, long in_strid
     // a rejected header still gets a DC band (mid grey): the 45 stages run for every image of the batch, and what they write
     // must not depend on what an earlier call left in the shared workspace (the image is flagged: llicti_image_status)
     const uint8_t *dc = p + 17;
+    const int dcs = ig.dcs;
     for (int t = threadIdx.x; t < h4 * w4; t += blockDim.x) {                              // :429-430, :443-444
         const int i = t / w4, j = t - i * w4;
         const int R = ok ? dc[t] : 128, G = ok ? dc[h4 * w4 + t] : 128, Bl = ok ? dc[2 * h4 * w4 + t] : 128;
         const int Co = R - Bl, tt = Bl + (Co >> 1), Cg = G - tt, Y = tt + (Cg >> 1) - 127;
-        const long off = ig.pix_off + (long)(32 * i) * W + 32 * j;
+        const long off = ig.pix_off + (long)(dcs * i) * W + dcs * j;
         planes[off] = (int16_t)Y; planes[off + plane] = (int16_t)Co; planes[off + 2 * plane] = (int16_t)Cg;
         fplanes[off] = (float)Y / 255.0f; fplanes[off + plane] = (float)Co / 255.0f; fplanes[off + 2 * plane] = (float)Cg / 255.0f;
     }
 }
 
-// decode: copy stream st of image b into its 4-byte aligned, zero padded slot
+// decode: copy stream st of image b into its 4-byte aligned, zero padded slot (segment 4 + st - st0, see pack_kernel)
 __global__ __launch_bounds__(256) void unpack_kernel(const uint8_t *__restrict__ in, long in_stride, const int32_t *__restrict__ seg_len,
                                                      int B, uint8_t *__restrict__ slots, const long *__restrict__ slot_off,
-                                                     const int32_t *__restrict__ slot_cap, int32_t *__restrict__ slot_len, int32_t *status)
+                                                     const int32_t *__restrict__ slot_cap, int32_t *__restrict__ slot_len, int32_t *status, int st0)
 {
-    const int st = blockIdx.x, b = blockIdx.y;
+    const int st = st0 + blockIdx.x, b = blockIdx.y, seg = 4 + blockIdx.x;
     const int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
     long src = 0;
     bool bad = false;
-    for (int k = 0; k < 4 + st; ++k) {          // a negative or oversized EARLIER entry must not move src outside the container
+    for (int k = 0; k < seg; ++k) {          // a negative or oversized EARLIER entry must not move src outside the container
         const int v = sl[k];
         if (v < 0 || v > in_stride) bad = true;
         src += v;
         if (src < 0 || src > in_stride) { bad = true; src = 0; }
     }
-    int n = sl[4 + st];
+    int n = sl[seg];
     const int cap = slot_cap[(long)st * B + b];
     if (bad || n < 0 || n + 16 > cap || src + n > in_stride) { if (threadIdx.x == 0) flag_image(status, b, LLICTI_EFORMAT); n = 0; src = 0; }
     const uint8_t *p = in + (long)b * in_stride + src;

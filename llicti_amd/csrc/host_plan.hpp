@@ -14,6 +14,7 @@
 struct TileRun { size_t off = 0; int n_tiles = 0, TH = 0, gx = 0; };      // band-CNN launch of one (level, band) of a mixed-size plan: its tile list
 struct Plan {
     int B = 0, ME = 0;
+    int nlev = LLICTI_NLEVELS;          // wavelet levels of the model (5: config A, 2: config B; see kLevelsB)
     int M = 0;                          // rANS streams per image (0: AC container only); images of a call may differ: the largest count
     int nstreams = 0;                   // ... and the streams of all images together (sref)
     std::vector<StreamRef> sref;        // [nstreams]: stream -> (image, stream of the image, its count, its first stream)
@@ -66,10 +67,18 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 static int stage_index(int lvl, int band, int clr) { return (LLICTI_NLEVELS - 1 - lvl) * 9 + band * 3 + clr; }   // scale 4..0
 
-static int pad_int(int H, int W)
+// Model shapes: config A codes 5 levels (88-wide heads), config B 2 (60-wide heads).  The stages keep config A's numbering for both: level l < L
+// is stage_index(l, ..) whatever L is, so a 2-level model's plan has its first 27 stages EMPTY (n = 0, never launched) and every kernel that
+// names "the last stage" (level 0, band x10: LLICTI_NSTREAMS - 1) or walks the stage table needs no change.  Its container has 4 + 9 L segments:
+// the AC streams of stages first_stage(L) .. 44 are segments 4 .. 4 + 9 L - 1; rANS streams, at most 9 L per image, are segments 4 .. 4 + M - 1.
+constexpr int kLevelsB = 2;
+static int first_stage(int nlev) { return 9 * (LLICTI_NLEVELS - nlev); }
+static int model_segments(int nlev) { return 4 + 9 * nlev; }
+
+static int pad_int(int H, int W, int nlev = LLICTI_NLEVELS)
 {
     int v = 0;
-    for (int l = 0; l < LLICTI_NLEVELS; ++l) {
+    for (int l = 0; l < nlev; ++l) {
         Geom g = make_geom(1, H, W, l);
         v = 4 * v + 2 * g.padH + g.padW;       // LLICTI_nets.py:230
     }
@@ -131,14 +140,15 @@ static TileForm choose_tile_form(int n_cu, int tile_rows, int band, COUNT &&coun
 // ME: streams per image, | 0x100 for wide (128-lane) streams, | 0x200 for xwide (256-lane) streams -- what mode_streams() returns.
 // Hs, Ws: B sizes; rgb_off: B byte offsets of the images in the caller's RGB buffer, or nullptr = tightly packed in call order.
 // n_cu, tile_rows: the band CNN's tile forms of a mixed-size plan are chosen (and its tile lists written) here.
-static int rans_byte0(int M, int Q);
+static int rans_byte0(int M, int Q, int nlev = LLICTI_NLEVELS);
 static int rans_pad_hi(int M, int Q);
 
 // Ms: B stream counts (rANS containers: the images of a call may have different ones -- every header carries its own -- so that larger images
 // get more streams and a stage launch does not wait for its largest image), each | 0x1000 if that image is "auto" (ME then has 0x1000 if any
 // image is), or nullptr = ME's count and kind for every image.  Fixed and "auto" xwide images may share a call: a fixed one has Mlo = 0.
+// nlev: the model's levels (LLICTI_NLEVELS: config A; kLevelsB: config B).
 static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, int n_cu = 256, int tile_rows = 0, bool force_ragged = false,
-                       const int *Ms = nullptr)
+                       const int *Ms = nullptr, int nlev = LLICTI_NLEVELS)
 {
     const int Q = 1 << ((ME >> 8) & 3);
     const bool per_image = Ms && (ME & 0xFF) > 0;
@@ -147,7 +157,7 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     auto auto_of = [&](int b) -> bool { return ((per_image ? Ms[b] : ME) & 0x1000) != 0; };
     int M = 0;
     for (int b = 0; b < B; ++b) M = std::max(M, auto_of(b) ? rans_auto_hi(m_of(b)) : m_of(b));
-    p.B = B; p.ME = ME; p.M = M; p.Q = Q;
+    p.B = B; p.ME = ME; p.M = M; p.Q = Q; p.nlev = nlev;
     p.uniform = !force_ragged;
     for (int b = 1; b < B; ++b) if (Hs[b] != Hs[0] || Ws[b] != Ws[0]) p.uniform = false;
     {
@@ -167,8 +177,10 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     for (int b = 0; b < B; ++b) {
         ImgGeo &ig = p.img[b];
         ig.H = Hs[b]; ig.W = Ws[b];
-        const Geom g4 = make_geom(1, ig.H, ig.W, 4);
+        const Geom g4 = make_geom(1, ig.H, ig.W, nlev - 1);          // the last level's grid: the header's size bytes and the raw DC band
         ig.h4 = g4.h; ig.w4 = g4.w; ig.hdr_bytes = 17 + 3 * g4.h * g4.w;
+        ig.dcs = 2 << (nlev - 1);
+        ig.nseg = model_segments(nlev);
         ig.plane = (long)ig.H * ig.W;
         ig.pix_off = pix;
         pix += p.uniform ? 3 * ig.plane : (long)align_up((size_t)(3 * ig.plane), 64);
@@ -179,8 +191,8 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
         p.max_plane = std::max(p.max_plane, ig.plane);
         ig.Mlo = auto_of(b) ? m_of(b) : 0;
         ig.M = auto_of(b) ? rans_auto_hi(ig.Mlo) : m_of(b);
-        ig.byte0 = ig.M ? rans_byte0(ig.M, Q) : LLICTI_NLEVELS;
-        ig.padint = pad_int(ig.H, ig.W) | ((ig.M ? rans_pad_hi(ig.M, Q) : 0) << 10);      // the header's int16 pad field (xwide v4: its high bits carry the stream count; an "auto" encode writes the count it picked)
+        ig.byte0 = ig.M ? rans_byte0(ig.M, Q, nlev) : nlev;
+        ig.padint = pad_int(ig.H, ig.W, nlev) | ((ig.M ? rans_pad_hi(ig.M, Q) : 0) << 10);      // the header's int16 pad field (xwide v4: its high bits carry the stream count; an "auto" encode writes the count it picked)
         p.key.push_back(ig.H); p.key.push_back(ig.W); p.key.push_back(ig.rgb_off); p.key.push_back(per_image ? Ms[b] : (ME & 0xFF));
     }
     size_t o = 0;
@@ -213,7 +225,7 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     long pair_pos = 0, slot_pos = 0;
     std::vector<size_t> container(B);
     for (int b = 0; b < B; ++b) container[b] = (size_t)p.img[b].hdr_bytes;
-    for (int lvl = LLICTI_NLEVELS - 1; lvl >= 0; --lvl) {
+    for (int lvl = nlev - 1; lvl >= 0; --lvl) {            // (the stages of levels >= nlev stay empty)
         for (int band = 0; band < 3; ++band) {
             StageGeom *sgr = &p.sg[(size_t)(lvl * 3 + band) * B];
             long cs = 0;
@@ -305,7 +317,7 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     p.tiles.clear();
     for (int k = 0; k < LLICTI_NLEVELS * 3; ++k) p.run[k] = TileRun{};
     if (!p.uniform) {
-        for (int lvl = 0; lvl < LLICTI_NLEVELS; ++lvl) {
+        for (int lvl = 0; lvl < nlev; ++lvl) {
             const Geom *gl = &p.geo[(size_t)lvl * B];
             auto count = [&](int th) -> long {
                 long t = 0;
@@ -359,8 +371,11 @@ static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 // (256 lanes) in the v4 layout, whose COUNT is in bits 10 .. 15 of the int16 pad field (rans_pad_hi(); those bits are zero in every other
 // container, so a reader of the older formats finds a pad field that contradicts the size and refuses).  v = 17 .. 31 were the xwide tags of
 // the v3 layout (rounds 4-5): retired, refused.
-static int rans_byte0(int M, int Q)
+// Config B (2 levels) writes xwide v4 only, with v = 17 (byte 0 = 0xE9): a tag no reader of config A's containers accepts, so that a container
+// names the model that wrote it (config A's bytes are untouched).  Its pad field holds 4 pad bits and the count (bits 4 .. 9 zero).
+static int rans_byte0(int M, int Q, int nlev)
 {
+    if (nlev == kLevelsB && Q == 4) return 0xE9;
     const int ext = (M > 32 || Q > 1) ? 1 : 0;
     const int v = Q == 4 ? 16 : Q == 2 ? M + 1 : M > 32 ? (M == 64 ? 0 : 1) : M - 1;
     return 0x88 | (ext << 6) | (((v >> 3) & 3) << 4) | (v & 7);
@@ -381,6 +396,26 @@ static int rans_streams_of_header(int b0, int padfield)
     return (v - 1) | 0x100;
 }
 
+// Levels of the model that wrote a header (5: config A, 2: config B), 0: not a container this build reads.  The AC container stores the number
+// of scales in byte 0 (the reference: LLICTI_nets.py:347); config B's pad field has 4 bits, and its rANS containers the tag 0xE9 (rans_byte0).
+static int header_levels(int b0, int padfield)
+{
+    if (b0 == LLICTI_NLEVELS) return LLICTI_NLEVELS;
+    if (b0 == kLevelsB) return (padfield >> (2 * kLevelsB)) == 0 ? kLevelsB : 0;
+    if (b0 == 0xE9) return ((padfield & 0x3F0) == 0 && rans_streams_of_header(0xE8, padfield) != 0) ? kLevelsB : 0;
+    return rans_streams_of_header(b0, padfield) ? LLICTI_NLEVELS : 0;
+}
+// rans_streams_of_header of either model's tags
+static int header_streams(int b0, int padfield) { return rans_streams_of_header(b0 == 0xE9 ? 0xE8 : b0, padfield); }
+// the modes a model's whole-batch calls take: config A every one; config B the reference format and xwide v4 streams, at most 9 L = 18 per image
+// (one per container segment; "auto" counts whose largest pick stays within that)
+static bool model_takes(int nlev, int ME)
+{
+    if (nlev == LLICTI_NLEVELS || (ME & 0xFF) == 0) return true;
+    const int M = ME & 0xFF;
+    return ((ME >> 8) & 3) == 2 && ((ME & 0x1000) ? rans_auto_hi(M) : M) <= 9 * nlev;
+}
+
 static int check_dims_v(int B, const int *Hs, const int *Ws)
 {
     if (B < 1 || !Hs || !Ws) return fail(LLICTI_EINVAL, "bad batch: B=%d (need B>=1 and the sizes of every image)", B);
@@ -389,7 +424,7 @@ static int check_dims_v(int B, const int *Hs, const int *Ws)
     return 0;
 }
 // modes: one mode (n_modes = 1) or one per image (rANS containers of one lane kind, stream counts may differ)
-static size_t plan_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes, int n_modes)
+static size_t plan_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int nlev = LLICTI_NLEVELS)
 {
     if (check_dims_v(B, Hs, Ws) || !modes || (n_modes != 1 && n_modes != B)) return 0;
     int ME = mode_streams(modes[0]);
@@ -406,8 +441,8 @@ static size_t plan_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const
         if (any_auto) ME |= 0x1000;
     }
     Plan p, q;
-    build_plan(p, B, Hs, Ws, nullptr, ME, 256, 0, false, Ms.empty() ? nullptr : Ms.data());
-    build_plan(q, B, Hs, Ws, nullptr, ME, 256, 0, true, Ms.empty() ? nullptr : Ms.data());      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)
+    build_plan(p, B, Hs, Ws, nullptr, ME, 256, 0, false, Ms.empty() ? nullptr : Ms.data(), nlev);
+    build_plan(q, B, Hs, Ws, nullptr, ME, 256, 0, true, Ms.empty() ? nullptr : Ms.data(), nlev);      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)
     return std::max(p.total, q.total);
 }
 static size_t plan_workspace_bytes_v(int B, const int *Hs, const int *Ws, int mode) { return plan_workspace_bytes_vm(B, Hs, Ws, &mode, 1); }
@@ -417,16 +452,16 @@ static size_t plan_workspace_bytes(int B, int H, int W, int mode)
     std::vector<int> Hs(B, H), Ws(B, W);
     return plan_workspace_bytes_v(B, Hs.data(), Ws.data(), mode);
 }
-static size_t plan_max_container_bytes(int H, int W)
+static size_t plan_max_container_bytes(int H, int W, int nlev = LLICTI_NLEVELS)
 {
     if (check_dims(1, H, W)) return 0;
     Plan p, q;
-    build_plan(p, 1, &H, &W, nullptr, 32);     // covers the AC container and M <= 32 ...
-    build_plan(q, 1, &H, &W, nullptr, kRansMaxStreams);     // ... and the many-stream latency modes (more per-stream slack)
+    build_plan(p, 1, &H, &W, nullptr, 32, 256, 0, false, nullptr, nlev);     // covers the AC container and M <= 32 ...
+    build_plan(q, 1, &H, &W, nullptr, kRansMaxStreams, 256, 0, false, nullptr, nlev);     // ... and the many-stream latency modes (more per-stream slack)
     Plan a, w, x;
-    build_plan(a, 1, &H, &W, nullptr, 0);
-    build_plan(w, 1, &H, &W, nullptr, 14 | 0x100);          // ... and wide ...
-    build_plan(x, 1, &H, &W, nullptr, 128 | 0x200);         // ... and xwide streams (larger state blocks)
+    build_plan(a, 1, &H, &W, nullptr, 0, 256, 0, false, nullptr, nlev);
+    build_plan(w, 1, &H, &W, nullptr, 14 | 0x100, 256, 0, false, nullptr, nlev);          // ... and wide ...
+    build_plan(x, 1, &H, &W, nullptr, 128 | 0x200, 256, 0, false, nullptr, nlev);         // ... and xwide streams (larger state blocks)
     return std::max(std::max(std::max(p.max_container, q.max_container), std::max(w.max_container, x.max_container)), a.max_container);
 }
 
@@ -435,12 +470,13 @@ static int plan_header_dims(const uint8_t *h, int *H, int *W)
     if (!h || !H || !W) return fail(LLICTI_EINVAL, "header_dims: null pointer");
     if ((h[0] & 0x88) == 0x80)
         return fail(LLICTI_EFORMAT, "header: byte 0 = 0x%02x is the retired LLICTI-rANS v2 container; this build reads and writes v3 only", h[0]);
-    if (h[0] != LLICTI_NLEVELS && rans_streams_of_header(h[0], (int)(uint16_t)(h[15] | (h[16] << 8))) == 0)
-        return fail(LLICTI_EFORMAT, "header: byte 0 = 0x%02x (pad field 0x%04x) is neither %d scales (AC container) nor a rANS container tag of this build "
-                    "(the xwide v3 layout of rounds 4-5 is retired)", h[0], (unsigned)(h[15] | (h[16] << 8)), LLICTI_NLEVELS);
+    const int nlev = header_levels(h[0], (int)(uint16_t)(h[15] | (h[16] << 8)));
+    if (nlev == 0)
+        return fail(LLICTI_EFORMAT, "header: byte 0 = 0x%02x (pad field 0x%04x) is neither %d / %d scales (AC container of config A / B) nor a rANS container tag of this build "
+                    "(the xwide v3 layout of rounds 4-5 is retired)", h[0], (unsigned)(h[15] | (h[16] << 8)), LLICTI_NLEVELS, kLevelsB);
     int Hc = h[1], Wc = h[2];
     int pad = (int)(int16_t)(h[15] | (h[16] << 8));
-    for (int l = LLICTI_NLEVELS - 1; l >= 0; --l) {     // _get_padHW_lev_list, LLICTI_nets.py:533-542
+    for (int l = nlev - 1; l >= 0; --l) {     // _get_padHW_lev_list, LLICTI_nets.py:533-542
         const int padW = pad & 1; pad >>= 1;
         const int padH = pad & 1; pad >>= 1;
         Hc = 2 * Hc - padH;

@@ -52,6 +52,8 @@ struct ImgGeo {
     int Mlo;                                  // "auto" xwide encodes (LLICTI_MODE_RANS_X_AUTO): the count the image's size gives; M is then the LARGEST the encoder may
                                               // pick -- it picks per image, on the device, from what the image's last stage costs (rans_auto_hi / rans_auto_min,
                                               // choose_streams_kernel) -- and the table holds M streams for it.  0: the count is M, fixed by the caller
+    int dcs;                                  // pixel stride of the raw DC band (the last level's x00: 2 << (L - 1), 32 for config A)
+    int nseg;                                 // container segments of the model: 4 + 9 L
     long plane;                               // H * W
     long pix_off;                             // first element of the image's [3][H][W] block in planes / fplanes (workspace)
     long rgb_off;                             // first byte of its [3][H][W] block in the caller's RGB buffer

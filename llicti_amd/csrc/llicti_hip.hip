@@ -77,7 +77,9 @@ static_assert(PROF_NCAT == LLICTI_NPROF, "include/llicti_hip.h: LLICTI_NPROF");
 
 struct llicti_ctx {
     int device = 0;
+    int head = kHead, nlev = LLICTI_NLEVELS;     // model shape (llicti_set_model): config A unless set
     float *d_pack[3] = { nullptr, nullptr, nullptr };
+    size_t pack_floats_n[3] = { 0, 0, 0 };       // floats d_pack[band] holds
     bool have[3] = { false, false, false };
     std::map<std::vector<long>, struct PlanDev *> plans;   // Plan::key -> plan + its device tables (at most kMaxPlans, least recently used out first)
     std::vector<PlanBlock> pool;      // table blocks of plans that left the cache, for the next new plan
@@ -176,14 +178,19 @@ extern "C" size_t llicti_workspace_bytes_v(int B, const int *Hs, const int *Ws, 
 extern "C" size_t llicti_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes) { return plan_workspace_bytes_vm(B, Hs, Ws, modes, B); }
 extern "C" size_t llicti_workspace_bytes(int B, int H, int W, int mode) { return plan_workspace_bytes(B, H, W, mode); }
 extern "C" size_t llicti_max_container_bytes(int H, int W) { return plan_max_container_bytes(H, W); }
+extern "C" size_t llicti_workspace_bytes_ctx(const llicti_ctx *c, int B, const int *Hs, const int *Ws, const int *modes, int n_modes)
+{
+    return c ? plan_workspace_bytes_vm(B, Hs, Ws, modes, n_modes, c->nlev) : 0;
+}
+extern "C" size_t llicti_max_container_bytes_ctx(const llicti_ctx *c, int H, int W) { return c ? plan_max_container_bytes(H, W, c->nlev) : 0; }
 extern "C" int llicti_header_dims(const uint8_t *h, int *H, int *W) { return plan_header_dims(h, H, W); }
 extern "C" int llicti_header_mode(const uint8_t *h, int *mode)
 {
     if (!h || !mode) return fail(LLICTI_EINVAL, "header_mode: null pointer");
     int H = 0, W = 0;
     if (int rc = plan_header_dims(h, &H, &W)) return rc;          // (rejects what this build does not read, with the reason)
-    if (h[0] == LLICTI_NLEVELS) { *mode = 0; return LLICTI_OK; }
-    const int v = rans_streams_of_header(h[0], (int)(uint16_t)(h[15] | (h[16] << 8)));
+    if (h[0] == LLICTI_NLEVELS || h[0] == kLevelsB) { *mode = 0; return LLICTI_OK; }
+    const int v = header_streams(h[0], (int)(uint16_t)(h[15] | (h[16] << 8)));
     *mode = ((v >> 8) == 2 ? 0x500 : (v >> 8) == 1 ? 0x300 : 0x100) | (v & 0xFF);
     return LLICTI_OK;
 }
@@ -226,7 +233,9 @@ extern "C" int llicti_create(llicti_ctx **out, int device)
     // the band CNN stages a whole head (up to 86 KB) in LDS
 #define LLICTI_CNN_ATTR(BAND, TH_) \
     HIPCHK(hipFuncSetAttribute((const void *)band_params_kernel<BAND, TH_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_))); \
-    HIPCHK(hipFuncSetAttribute((const void *)band_params_kernel<BAND, TH_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_)))
+    HIPCHK(hipFuncSetAttribute((const void *)band_params_kernel<BAND, TH_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_))); \
+    HIPCHK(hipFuncSetAttribute((const void *)band_params_h60_kernel<BAND, TH_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_, kHeadB))); \
+    HIPCHK(hipFuncSetAttribute((const void *)band_params_h60_kernel<BAND, TH_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_, kHeadB)))
     LLICTI_CNN_ATTR(0, kTileHMax); LLICTI_CNN_ATTR(1, kTileHMax); LLICTI_CNN_ATTR(2, kTileHMax);
     LLICTI_CNN_ATTR(0, kTileHMid); LLICTI_CNN_ATTR(1, kTileHMid); LLICTI_CNN_ATTR(2, kTileHMid);
     LLICTI_CNN_ATTR(0, kTileHSmall); LLICTI_CNN_ATTR(1, kTileHSmall); LLICTI_CNN_ATTR(2, kTileHSmall);
@@ -278,11 +287,13 @@ extern "C" int llicti_set_band_weights(llicti_ctx *c, int band, int K0, const fl
     static const int K0s[3] = { 48, 72, 120 };
     if (K0 != K0s[band]) return fail(LLICTI_EINVAL, "set_band_weights: band %d needs K0=%d, got %d", band, K0s[band], K0);
     std::vector<float> pk;
-    pack_band(K0, w0, b0, w1, b1, w2, b2, pk);
+    pack_band(K0, c->head, w0, b0, w1, b1, w2, b2, pk);          // (the arrays are the context's model's: llicti_set_model)
     DeviceGuard guard(c);
     // blocking by contract (include/llicti_hip.h): work in flight on any stream may still read the old weights
     HIPCHK(hipDeviceSynchronize());
+    if (c->d_pack[band] && c->pack_floats_n[band] != pk.size()) { HIPCHK(hipFree(c->d_pack[band])); c->d_pack[band] = nullptr; }
     if (!c->d_pack[band]) HIPCHK(hipMalloc(&c->d_pack[band], pk.size() * sizeof(float)));
+    c->pack_floats_n[band] = pk.size();
     HIPCHK(hipMemcpy(c->d_pack[band], pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     c->have[band] = true;
     return LLICTI_OK;
@@ -293,6 +304,19 @@ static void drop_plans(llicti_ctx *c)
 {
     for (auto &kv : c->plans) { c->pool.push_back(kv.second->blk); delete kv.second; }
     c->plans.clear();
+}
+
+extern "C" int llicti_set_model(llicti_ctx *c, int head, int nlevels)
+{
+    if (!c) return fail(LLICTI_EINVAL, "set_model: null ctx");
+    if (!((head == kHead && nlevels == LLICTI_NLEVELS) || (head == kHeadB && nlevels == kLevelsB)))
+        return fail(LLICTI_EINVAL, "set_model: (head %d, %d levels) -- this build runs config A (88, 5) and config B (60, 2)", head, nlevels);
+    if (head == c->head && nlevels == c->nlev) return LLICTI_OK;
+    c->head = head;
+    c->nlev = nlevels;
+    for (int b = 0; b < 3; ++b) c->have[b] = false;      // the weights of the other shape no longer apply (the buffers are reused or replaced)
+    drop_plans(c);                                       // (a plan is built for the model's levels)
+    return LLICTI_OK;
 }
 
 extern "C" int llicti_set_tuning(llicti_ctx *c, const char *key, int value)
@@ -331,7 +355,7 @@ extern "C" int llicti_workspace_planes(llicti_ctx *c, int B, int H, int W, int m
     if (ME < 0) return fail(LLICTI_EINVAL, "workspace_planes: unknown mode 0x%x", mode);
     std::vector<int> Hs(B, H), Ws(B, W);
     Plan p;
-    build_plan(p, B, Hs.data(), Ws.data(), nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0);
+    build_plan(p, B, Hs.data(), Ws.data(), nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, nullptr, c->nlev);
     if (!p.uniform && B > 1) return fail(LLICTI_EINVAL, "workspace_planes: with the tuning switch force_ragged the images of a batch are not tightly packed");
     *off_planes = p.off_planes;
     *off_fplanes = p.off_fplanes;
@@ -377,6 +401,37 @@ static int launch_lift(const uint8_t *d_rgb, int B, long plane, bool vec_ok, int
     return 0;
 }
 
+// The band CNN of config B (60-wide heads): the 18 forms of config A's, same grid and tile lists (launch_band_params decides them).
+static int launch_band_params_h60(llicti_ctx *c, const float *fplanes, const Geom &g, int band, float *params, hipStream_t s, const Geom *gv,
+                                  const TileRef *tiles, int form, int gx, int lds_bytes, int tiles_x, int tiles_y, int n_tiles)
+{
+    dim3 grid((unsigned)gx, 4);
+#define LLICTI_CNN_LAUNCH(BAND, TH_, RAG) band_params_h60_kernel<BAND, TH_, RAG><<<grid, 64 * TH_, lds_bytes, s>>>(fplanes, g, c->d_pack[BAND], params, tiles_x, tiles_y, n_tiles, gv, tiles)
+    switch (form) {
+    case 0: LLICTI_CNN_LAUNCH(0, kTileHMax, false); break;
+    case 1: LLICTI_CNN_LAUNCH(1, kTileHMax, false); break;
+    case 2: LLICTI_CNN_LAUNCH(2, kTileHMax, false); break;
+    case 3: LLICTI_CNN_LAUNCH(0, kTileHSmall, false); break;
+    case 4: LLICTI_CNN_LAUNCH(1, kTileHSmall, false); break;
+    case 5: LLICTI_CNN_LAUNCH(2, kTileHSmall, false); break;
+    case 6: LLICTI_CNN_LAUNCH(0, kTileHMid, false); break;
+    case 7: LLICTI_CNN_LAUNCH(1, kTileHMid, false); break;
+    case 8: LLICTI_CNN_LAUNCH(2, kTileHMid, false); break;
+    case 9: LLICTI_CNN_LAUNCH(0, kTileHMax, true); break;
+    case 10: LLICTI_CNN_LAUNCH(1, kTileHMax, true); break;
+    case 11: LLICTI_CNN_LAUNCH(2, kTileHMax, true); break;
+    case 12: LLICTI_CNN_LAUNCH(0, kTileHSmall, true); break;
+    case 13: LLICTI_CNN_LAUNCH(1, kTileHSmall, true); break;
+    case 14: LLICTI_CNN_LAUNCH(2, kTileHSmall, true); break;
+    case 15: LLICTI_CNN_LAUNCH(0, kTileHMid, true); break;
+    case 16: LLICTI_CNN_LAUNCH(1, kTileHMid, true); break;
+    default: LLICTI_CNN_LAUNCH(2, kTileHMid, true); break;
+    }
+#undef LLICTI_CNN_LAUNCH
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // One band-CNN launch.  Equal sizes (tiles == nullptr): B images of g's size, tile -> image by division; mixed sizes: the plan's tile list of
 // this (level, band) and its per-image geometry table, form and grid chosen when the plan was built.
 static int launch_band_params(llicti_ctx *c, const float *fplanes, const Geom &g, int band, float *params, hipStream_t s,
@@ -394,12 +449,13 @@ static int launch_band_params(llicti_ctx *c, const float *fplanes, const Geom &g
     const int tiles_y = (g.h + TH - 1) / TH;
     if (n_tiles_l > 0x7FFFFFFFL || n_tiles_l < 1) return fail(LLICTI_EINVAL, "band_params: bad tile count");
     const int n_tiles = (int)n_tiles_l;
-    const int lds_bytes = cnn_lds_bytes(band, TH);
+    const int lds_bytes = cnn_lds_bytes(band, TH, c->head);
     const int kCnnThreads = 64 * TH;
     dim3 grid((unsigned)gx, 4);
     ProfSpan span(c, PROF_CNN, s, g.lvl);
-#define LLICTI_CNN_LAUNCH(BAND, TH_, RAG) band_params_kernel<BAND, TH_, RAG><<<grid, kCnnThreads, lds_bytes, s>>>(fplanes, g, c->d_pack[BAND], params, tiles_x, tiles_y, n_tiles, gv, tiles)
     const int form = band + (TH == kTileHSmall ? 3 : TH == kTileHMid ? 6 : 0) + (tiles ? 9 : 0);
+    if (c->head == kHeadB) return launch_band_params_h60(c, fplanes, g, band, params, s, gv, tiles, form, gx, lds_bytes, tiles_x, tiles_y, n_tiles);
+#define LLICTI_CNN_LAUNCH(BAND, TH_, RAG) band_params_kernel<BAND, TH_, RAG><<<grid, kCnnThreads, lds_bytes, s>>>(fplanes, g, c->d_pack[BAND], params, tiles_x, tiles_y, n_tiles, gv, tiles)
     switch (form) {
     case 0: LLICTI_CNN_LAUNCH(0, kTileHMax, false); break;
     case 1: LLICTI_CNN_LAUNCH(1, kTileHMax, false); break;
@@ -452,7 +508,7 @@ extern "C" int llicti_band_params_f32(llicti_ctx *c, const float *d_fplanes, int
     if (!c || !d_fplanes || !d_params) return fail(LLICTI_EINVAL, "band_params: null pointer");
     DeviceGuard guard(c);
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
-    if (lvl < 0 || lvl >= LLICTI_NLEVELS || band < 0 || band > 2) return fail(LLICTI_EINVAL, "band_params: bad level/band");
+    if (lvl < 0 || lvl >= c->nlev || band < 0 || band > 2) return fail(LLICTI_EINVAL, "band_params: bad level/band (the model has %d levels)", c->nlev);
     Geom g = make_geom(B, H, W, lvl);
     return launch_band_params(c, d_fplanes, g, band, d_params, (hipStream_t)stream);
 }
@@ -475,7 +531,7 @@ extern "C" int llicti_selfinfo_f32(llicti_ctx *c, const float *d_fplanes, const 
     if (!c || !d_fplanes || !d_params || !d_bits) return fail(LLICTI_EINVAL, "selfinfo: null pointer");
     DeviceGuard guard(c);
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
-    if (lvl < 0 || lvl >= LLICTI_NLEVELS || band < 0 || band > 2) return fail(LLICTI_EINVAL, "selfinfo: bad level/band");
+    if (lvl < 0 || lvl >= c->nlev || band < 0 || band > 2) return fail(LLICTI_EINVAL, "selfinfo: bad level/band (the model has %d levels)", c->nlev);
     Geom g = make_geom(B, H, W, lvl);
     StageGeom sg = make_stage(g, band);
     SelfGeom s;
@@ -526,7 +582,7 @@ extern "C" int llicti_cdf_u16(llicti_ctx *c, const int16_t *d_planes, const floa
     if (!c || !d_planes || !d_params || !d_minmax || !d_tables) return fail(LLICTI_EINVAL, "cdf_u16: null pointer");
     DeviceGuard guard(c);
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
-    if (lvl < 0 || lvl >= LLICTI_NLEVELS || band < 0 || band > 2 || clr < 0 || clr > 2) return fail(LLICTI_EINVAL, "cdf_u16: bad level/band/clr");
+    if (lvl < 0 || lvl >= c->nlev || band < 0 || band > 2 || clr < 0 || clr > 2) return fail(LLICTI_EINVAL, "cdf_u16: bad level/band/clr");
     if (row_stride < 8 || row_stride > 512 || (row_stride & 7)) return fail(LLICTI_EINVAL, "cdf_u16: row_stride must be a multiple of 8 in [8,512]");
     Geom g = make_geom(B, H, W, lvl);
     int hc, wc;
@@ -541,7 +597,7 @@ extern "C" int llicti_cdf_pairs_u32(llicti_ctx *c, const int16_t *d_planes, cons
     if (!c || !d_planes || !d_params || !d_minmax || !d_pairs) return fail(LLICTI_EINVAL, "cdf_pairs: null pointer");
     DeviceGuard guard(c);
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
-    if (lvl < 0 || lvl >= LLICTI_NLEVELS || band < 0 || band > 2) return fail(LLICTI_EINVAL, "cdf_pairs: bad level/band");
+    if (lvl < 0 || lvl >= c->nlev || band < 0 || band > 2) return fail(LLICTI_EINVAL, "cdf_pairs: bad level/band");
     Geom g = make_geom(B, H, W, lvl);
     return launch_cdf_pairs(d_planes, d_params, d_minmax, g, band, d_pairs, (hipStream_t)stream);
 }
@@ -643,7 +699,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     std::unique_ptr<PlanDev> pd(new PlanDev());
     Plan &p = pd->p;
     ++c->n_plan_build;
-    build_plan(p, B, Hs, Ws, rgb_off, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms);
+    build_plan(p, B, Hs, Ws, rgb_off, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms, c->nlev);
     if (p.key != key) return fail(LLICTI_EINVAL, "plan: key mismatch");
     if (p.rslot_off.size() != (size_t)p.nstreams || p.sref.size() != (size_t)p.nstreams)
         return fail(LLICTI_EINVAL, "plan: stream tables have %zu / %zu entries, expected %d", p.rslot_off.size(), p.sref.size(), p.nstreams);
@@ -746,6 +802,17 @@ static int resolve_modes(const char *who, const int *modes, int n_modes, int B, 
     return 0;
 }
 
+// the container modes the context's model takes (host_plan.hpp: model_takes)
+static int check_model(const llicti_ctx *c, const char *who, int ME, const std::vector<int> &Ms)
+{
+    bool ok = model_takes(c->nlev, ME);
+    for (int m : Ms) ok = ok && model_takes(c->nlev, (ME & 0x300) | m);
+    if (!ok)
+        return fail(LLICTI_EINVAL, "%s: a %d-level model (config B) codes the reference-format container or xwide v4 streams, at most %d per image "
+                    "(\"auto\": a size-rule count of at most 13)", who, c->nlev, 9 * c->nlev);
+    return 0;
+}
+
 extern "C" int llicti_workspace_params_v(llicti_ctx *c, int B, const int *Hs, const int *Ws, const int *modes, int image, size_t *off_params, long *npos)
 {
     if (!c || !off_params || !npos || !modes) return fail(LLICTI_EINVAL, "workspace_params_v: null argument");
@@ -755,7 +822,7 @@ extern "C" int llicti_workspace_params_v(llicti_ctx *c, int B, const int *Hs, co
     std::vector<int> Ms;
     if (int rc = resolve_modes("workspace_params_v", modes, B, B, &ME, Ms)) return rc;
     Plan p;
-    build_plan(p, B, Hs, Ws, nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms.empty() ? nullptr : Ms.data());
+    build_plan(p, B, Hs, Ws, nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms.empty() ? nullptr : Ms.data(), c->nlev);
     const Geom &g = p.geo[(size_t)0 * B + image];            // level 0: the last level both passes launch
     *off_params = p.off_params + (size_t)g.par_off * sizeof(float);
     *npos = (long)g.h * g.w;
@@ -770,6 +837,14 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
     int ME = 0;
     std::vector<int> Ms;
     if (int rc = resolve_modes("encode_images", modes, n_modes, B, &ME, Ms)) return rc;
+    if (int rc = check_model(c, "encode_images", ME, Ms)) return rc;
+    if (c->nlev < LLICTI_NLEVELS)
+        for (int b = 0; b < B; ++b) {
+            const Geom gl = make_geom(1, Hs[b], Ws[b], c->nlev - 1);
+            if (gl.h > 255 || gl.w > 255)
+                return fail(LLICTI_EINVAL, "encode_images: image %d is %dx%d; a %d-level model's header stores its level-%d grid (%dx%d) in one byte each "
+                            "(at most %d pixels per side)", b, Ws[b], Hs[b], c->nlev, c->nlev - 1, gl.w, gl.h, 255 << c->nlev);
+        }
     const int Q = 1 << ((ME >> 8) & 3);
     const bool autoM = (ME & 0x1000) != 0;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
@@ -819,7 +894,7 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
         HIPCHK(hipEventRecord(c->ev_enc[0], s));      // lift and header are done
         HIPCHK(hipStreamWaitEvent(s2, c->ev_enc[0], 0));
     }
-    for (int lvl = LLICTI_NLEVELS - 1; lvl >= 0; --lvl) {
+    for (int lvl = p.nlev - 1; lvl >= 0; --lvl) {
         const Geom &g = p.geo[(size_t)lvl * B];                         // image 0's (equal sizes: every image's)
         const Geom *gv = p.uniform ? nullptr : d_geo + (size_t)lvl * B;
         hipStream_t s = (lvl >= 1) ? s2 : (hipStream_t)stream;          // (shadows the call's stream inside the loop)
@@ -857,9 +932,10 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
     }
     if (M == 0) {
         ProfSpan span(c, PROF_AC, s);
-        const int n_streams = LLICTI_NSTREAMS * B;
-        ac_encode_pairs_kernel<<<n_streams, 64, 0, s>>>(pairs, d_desc, n_streams, slots, slot_len, status);
-        pack_kernel<<<dim3(LLICTI_NSTREAMS, B), 256, 0, s>>>(slots, pd->dev<long>(p.d_slot_off), slot_len, B, p.img[0].hdr_bytes, d_out, (long)out_stride, d_seg_len, status);
+        const int st0 = first_stage(p.nlev), nst = LLICTI_NSTREAMS - st0;      // (the model's stages)
+        const int n_streams = nst * B;
+        ac_encode_pairs_kernel<<<n_streams, 64, 0, s>>>(pairs, d_desc + (size_t)st0 * B, n_streams, slots, slot_len + (size_t)st0 * B, status);
+        pack_kernel<<<dim3(nst, B), 256, 0, s>>>(slots, pd->dev<long>(p.d_slot_off), slot_len, B, p.img[0].hdr_bytes, d_out, (long)out_stride, d_seg_len, status, st0);
     } else {
         ProfSpan span(c, PROF_RANS_ENC, s);
         int32_t *rinfo = (int32_t *)(ws + p.off_rinfo);
@@ -932,7 +1008,8 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
         ProfSpan span(c, PROF_MISC, s);
         header_read_kernel<<<B, 256, 0, s>>>(d_in, (long)in_stride, d_seg_len, d_img, planes, fplanes, mm, status);
         if (M == 0) {
-            unpack_kernel<<<dim3(LLICTI_NSTREAMS, B), 256, 0, s>>>(d_in, (long)in_stride, d_seg_len, B, slots, pd->dev<long>(p.d_slot_off), pd->dev<int32_t>(p.d_slot_cap), slot_len, status);
+            const int st0 = first_stage(p.nlev);
+            unpack_kernel<<<dim3(LLICTI_NSTREAMS - st0, B), 256, 0, s>>>(d_in, (long)in_stride, d_seg_len, B, slots, pd->dev<long>(p.d_slot_off), pd->dev<int32_t>(p.d_slot_cap), slot_len, status, st0);
         } else {
             const StageGeom *sglv = d_sg + (size_t)(0 * 3 + 2) * B;      // the last stage: an xwide v4 tail is at most the stream's share of it
             rans_unpack_kernel<<<NS, 256, 0, s>>>(d_in, (long)in_stride, d_seg_len, d_sref, 2 + Q * RansGeo<1>::kPayBytes,
@@ -942,8 +1019,8 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
             else rans_init_kernel<1><<<NS, 64, 0, s>>>(slots, d_rslot_off, d_sref, rstate, rpos, rtail, status, sglv);
         }
     }
-    // 45 dependent stages (LLICTI_nets.py:440-498): CNN of band b needs bands < b of this level, Co needs Y, Cg needs Y, Co
-    for (int lvl = LLICTI_NLEVELS - 1; lvl >= 0; --lvl) {
+    // 45 dependent stages (LLICTI_nets.py:440-498; 9 L for a model of L levels): CNN of band b needs bands < b of this level, Co needs Y, Cg needs Y, Co
+    for (int lvl = p.nlev - 1; lvl >= 0; --lvl) {
         const Geom &g = p.geo[(size_t)lvl * B];                         // image 0's (equal sizes: every image's)
         const Geom *gv = p.uniform ? nullptr : d_geo + (size_t)lvl * B;
         for (int band = 0; band < 3; ++band) {
@@ -1035,6 +1112,7 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
     int ME = 0;
     std::vector<int> Ms;
     if (int rc = resolve_modes("decode_images", modes, n_modes, B, &ME, Ms)) return rc;
+    if (int rc = check_model(c, "decode_images", ME, Ms)) return rc;
     if (ME & 0x1000) return fail(LLICTI_EINVAL, "decode_images: LLICTI_MODE_RANS_X_AUTO is an encoder's mode -- a container says how many streams it has (header: llicti_header_mode)");
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);

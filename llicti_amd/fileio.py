@@ -7,7 +7,8 @@ The reference never writes a compressed file: `compress` returns a Python list o
   * `.llic` file = magic b"LLIC", format version (1 byte), number of segments n (1 byte), n little-endian
     uint32 segment lengths, then the segments back to back -- exactly the device container of
     include/llicti_hip.h (header triplet, raw DC band, then the 45 AC streams or the M rANS streams) with its
-    `seg_len` row in front, so a file maps to a `bytestream_list` and back without touching a byte of payload;
+    `seg_len` row in front, so a file maps to a `bytestream_list` and back without touching a byte of payload.  The segment count n
+    names the model: 49 = 4 + 9 x 5 levels (config A), 22 = 4 + 9 x 2 (config B) -- the format needed no change for the second model;
   * 8-bit RGB images as uint8 [3, H, W]: binary PPM (P6) natively, PNG/JPG through PIL when it is installed.
 """
 from __future__ import annotations
@@ -20,19 +21,20 @@ import numpy as np
 MAGIC = b"LLIC"
 VERSION = 1
 NSEG = 49
+NSEGS = (49, 22)        # config A, config B
 
 
 def bytestream_list_to_segments(bl):
-    if len(bl) != 6 or any(len(r) != 9 for r in bl):
-        raise ValueError("bytestream_list must be 6 lists of 9 byte strings")
+    if len(bl) not in (6, 3) or any(len(r) != 9 for r in bl):
+        raise ValueError("bytestream_list must be 6 (config A) or 3 (config B) lists of 9 byte strings")
     return list(bl[0][:4]) + [s for row in bl[1:] for s in row]
 
 
 def segments_to_bytestream_list(segs):
-    if len(segs) != NSEG:
-        raise ValueError(f"expected {NSEG} segments, got {len(segs)}")
+    if len(segs) not in NSEGS:
+        raise ValueError(f"expected {NSEG} (config A) or 22 (config B) segments, got {len(segs)}")
     em = b""
-    return [[segs[0], segs[1], segs[2], segs[3], em, em, em, em, em]] + [list(segs[4 + 9 * s: 13 + 9 * s]) for s in range(5)]
+    return [[segs[0], segs[1], segs[2], segs[3], em, em, em, em, em]] + [list(segs[4 + 9 * s: 13 + 9 * s]) for s in range((len(segs) - 4) // 9)]
 
 
 def dumps_llic(bl) -> bytes:
@@ -47,7 +49,7 @@ def loads_llic(buf: bytes):
     if buf[4] != VERSION:
         raise ValueError(f"unsupported LLIC version {buf[4]}")
     n = buf[5]
-    if n != NSEG or len(buf) < 6 + 4 * n:
+    if n not in NSEGS or len(buf) < 6 + 4 * n:
         raise ValueError("truncated or malformed LLIC index")
     lens = struct.unpack("<%dI" % n, buf[6:6 + 4 * n])
     pos, segs = 6 + 4 * n, []

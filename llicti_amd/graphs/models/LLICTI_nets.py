@@ -20,7 +20,7 @@ import torch
 from torch import nn
 
 from ...codec import (MODE_AC, MODE_RANS, NSEG, HipCodec, auto_modes, bytestream_list_to_container, container_to_bytestream_list, header_dims, mode_of_header, mode_of_name)
-from ...config import check_supported
+from ...config import check_supported, model_shape
 
 
 class _LowerBound(nn.Module):
@@ -128,6 +128,7 @@ class LLICTI(nn.Module):
                 p = next(self.parameters())
                 dev = p.device if p.is_cuda else None
             self._codec = HipCodec(dev)
+            self._codec.set_model(*model_shape(self.config))       # (config B: 60-wide heads, 2 levels; a new context is config A)
         key = self._weights_key()
         if key != self._weights_version:
             self._codec.load_state_dict({k: v for k, v in self.state_dict().items()})
@@ -138,7 +139,7 @@ class LLICTI(nn.Module):
     def forward(self, x):
         """Validation likelihood (LLICTI_nets.py:101-123): x float32 [B,3,H,W] in {k/255} (or uint8), H and W
         multiples of 32 (lazyDWT(pad=False) needs equal sub-band sizes; the reference's validate() pads first,
-        llicti_agent.py:105-113) -> list of 5 tensors [B, 9, h, w] of -log2 pmf in bits, scale 0 first,
+        llicti_agent.py:105-113) -> list of L tensors (5: config A, 2: config B) [B, 9, h, w] of -log2 pmf in bits, scale 0 first,
         channel = 3 * band + colour.  Inference only: the kernels do not produce gradients (training stays
         outside this package)."""
         assert x.dim() == 4 and x.shape[1] == 3
@@ -174,7 +175,7 @@ class LLICTI(nn.Module):
         if not sizes:
             raise ValueError('container "auto" needs the image sizes')
         sz = list(sizes) if len(sizes) == B else [sizes[0]] * B
-        modes = auto_modes(sz)
+        modes = auto_modes(sz, self.num_scales)
         return modes[0] if all(m == modes[0] for m in modes) else modes
 
     def _pinned(self, key, nbytes):
@@ -315,8 +316,8 @@ class LLICTI(nn.Module):
         codec = self.codec(devc if (devc is not None and torch.device(devc).type == "cuda") else None)
         Hs, Ws, modes = [], [], []
         for bl in lists:
-            if len(bl) != 6 or any(len(r) != 9 for r in bl):
-                raise ValueError("bytestream_list must be 6 lists of 9 byte strings")
+            if len(bl) != 1 + self.num_scales or any(len(r) != 9 for r in bl):
+                raise ValueError(f"bytestream_list must be {1 + self.num_scales} lists of 9 byte strings (1 + the model's {self.num_scales} levels)")
             if len(bl[0][0]) != 3 or len(bl[0][1]) != 12 or len(bl[0][2]) != 2:
                 raise ValueError("malformed header streams")
             hdr = bytes(bl[0][0]) + bytes(bl[0][1]) + bytes(bl[0][2])
@@ -347,6 +348,7 @@ class LLICTI(nn.Module):
                     seg_np[i, k] = n
                     pos += n
                     k += 1
+            seg_np[i, k:] = 0                            # (config B: 22 segments; the pinned buffer is reused)
         cur = torch.cuda.current_stream(codec.device)
         up, _ = self._copy_streams(codec.device)
         with torch.cuda.stream(up):
@@ -374,7 +376,7 @@ class EncodedBatch:
         self._lists = None
 
     def lists(self, check=True):
-        """Wait for the download (NOT for anything enqueued after it) and cut the containers into bytestream_lists (6 lists x 9 `bytes`).
+        """Wait for the download (NOT for anything enqueued after it) and cut the containers into bytestream_lists (1 + L lists x 9 `bytes`).
         check=False leaves the device-side status to a later codec.check() (which synchronises the whole stream)."""
         if self._lists is None:
             self.ev.synchronize()

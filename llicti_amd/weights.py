@@ -13,6 +13,8 @@ numerics spec is written in:
     w1 [352][88], b1 [352]    grouped 1x1 (4 heads of 88)
     w2 [60][88],  b2 [60]     grouped 1x1 (4 heads of 15 outputs)
 
+(config A, 88-wide heads; config B has 60-wide heads: 240 for 352, 60 for 88 -- the width is read from the tensors).
+
 compressai's extra buffers in a real checkpoint (`*_bound.bound`, `scale_table`, `_offset`,
 `_quantized_cdf`, `_cdf_length` ...) are ignored: the bounds 0.11/255 and 1e-6 are constants of the
 spec (entropy_layer_nets.py:149-158).
@@ -29,7 +31,8 @@ LAYER0 = {
     2: ["layer0_00_10", "layer0_11_10", "layer0_01_10"],
 }
 K0 = {0: 48, 1: 72, 2: 120}
-NCH, HEAD, NPAR = 352, 88, 60
+NCH, HEAD, NPAR = 352, 88, 60          # config A
+HEADS = (88, 60)                       # head widths of the two configurations this build runs (A, B)
 
 
 def _np(v):
@@ -38,32 +41,44 @@ def _np(v):
     return np.ascontiguousarray(np.asarray(v, dtype=np.float32))
 
 
+def head_of_state_dict(sd) -> int:
+    """Channels per head of a reference state_dict: 88 (config A) or 60 (config B), from layers1toL.2.weight [60, head, 1, 1]."""
+    head = int(_np(sd[f"{PREFIX}0.layers1toL.2.weight"]).shape[1])
+    if head not in HEADS:
+        raise NotImplementedError(f"state_dict has {head}-wide heads; this build runs 88 (config A) and 60 (config B)")
+    return head
+
+
 def pack_state_dict(sd) -> dict:
-    """state_dict -> {band: {"K0", "w0", "b0", "w1", "b1", "w2", "b2"}} (all float32, C-contiguous)."""
+    """state_dict -> {band: {"K0", "head", "w0", "b0", "w1", "b1", "w2", "b2"}} (all float32, C-contiguous).  The head width (88 / 60) is
+    the tensors'."""
+    head = head_of_state_dict(sd)
+    nch = 4 * head
     out = {}
     for b in range(3):
         p = f"{PREFIX}{b}."
         ws, bs = [], []
         for name in LAYER0[b]:
             w = _np(sd[p + name + ".weight"])
-            assert w.shape[0] == NCH and w.shape[1] == 3, w.shape
+            assert w.shape[0] == nch and w.shape[1] == 3, w.shape
             if w.shape[3] == 3:                      # (kh, kw) = (4, 3): walk ky fastest
                 assert w.shape[2] == 4
                 w = np.ascontiguousarray(w.transpose(0, 1, 3, 2))
             else:
                 assert w.shape[3] == 4
-            ws.append(w.reshape(NCH, -1))
+            ws.append(w.reshape(nch, -1))
             bs.append(_np(sd[p + name + ".bias"]))
         w0 = np.ascontiguousarray(np.concatenate(ws, axis=1))
-        assert w0.shape == (NCH, K0[b]), w0.shape
+        assert w0.shape == (nch, K0[b]), w0.shape
         b0 = bs[0].copy()
         for extra in bs[1:]:
             b0 = (b0 + extra).astype(np.float32)
-        w1 = _np(sd[p + "layers1toL.0.weight"]).reshape(NCH, HEAD)
+        w1 = _np(sd[p + "layers1toL.0.weight"]).reshape(nch, head)
         b1 = _np(sd[p + "layers1toL.0.bias"])
-        w2 = _np(sd[p + "layers1toL.2.weight"]).reshape(NPAR, HEAD)
+        w2 = _np(sd[p + "layers1toL.2.weight"]).reshape(NPAR, head)
         b2 = _np(sd[p + "layers1toL.2.bias"])
-        out[b] = {"K0": K0[b], "w0": w0, "b0": np.ascontiguousarray(b0), "w1": np.ascontiguousarray(w1),
+        assert b0.shape == (nch,) and b1.shape == (nch,) and b2.shape == (NPAR,), (b0.shape, b1.shape, b2.shape)
+        out[b] = {"K0": K0[b], "head": head, "w0": w0, "b0": np.ascontiguousarray(b0), "w1": np.ascontiguousarray(w1),
                   "b1": b1, "w2": np.ascontiguousarray(w2), "b2": b2}
     return out
 
@@ -92,7 +107,11 @@ def load_reference_state_dict(model, sd):
     kept = {k: v for k, v in sd.items() if not k.endswith(COMPRESSAI_EXTRA_SUFFIXES)}
     missing = [k for k in expected_keys() if k not in kept]
     if missing:
-        raise KeyError(f"checkpoint state_dict lacks {len(missing)} of the 24 weight entries of LLICTI (config A), e.g. {missing[:3]}; "
+        raise KeyError(f"checkpoint state_dict lacks {len(missing)} of the 24 weight entries of LLICTI, e.g. {missing[:3]}; "
                        f"first keys present: {list(sd)[:3]}")
+    have, want = head_of_state_dict(kept), head_of_state_dict(model.state_dict())
+    if have != want:
+        raise ValueError(f"checkpoint has {have}-wide heads (config {'A' if have == 88 else 'B'}), the model {want}-wide ones "
+                         f"(config {'A' if want == 88 else 'B'}): load it into a model built from the config it was trained with")
     model.load_state_dict(kept, strict=True)
     return model
