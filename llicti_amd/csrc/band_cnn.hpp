@@ -127,8 +127,9 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
     // For a tile whose whole halo lies inside the band grid (and off the odd edge) no clamp fires, and a lane's source
     // address is  image base + tile origin (both wave-uniform) + a constant of (wave, piece, lane): those constants are
     // computed ONCE per kernel (byte offsets, < 2^32), so that staging an interior tile costs no address arithmetic per
-    // piece -- the ~20 vector operations per piece of the general path compete with the MFMAs for the issue port
-    // (deletion experiments: staging is ~6 % of the kernel).  Border tiles take the general path.
+    // piece (the general path's ~20 vector operations per piece cost 2.2 % of the kernel: profiles/r3/tried_cnn_dma16_staging.json).  Border tiles
+    // take the general path.  (What the rest of the staging's ~5.5 % pays for is NOT the number or width of its instructions -- same file -- and not a
+    // wait for memory either: see the note at the staging sites in the tile loop.)
     // lane-dependent part: only the piece's phase t matters (row t or t + 1 of its 4-row group, column within the row)
     uint32_t lane_t[3];
     if constexpr (!RAGGED) {
@@ -217,7 +218,14 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
     static_assert(kInPitch == 48 && kInRows % 4 == 0 && kPP * 64 == kInPlane && kPP == 3 * (kInRows / 4), "piece decomposition assumes pitch 48 and whole 4-row groups");
     static_assert(kInPlane % 64 == 0, "tile plane must be a whole number of 64-float pieces");
 
-    const int stage_site = (__builtin_amdgcn_readfirstlane(wave) / (kCnnThreads >= 256 ? kCnnThreads / 256 : 1)) % CNN_STAGE_SITES;
+    // The wave groups take the sites in REVERSE order: waves 12-15, the youngest of their SIMDs, request right after the barrier and waves 0-3 last.
+    // In-kernel stamps (tools/stamp_cnn_staging.py, profiles/r7/cnn_staging_stamps.json) show a wave inside its staging site for 7-24 k cycles of
+    // band 2's 94 k-cycle tile (2-3 k of band 0's 65 k) while its drain in front of the barrier is free (~40 cycles for the DMA, ~150 for the params
+    // stores): the time a staging wave loses is paid where it stages, not where it waits.  With the sites in wave order the waves that arrive LAST at
+    // the barrier (12-15: 0.8 k cycles of barrier wait against 14 k for waves 0-3) were also the ones that lost that time two thirds into layers 1-2,
+    // with no tile left to catch up in, and ran the tile's last stretch alone.  Reversed, the latecomers pay first and the early finishers' slack pays
+    // for the late site: -1.4 % CNN time per pass.  (Requesting an interior tile's pieces one at a time between layer 0's k-steps instead: +1.3 %, slower.)
+    const int stage_site = CNN_STAGE_SITES - 1 - (__builtin_amdgcn_readfirstlane(wave) / (kCnnThreads >= 256 ? kCnnThreads / 256 : 1)) % CNN_STAGE_SITES;
     int cur = 0;
     if ((int)blockIdx.x < n_tiles) stage(blockIdx.x, lds_in);
 #if CNN_STAGGER
@@ -245,10 +253,11 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
         // memory model does not promise it (common.hpp's lds_barrier() is exactly a barrier that does not).
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        // The next tile's DMA (address arithmetic + issue: pure VALU / VMEM work) is requested at four
-        // different points of the tile, one per wave group: a SIMD hosts one wave of each group, so while
-        // one of its waves stages, the other three keep the matrix pipe busy.  (All 16 waves staging right
-        // after the barrier left the pipe idle for ~9 % of the tile.)
+        // The next tile's DMA is requested at four different points of the tile, one per wave group: a SIMD hosts
+        // one wave of each group, so while one of its waves stages, the other three keep the matrix pipe busy.
+        // (All 16 waves staging right after the barrier left the pipe idle for ~9 % of the tile.  No wave WAITS for
+        // the data: the compiler puts no vmcnt wait into this loop -- tools/cnn_wait_audit.py, tests/test_cnn_isa_cpu.py --
+        // and the explicit drain above finds everything landed.)
         const bool more = tile + (int)gridDim.x < n_tiles && (CNN_EXP_STAGE_EVERY == 1 || ((tile / (int)gridDim.x) % CNN_EXP_STAGE_EVERY) == CNN_EXP_STAGE_EVERY - 1);
         auto stage_next = [&](int site) __attribute__((always_inline)) {
             if (more && stage_site == site % CNN_STAGE_SITES) stage(tile + gridDim.x, lds_in + (cur ^ 1) * (NPL * kInPlane));
