@@ -115,10 +115,10 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 
     // Input tile: LDS-DMA (global_load_lds), double buffered.  One wave-instruction fills 64 consecutive LDS
     // floats, so the tile image [plane][20 rows][pitch 48] is cut into NPL*15 such pieces (the 12 pad columns
-    // of a row are filled with a duplicate of column 35); each lane computes its own clamped source address.
+    // of a row are filled with a duplicate of column 35); each lane requests its own (clamped) source address.
     // Pitch 48 makes four tile rows exactly three 64-float pieces, so a piece's plane, row group and phase are
-    // functions of the wave-uniform piece index (scalar arithmetic) and only ~20 vector operations per piece
-    // depend on the lane: piece phase t covers row 4q+t from column 16t (lanes below 48-16t) and the head
+    // functions of the wave-uniform piece index (scalar arithmetic) and only the column and the choice between
+    // two rows depend on the lane: piece phase t covers row 4q+t from column 16t (lanes below 48-16t) and the head
     // of row 4q+t+1 (the others).
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     constexpr int kPieces = NPL * kPP;                                               // TH = 16: 45 / 90 / 135
@@ -127,9 +127,12 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
     // For a tile whose whole halo lies inside the band grid (and off the odd edge) no clamp fires, and a lane's source
     // address is  image base + tile origin (both wave-uniform) + a constant of (wave, piece, lane): those constants are
     // computed ONCE per kernel (byte offsets, < 2^32), so that staging an interior tile costs no address arithmetic per
-    // piece (the general path's ~20 vector operations per piece cost 2.2 % of the kernel: profiles/r3/tried_cnn_dma16_staging.json).  Border tiles
-    // take the general path.  (What the rest of the staging's ~5.5 % pays for is NOT the number or width of its instructions -- same file -- and not a
-    // wait for memory either: see the note at the staging sites in the tile loop.)
+    // piece.  Border tiles reuse the same scalars: their pieces take this formula too, with the lane's CLAMPED column in the per-lane part (three
+    // phase offsets per tile) -- all but the few pieces that touch a row outside the grid, which take the general formula (see `Border tile` in
+    // stage()).  The old border path -- a rolled loop of 71 instructions per piece, 27 of them vector, that re-derived everything per piece -- cost
+    // 1.9 % of the kernel (profiles/r8/cnn_border_bound.json; 2.2 % in round 3: profiles/r3/tried_cnn_dma16_staging.json), the present one a fifth of
+    // that (profiles/r8/ab_cnn_border.json; tools/cnn_border_isa.py counts the instructions).  (What the rest of the staging's ~5.5 % pays for is
+    // NOT the number or width of its instructions -- r3 file -- and not a wait for memory either: see the note at the staging sites in the tile loop.)
     // lane-dependent part: only the piece's phase t matters (row t or t + 1 of its 4-row group, column within the row)
     uint32_t lane_t[3];
     if constexpr (!RAGGED) {
@@ -186,7 +189,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
                 if (u < kPieces) {
                     const int pl = u / kPP, v = u - kPP * pl, q4 = v / 3, t = v - 3 * q4;
                     const int src = pl / 3, ci = pl - 3 * src;
-                    const long uoff = ((long)ci * g.plane + (((long)(8 * q4 + src_oi(src)) * g.W + src_oj(src)) << g.lvl)) * 4;
+                    const uint32_t uoff = (uint32_t)(ci * (int)g.plane + (((8 * q4 + src_oi(src)) * g.W + src_oj(src)) << g.lvl)) * 4;     // < 3 planes: 32 bits (check_dims: H, W <= 8160)
                     uint32_t lo;
                     if constexpr (RAGGED) lo = lane_off(t);
                     else lo = (t == 0) ? lane_t[0] : (t == 1) ? lane_t[1] : lane_t[2];
@@ -197,17 +200,68 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
             return;
         }
 #endif
-        for (int u = wave_u; u < kPieces; u += kCnnThreads / 64) {
+        // Border tile.  Source element of halo position (r, c), sub-band (oi, oj):  row rr = 2 clamp(i0 + r) + oi, column cc = 2 clamp(j0 + c) + oj,
+        // each stepped back by 2 where it passes the odd edge (lazyDWT's replicate pad, LLICTI_nets.py:226-240).
+        //  - Columns are the lane's work, but per (tile, phase), not per piece: the phase of a wave's k-th piece is (t0 + k * waves) % 3 (kPP is a
+        //    multiple of 3), so the lane's offset with its CLAMPED column is computed for the three phases once per tile, in phase order rotated
+        //    by the wave's t0, and piece k takes index (k * waves) % 3 -- a compile-time one.  Relative to the tile's (unclamped) origin the
+        //    offset is never negative.
+        //  - Rows are wave-uniform.  A piece whose two rows lie inside the grid and off its last row (scalar test) has the interior formula's row
+        //    part as it is: it is requested like an interior piece, with the clamped-column offsets.  In a top / bottom tile that is all but the
+        //    two or three pieces per plane that touch the rows outside.
+        //  - The pieces left over (a row clamps; or, all pieces of the tile, the column's odd-edge step can fire: a tile that reaches the last
+        //    column of a grid with odd Wl) take the general formula afterwards, one by one.  Which pieces are plain is ONE ballot per tile (lane k
+        //    tests piece k), so a plain piece costs a bit test on top of an interior one and keeps no scalar of its own across the tile loop.
+        constexpr int kWaves = kCnnThreads / 64;
+        static_assert(kPP % 3 == 0 && kMyPieces >= 3 && kMyPieces <= 32, "a piece's phase is its index modulo 3; one mask bit per piece of a wave");
+        int lb = lane;
+        asm volatile("" : "+v"(lb));                            // (opaque per staged tile, as above: nothing of the lane's part is kept across the tile loop)
+        int t0 = wave_u % 3;                                    // phase of piece wave_u
+        asm volatile("" : "+s"(t0));                            // (opaque too: the phases' scalars are a few instructions per tile, and the kernel is at its SGPR budget)
+        uint32_t lt[3];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const int t = t0 + p >= 3 ? t0 + p - 3 : t0 + p;
+            const int x = lb + 16 * t;                          // columns 16 t .. of the piece's first row, then, 48 further, 0 .. of its second
+            const bool up = x >= kInPitch;
+            const int bj = max(0, min(j0 + min(up ? x - kInPitch : x, kInCols - 1), g.w - 1));     // the conv's replicate padding, in band coordinates
+            lt[p] = (uint32_t)(((up ? 2 * (t + 1) * g.W : 2 * t * g.W) + 2 * (bj - j0)) << g.lvl) * 4;
+        }
+        // rows i0 + r0 and i0 + r0 + 1 of a piece are plain when 0 <= i0 + r0 < rlim (one unsigned comparison); no piece of the tile is where
+        // the column's odd-edge step can fire (a sub-band x.1 -- bands 1 and 2 have them -- at column w - 1; an x.0 never steps: 2 (w - 1) < Wl
+        // as w = (Wl + 1) / 2, and likewise no row up to h - 2 does -- what the interior test above relies on too)
+        const bool odd_col = BAND > 0 && j0 + kInCols - 1 > g.w - 2 && 2 * (g.w - 1) + 1 >= g.Wl;
+        const unsigned rlim = odd_col ? 0u : (unsigned)max(g.h - 2, 0);
+        const char *origin = reinterpret_cast<const char *>(base) + (((long)(2 * i0) * g.W + 2 * j0) << g.lvl) * 4;      // (outside the plane where i0 or j0 is -2: an address only with a piece's offsets)
+        // which of the wave's pieces are plain: lane k looks at piece k (its first halo row is 4 q4 + t = v + v / 3 for v = 3 q4 + t), one ballot per tile
+        const int uk = wave_u + lb * kWaves, vk = uk % kPP;
+        const bool mine = lb < kMyPieces && uk < kPieces;
+        const unsigned plain = (unsigned)__ballot(mine && (unsigned)(i0 + vk + vk / 3) < rlim);
+        unsigned rest = (unsigned)__ballot(mine) & ~plain;
+#pragma unroll
+        for (int k = 0; k < kMyPieces; ++k) {
+            if (plain >> k & 1) {
+                const int u = wave_u + k * kWaves;                                      // wave-uniform: the interior path's scalars
+                const int pl = u / kPP, v = u - kPP * pl, q4 = v / 3;
+                const int src = pl / 3, ci = pl - 3 * src;
+                const uint32_t uoff = (uint32_t)(ci * (int)g.plane + (((8 * q4 + src_oi(src)) * g.W + src_oj(src)) << g.lvl)) * 4;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(origin + uoff + lt[(k * kWaves) % 3]),
+                                                 (__attribute__((address_space(3))) void *)(dst + u * 64), 4, 0, 0);
+            }
+        }
+        while (rest) {
+            const int u = wave_u + __builtin_ctz(rest) * kWaves;
+            rest &= rest - 1;
             const int pl = u / kPP, v = u - kPP * pl, q4 = v / 3, t = v - 3 * q4;       // wave-uniform
             const int src = pl / 3, ci = pl - 3 * src;
             const int thr = 48 - 16 * t;
-            const bool up = lane >= thr;
-            const int cidx = min(up ? lane - thr : lane + 16 * t, kInCols - 1);
+            const bool up = lb >= thr;
+            const int cidx = min(up ? lb - thr : lb + 16 * t, kInCols - 1);
             const int r = 4 * q4 + t + (up ? 1 : 0);
-            const int bi = max(0, min(i0 + r, g.h - 1));            // the conv's replicate padding, in band coordinates
+            const int bi = max(0, min(i0 + r, g.h - 1));
             const int bj = max(0, min(j0 + cidx, g.w - 1));
             int rr = 2 * bi + src_oi(src), cc = 2 * bj + src_oj(src);
-            if (rr >= g.Hl) rr -= 2;                   // lazyDWT's replicate pad of the odd edge (LLICTI_nets.py:226-240)
+            if (rr >= g.Hl) rr -= 2;
             if (cc >= g.Wl) cc -= 2;
             const unsigned off = (unsigned)(rr * g.W + cc) << g.lvl;   // < H * W
             const float *gp = base + (long)ci * g.plane + off;

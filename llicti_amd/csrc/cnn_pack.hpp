@@ -59,6 +59,7 @@ constexpr int kParamStride = LLICTI_PARAM_STRIDE;
 #endif
 #ifndef CNN_STAGE_FAST
 #define CNN_STAGE_FAST 1       // interior tiles (no clamp can fire): per-lane source offsets of a wave's pieces precomputed once per kernel
+                               //   (0: every tile takes the border path -- the build tools/cnn_border_isa.py counts that path's instructions in)
 #endif
 #ifndef CNN_REM4X4
 #define CNN_REM4X4 1           // layer 0: channels 80..87 of a head on v_mfma_f32_4x4x1 (16 blocks = 2 x 4 channels x 8 x 4 pixels,
