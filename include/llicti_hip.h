@@ -243,6 +243,26 @@ int llicti_decode_images_v(llicti_ctx *ctx, const uint8_t *d_in, size_t in_strid
                            int B, const int *Hs, const int *Ws, int mode, void *d_workspace, size_t workspace_bytes,
                            uint8_t *d_rgb, const size_t *rgb_off, void *stream);
 
+/* REDUCED-RESOLUTION decode: image b at 1 / 2^reduce of its size -- Hr = ceil(Hs[b] / 2^reduce), Wr = ceil(Ws[b] / 2^reduce)
+ * (llicti_reduced_dims) -- EXACTLY the pixels full[:, ::2^reduce, ::2^reduce] of the full decode, which are the original image's (the codec is
+ * lossless).  It is a DECIMATION, not a low-pass: the lazy wavelet has no smoothing filter, so fine texture aliases.  The decoder works coarse to
+ * fine and a level never reads a finer one, so the call launches the stages of levels >= reduce only: 3 x (nlevels - reduce) band-CNN launches
+ * (level 0 alone holds 3/4 of the symbols and CNN positions), none at reduce = nlevels, where the output is the header's raw DC band.
+ * reduce = 0 is llicti_decode_images_vm / _v: same launches, bytes and status words.  0 <= reduce <= the model's levels (5 config A, 2 config B),
+ * LLICTI_EINVAL otherwise; one value per call.
+ *   Hs, Ws   the FULL sizes the headers describe; modes: one mode (n_modes = 1) or one per image (n_modes = B), as for llicti_decode_images_vm;
+ *            every container the full decoder reads (the reference format: equal sizes per call)
+ *   d_rgb    image b's uint8 [3][Hr][Wr] at d_rgb + rgb_off[b]; rgb_off = NULL: the reduced images tightly packed in call order
+ *   workspace  what llicti_workspace_bytes* gives for the full decode of the same batch (a reduced call uses the same layout)
+ * INTEGRITY: a rANS container's end-of-stream check belongs to the tail coder of the LAST stage (level 0, band x10: it must end in its start
+ * state), which a call with reduce >= 1 never launches.  Such a call reports what the kernels it did launch flag -- header, unpack, init and
+ * the decoded stages (llicti_check_status, llicti_image_status) -- and nothing else: damage confined to the skipped levels goes unnoticed.
+ * A valid container gives status 0 for every image. */
+int llicti_reduced_dims(int H, int W, int reduce, int *Hr, int *Wr);
+int llicti_decode_images_reduced(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                 int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                 void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream);
+
 /* Where llicti_encode_images / llicti_decode_images of B images of H x W in `mode` keep the YCoCg-R planes inside the caller's workspace
  * (byte offsets): int16 [B][3][H][W] (Y - 127, Co, Cg) and float32 [B][3][H][W] = planes / 255 -- the second is the `x_ycocg` the
  * reference's compress() returns beside the streams (LLICTI_nets.py:143-144, :159), so a caller that wants it reads it from the workspace

@@ -67,6 +67,8 @@ _SIGS = {
     "llicti_decode_images_vm": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "llicti_encode_images_v": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images_v": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "llicti_reduced_dims": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "llicti_decode_images_reduced": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_encode_images": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),

@@ -1,12 +1,14 @@
 """python -m llicti_amd.cli encode IN.(png|ppm|jpg) OUT.llic [--container ac|auto|rans<M>|wrans<M>|xrans<M>] [--checkpoint model_best.pth.tar]
                                 [--config llicti_B.json]
-   python -m llicti_amd.cli decode IN.llic OUT.(png|ppm) [--checkpoint model_best.pth.tar] [--config llicti_B.json]
+   python -m llicti_amd.cli decode IN.llic OUT.(png|ppm) [--reduce R] [--checkpoint model_best.pth.tar] [--config llicti_B.json]
    python -m llicti_amd.cli info   IN.llic
 
 File-level front end of the MI355X hot path (needs a GPU: there is no CPU fallback).  Without a checkpoint the
 seed-1337 default init is used, as the reference does when `model_best.pth.tar` is missing (agents/base.py:78-80).  --config names the
 reference's JSON file the model was trained with (configs/llicti_A.json -- the default -- or llicti_B.json): as the reference's README says,
-compress and decompress with the json file that was used to train the model."""
+compress and decompress with the json file that was used to train the model.  decode --reduce R writes the image at 1 / 2^R of its size
+(R = 0 .. the model's levels: 5 for config A, 2 for config B; `info` lists the sizes): exactly every 2^R-th pixel of every 2^R-th row, decoded
+from the coarse levels alone -- a decimation without smoothing, so fine texture aliases."""
 from __future__ import annotations
 
 import argparse
@@ -32,23 +34,37 @@ def _model(container, checkpoint, config_path=None):
     return model, torch
 
 
-def main(argv=None):
+def _reduce_arg(v):
+    r = int(v)
+    if not 0 <= r <= 5:
+        raise argparse.ArgumentTypeError("--reduce takes 0 .. 5 (0 .. 2 for a config-B model)")
+    return r
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog="llicti_amd.cli")
     sub = ap.add_subparsers(dest="cmd", required=True)
     e = sub.add_parser("encode"); e.add_argument("src"); e.add_argument("dst")
     e.add_argument("--container", default="ac"); e.add_argument("--checkpoint", default=None); e.add_argument("--config", default=None)
     d = sub.add_parser("decode"); d.add_argument("src"); d.add_argument("dst"); d.add_argument("--checkpoint", default=None)
     d.add_argument("--config", default=None)
+    d.add_argument("--reduce", type=_reduce_arg, default=0, metavar="R", help="decode at 1 / 2^R of the size (every 2^R-th pixel; no smoothing)")
     i = sub.add_parser("info"); i.add_argument("src")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     from . import fileio
     if a.cmd == "info":
-        from .codec import header_dims, mode_of_header, name_of_mode
+        from .codec import header_dims, levels_of_header, mode_of_header, name_of_mode, reduced_dims
         bl = fileio.read_llic(a.src)
         H, W = header_dims(bl[0][0] + bl[0][1] + bl[0][2])
         n = sum(len(s) for r in bl for s in r)
         mode = mode_of_header(bl)
         print(f"{a.src}: {W}x{H} RGB, container {name_of_mode(mode)}, {n} bytes, {8.0 * n / (H * W):.4f} bpp")
+        sizes = (reduced_dims(H, W, r) for r in range(levels_of_header(bl[0][0][0]) + 1))
+        print("decodable sizes (decode --reduce R): " + ", ".join(f"r={r} {w}x{h}" for r, (h, w) in enumerate(sizes)))
         return 0
     if a.cmd == "encode":
         rgb = fileio.read_image(a.src)
@@ -65,11 +81,12 @@ def main(argv=None):
     bl = fileio.read_llic(a.src)
     model, torch = _model("ac", a.checkpoint, a.config)
     t0 = time.time()
-    x = model.decompres(bl, torch.device("cuda:0"))
+    x = model.decompres(bl, torch.device("cuda:0"), reduce=a.reduce)
     torch.cuda.synchronize()
     dt = time.time() - t0
     fileio.write_image(a.dst, (x[0] * 255).round().to(torch.uint8).cpu().numpy())
-    print(f"{a.src} -> {a.dst}: {x.shape[3]}x{x.shape[2]}, {dt:.3f} s")
+    note = f" (reduce {a.reduce})" if a.reduce else ""
+    print(f"{a.src} -> {a.dst}: {x.shape[3]}x{x.shape[2]}{note}, {dt:.3f} s")
     return 0
 
 

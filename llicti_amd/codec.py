@@ -218,6 +218,15 @@ def name_of_mode(mode: int) -> str:
     return "ac" if mode == MODE_AC else ("rans%d", "wrans%d", "xrans%d")[_mode_wide(mode)] % (mode & 0xFF)
 
 
+def reduced_dims(H, W, reduce):
+    """Size of an H x W image decoded at `reduce` (HipCodec.decode(..., reduce=r)): (ceil(H / 2^r), ceil(W / 2^r)) -- the shape of
+    img[::2**r, ::2**r].  The decode is a DECIMATION of the lossless image (the lazy wavelet has no smoothing filter: fine texture aliases)."""
+    H, W, r = int(H), int(W), int(reduce)
+    if H < 1 or W < 1 or not 0 <= r <= 5:
+        raise ValueError(f"reduced_dims: H={H} W={W} reduce={r} (need H, W >= 1 and 0 <= reduce <= 5)")
+    return (H + (1 << r) - 1) >> r, (W + (1 << r) - 1) >> r
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -451,9 +460,13 @@ class HipCodec:
                                                _ptr(seg_len), _stream_ptr(self.device)))
         return out, seg_len
 
-    def decode(self, containers, seg_len, H, W, mode=MODE_AC, out=None):
-        """device containers -> uint8 [B,3,H,W], async."""
+    def decode(self, containers, seg_len, H, W, mode=MODE_AC, out=None, reduce=0):
+        """device containers -> uint8 [B,3,H,W], async.  reduce = r (0 .. the model's levels): uint8 [B,3,Hr,Wr] of reduced_dims(H, W, r) --
+        exactly full[..., ::2**r, ::2**r], from the levels >= r alone (decode_reduced)."""
         B = containers.shape[0]
+        if reduce:
+            flat = self.decode_reduced(containers, seg_len, [H] * B, [W] * B, mode, reduce, out=None if out is None else out.view(-1))
+            return out if out is not None else flat.view(B, 3, *reduced_dims(H, W, reduce))
         ws = self.workspace(B, H, W, mode)
         if out is None:
             out = torch.empty((B, 3, H, W), dtype=torch.uint8, device=self.device)
@@ -492,8 +505,39 @@ class HipCodec:
                                                       _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
         return out, seg_len
 
-    def decode_v(self, containers, seg_len, Hs, Ws, mode, out=None):
-        """device containers of B images of sizes Hs[b] x Ws[b] -> flat uint8 device tensor (the images back to back), async."""
+    def decode_reduced(self, containers, seg_len, Hs, Ws, mode, reduce, out=None, rgb_off=None):
+        """llicti_decode_images_reduced: device containers of B images of FULL sizes Hs[b] x Ws[b] (mode: one, or one per image) -> flat uint8
+        device tensor holding image b's [3][Hr][Wr] block (reduced_dims) at byte rgb_off[b], or back to back (rgb_off None), async.  Only the
+        stages of levels >= reduce are launched; a rANS container's end-of-stream check (the last stage's tail coder) is therefore not run for
+        reduce >= 1: check() / image_status() report what the launched kernels flag.  reduce = 0 is decode_v."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.shape[0] == B
+        ws = self.workspace_v(Hs, Ws, mode)          # (the full decode's: a reduced call uses the same layout)
+        r = int(reduce)
+        dims = [reduced_dims(h, w, r) if 0 <= r <= 5 else (int(h), int(w)) for h, w in zip(Hs, Ws)]      # (a bad r: the library says so)
+        sizes = [3 * h * w for h, w in dims]
+        if rgb_off is None:
+            offs, total = None, sum(sizes)
+        else:
+            offs = np.ascontiguousarray(rgb_off, dtype=np.uint64)
+            assert offs.shape == (B,)
+            total = max(int(o) + n for o, n in zip(offs, sizes))
+        if out is None:
+            out = torch.empty((total,), dtype=torch.uint8, device=self.device)
+        assert out.numel() >= total
+        one, per = self._modes_arg(mode, B)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        _lib.check(self.L.llicti_decode_images_reduced(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                                                       _ptr(modes), len(modes), r, _ptr(ws), ws.numel(), _ptr(out), _ptr(offs),
+                                                       _stream_ptr(self.device)))
+        return out
+
+    def decode_v(self, containers, seg_len, Hs, Ws, mode, out=None, reduce=0):
+        """device containers of B images of sizes Hs[b] x Ws[b] -> flat uint8 device tensor (the images back to back), async.
+        reduce = r: the images at reduced_dims(Hs[b], Ws[b], r), back to back (decode_reduced)."""
+        if reduce:
+            return self.decode_reduced(containers, seg_len, Hs, Ws, mode, reduce, out=out)
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
         assert containers.shape[0] == B

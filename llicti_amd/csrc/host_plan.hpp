@@ -45,6 +45,10 @@ struct Plan {
     TileRun run[LLICTI_NLEVELS * 3];
     // device copies (one block, see PlanBlock)
     size_t d_img = 0, d_geo = 0, d_sg = 0, d_desc = 0, d_slot_off = 0, d_slot_cap = 0, d_rslot_off = 0, d_tiles = 0, d_sref = 0, d_total = 0;
+    // reduced-resolution decodes (plan_add_reduced): the levels the call skips and where every image's reduced output goes
+    int reduce = 0;
+    std::vector<RedGeo> red;            // [B], empty for reduce = 0
+    size_t d_red = 0;
 };
 
 // AC decode has two table forms.  Few images in flight (latency bound: every stream is one serial wave and the GPU is
@@ -349,6 +353,40 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     p.d_tiles = dtake(p.tiles.size() * sizeof(TileRef));
     p.d_sref = dtake(p.sref.size() * sizeof(StreamRef));
     p.d_total = d;
+}
+
+// The extra words a reduced-resolution decode adds to the cache key of its batch's plan: a marker that no full-size key holds at that place
+// (-reduce: sizes are >= 32), then the byte offset of every image's reduced output (out_off, or nullptr = tightly packed in call order).
+// A full-size key has 3 + 4 B words, a reduced one 4 + 5 B: the two never compare equal, so a reduced call never finds, changes or
+// replaces the full-size plan of the same batch.
+static void reduced_key_tail(std::vector<long> &key, int B, const int *Hs, const int *Ws, int reduce, const size_t *out_off)
+{
+    key.push_back(-(long)reduce);
+    long pos = 0;
+    for (int b = 0; b < B; ++b) {
+        key.push_back(out_off ? (long)out_off[b] : pos);
+        pos += 3L * reduced_dim(Hs[b], reduce) * reduced_dim(Ws[b], reduce);
+    }
+}
+// Turns the plan build_plan made for a batch -- with FULL-size tight RGB placement: `uniform`, `vec_ok`, ImgGeo::rgb_off and rgb_bytes keep
+// their full-size meaning and nothing of the decode's stages changes -- into the plan of a decode that stops after level `reduce`
+// (1 .. nlev): the output table of unlift_reduced_kernel goes behind the other tables of the device block, the key gets its tail.
+static void plan_add_reduced(Plan &p, int reduce, const size_t *out_off)
+{
+    p.reduce = reduce;
+    p.red.assign(p.B, RedGeo{});
+    std::vector<int> Hs(p.B), Ws(p.B);
+    long pos = 0;
+    for (int b = 0; b < p.B; ++b) {
+        RedGeo &rg = p.red[b];
+        Hs[b] = p.img[b].H; Ws[b] = p.img[b].W;
+        rg.Hr = reduced_dim(Hs[b], reduce); rg.Wr = reduced_dim(Ws[b], reduce);
+        rg.off = out_off ? (long)out_off[b] : pos;
+        pos += 3L * rg.Hr * rg.Wr;
+    }
+    reduced_key_tail(p.key, p.B, Hs.data(), Ws.data(), reduce, out_off);
+    p.d_red = p.d_total;
+    p.d_total = align_up(p.d_total + p.red.size() * sizeof(RedGeo), 256);
 }
 
 // mode: 0 = AC container (torchac-compatible, the reference's format); 0x100 | M = rANS container (v3) with M

@@ -58,6 +58,13 @@ struct ImgGeo {
     long pix_off;                             // first element of the image's [3][H][W] block in planes / fplanes (workspace)
     long rgb_off;                             // first byte of its [3][H][W] block in the caller's RGB buffer
 };
+// One image's OUTPUT of a reduced-resolution decode (llicti_decode_images_reduced; device table of the call's plan, behind the tables above):
+// the pixels whose row and column are multiples of 2^r, planar uint8 [3][Hr][Wr] at byte `off` of the caller's buffer.
+struct RedGeo {
+    long off;
+    int Hr, Wr;                               // ceil(H / 2^r), ceil(W / 2^r)
+};
+LLICTI_HD int reduced_dim(int n, int r) { return (n + (1 << r) - 1) >> r; }
 static Geom make_geom(int B, int H, int W, int lvl)
 {
     Geom g;

@@ -120,3 +120,32 @@ __global__ __launch_bounds__(256) void unlift_kernel(const int16_t *__restrict__
         dst[p] = (uint8_t)R; dst[plane + p] = (uint8_t)G; dst[2 * plane + p] = (uint8_t)Bl;
     }
 }
+
+// The last kernel of a reduced-resolution decode (llicti_decode_images_reduced, r >= 1): output pixel (i, j) of image b is the plane pixel
+// (i << r, j << r) -- final once level r has been decoded; the finer levels' pixels are never written and never read here -- through the same
+// inverse YCoCg-R, written as compact planar uint8 [3][Hr][Wr] at rv[b].off.  One thread per output pixel; image b's sizes and offsets are
+// scalar loads from the call's tables.  Latches the call's status words like unlift_kernel.
+__global__ __launch_bounds__(256) void unlift_reduced_kernel(const int16_t *__restrict__ planes, uint8_t *__restrict__ rgb, int r,
+                                                             const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                             int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
+                                                             const RedGeo *__restrict__ rv)
+{
+    const int b = blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (b == 0 && status[0] != 0) *latched = status[0];
+        if (img_latched) img_latched[b] = status[status_head + b];
+    }
+    const int W = iv[b].W, Hr = rv[b].Hr, Wr = rv[b].Wr;
+    const long plane = iv[b].plane, rplane = (long)Hr * Wr;
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= rplane) return;
+    const int i = (int)((uint32_t)p / (uint32_t)Wr), j = (int)((uint32_t)p - (uint32_t)i * (uint32_t)Wr);      // (rplane <= 4080^2 < 2^32)
+    const int16_t *src = planes + iv[b].pix_off + ((long)(i << r) * W + (j << r));
+    uint8_t *dst = rgb + rv[b].off + p;
+    const int Y = src[0] + 127, Co = src[plane], Cg = src[2 * plane];
+    const int t = Y - (Cg >> 1);
+    const int G = Cg + t;
+    const int Bl = t - (Co >> 1);
+    const int R = Bl + Co;
+    dst[0] = (uint8_t)R; dst[rplane] = (uint8_t)G; dst[2 * rplane] = (uint8_t)Bl;
+}

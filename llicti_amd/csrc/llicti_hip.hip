@@ -674,8 +674,12 @@ static int acquire_block(llicti_ctx *c, size_t need, PlanBlock *out)
 
 // The plan of a batch: cached by (mode, sizes, placement).  A miss builds the tables on the host, copies them into a pinned block and
 // enqueues ONE asynchronous upload on the call's stream -- no device synchronisation, no allocation once the pool is warm.
-static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, const int *Ms, hipStream_t s, PlanDev **out)
+// reduce >= 1 (llicti_decode_images_reduced): rgb_off places the REDUCED outputs; the plan itself is the batch's full-size one with tight
+// placement (the unused default of its full-size fields) plus the reduced output table, under a key of its own (host_plan.hpp: plan_add_reduced).
+static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, const int *Ms, hipStream_t s, PlanDev **out, int reduce = 0)
 {
+    const size_t *red_off = reduce > 0 ? rgb_off : nullptr;
+    if (reduce > 0) rgb_off = nullptr;
     std::vector<long> key;
     key.reserve(3 + 4 * (size_t)B);
     key.push_back(ME); key.push_back(B); key.push_back(c->cnn_tile_rows * 2 + (c->force_ragged ? 1 : 0));
@@ -686,6 +690,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
             pos += 3L * Hs[b] * Ws[b];
         }
     }
+    if (reduce > 0) reduced_key_tail(key, B, Hs, Ws, reduce, red_off);
     auto it = c->plans.find(key);
     if (it != c->plans.end()) {
         PlanDev *pd = it->second;
@@ -700,6 +705,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     Plan &p = pd->p;
     ++c->n_plan_build;
     build_plan(p, B, Hs, Ws, rgb_off, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms, c->nlev);
+    if (reduce > 0) plan_add_reduced(p, reduce, red_off);
     if (p.key != key) return fail(LLICTI_EINVAL, "plan: key mismatch");
     if (p.rslot_off.size() != (size_t)p.nstreams || p.sref.size() != (size_t)p.nstreams)
         return fail(LLICTI_EINVAL, "plan: stream tables have %zu / %zu entries, expected %d", p.rslot_off.size(), p.sref.size(), p.nstreams);
@@ -715,6 +721,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     put(p.d_rslot_off, p.rslot_off.data(), p.rslot_off.size() * sizeof(long));
     put(p.d_tiles, p.tiles.data(), p.tiles.size() * sizeof(TileRef));
     put(p.d_sref, p.sref.data(), p.sref.size() * sizeof(StreamRef));
+    put(p.d_red, p.red.data(), p.red.size() * sizeof(RedGeo));
     bool ok = hipMemcpyAsync(pd->blk.dev, h, p.d_total, hipMemcpyHostToDevice, s) == hipSuccess;
     ok = ok && hipEventRecord(pd->blk.uploaded, s) == hipSuccess;
     ok = ok && hipEventRecord(pd->blk.done, s) == hipSuccess;      // (so that the block is never recycled in front of its own upload)
@@ -979,7 +986,7 @@ extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, 
 }
 
 static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
-                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s)
+                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce)
 {
     const Plan &p = pd->p;
     const int B = p.B, M = p.M, Q = p.Q;
@@ -1020,7 +1027,10 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
         }
     }
     // 45 dependent stages (LLICTI_nets.py:440-498; 9 L for a model of L levels): CNN of band b needs bands < b of this level, Co needs Y, Cg needs Y, Co
-    for (int lvl = p.nlev - 1; lvl >= 0; --lvl) {
+    // A reduced decode (reduce = r >= 1) stops after level r: every pixel whose row and column are multiples of 2^r is final then, and nothing that
+    // ran reads a finer one.  The whole container has been unpacked above; the rANS bit region is read downwards from the stream's end and the coarse
+    // stages come first, so stopping is sound -- but the tail coder (the last stage's) never runs, and with it the end-of-stream check.
+    for (int lvl = p.nlev - 1; lvl >= reduce; --lvl) {
         const Geom &g = p.geo[(size_t)lvl * B];                         // image 0's (equal sizes: every image's)
         const Geom *gv = p.uniform ? nullptr : d_geo + (size_t)lvl * B;
         for (int band = 0; band < 3; ++band) {
@@ -1093,6 +1103,16 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
             }
         }
     }
+    if (reduce > 0) {
+        // (every side stream of the reference-format pipeline was joined back onto `s` at the end of its band: nothing is pending here)
+        long max_rplane = 0;
+        for (const RedGeo &rg : p.red) max_rplane = std::max(max_rplane, (long)rg.Hr * rg.Wr);
+        ProfSpan span(c, PROF_MISC, s);
+        unlift_reduced_kernel<<<dim3((unsigned)((max_rplane + 255) / 256), B), 256, 0, s>>>(planes, d_rgb, reduce, status, kStatusHead, c->d_status, c->d_img_status,
+                                                                                            d_img, pd->dev<RedGeo>(p.d_red));
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     const int gx = (int)std::min<long>((p.max_plane + 255) / 256, 1024);
     {
         ProfSpan span(c, PROF_MISC, s);
@@ -1105,9 +1125,10 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
 }
 
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
-                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream)
+                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0)
 {
     if (!c || !d_in || !d_seg_len || !d_workspace || !d_rgb) return fail(LLICTI_EINVAL, "decode_images: null pointer");
+    if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
     if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
     int ME = 0;
     std::vector<int> Ms;
@@ -1118,7 +1139,7 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
     PlanDev *pd = nullptr;
-    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd)) return rc;
+    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd, reduce)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     if (!p.uniform && p.M == 0) return fail(LLICTI_EINVAL, "decode_images: a batch of mixed sizes needs a rANS container (the reference-format container codes equal sizes per call)");
@@ -1139,7 +1160,7 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
         c->img_status_cap = cap;
     }
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s)) return rc;
+    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce)) return rc;
     c->img_status_n = B;
     return LLICTI_OK;
 }
@@ -1156,6 +1177,21 @@ extern "C" int llicti_decode_images_vm(llicti_ctx *c, const uint8_t *d_in, size_
                                        uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
     return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_rgb, rgb_off, stream);
+}
+
+extern "C" int llicti_reduced_dims(int H, int W, int reduce, int *Hr, int *Wr)
+{
+    if (H < 1 || W < 1 || reduce < 0 || reduce > LLICTI_NLEVELS) return fail(LLICTI_EINVAL, "reduced_dims: H=%d W=%d reduce=%d (need H, W >= 1 and 0 <= reduce <= %d)", H, W, reduce, LLICTI_NLEVELS);
+    if (Hr) *Hr = reduced_dim(H, reduce);
+    if (Wr) *Wr = reduced_dim(W, reduce);
+    return LLICTI_OK;
+}
+
+extern "C" int llicti_decode_images_reduced(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                            int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                            void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream)
+{
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, d_rgb, rgb_off, stream, reduce);
 }
 
 extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ...codec import (MODE_AC, MODE_RANS, NSEG, HipCodec, auto_modes, bytestream_list_to_container, container_to_bytestream_list, header_dims, mode_of_header, mode_of_name)
+from ...codec import (MODE_AC, MODE_RANS, NSEG, HipCodec, auto_modes, bytestream_list_to_container, container_to_bytestream_list, header_dims, mode_of_header, mode_of_name, reduced_dims)
 from ...config import check_supported, model_shape
 
 
@@ -283,24 +283,36 @@ class LLICTI(nn.Module):
         return self._xfer[key]
 
     @torch.no_grad()
-    def decompres(self, bytestream_list, devc=None, xorg=None):
+    def decompres(self, bytestream_list, devc=None, xorg=None, reduce=0):
         """bytestream_list -> float32 [1,3,H,W] (LLICTI_nets.py:161-179).  xorg: the reference's diagnostic (:167-171) -- the float planes
-        compress() returned; the decoded planes are compared with them on the device and a difference of a grey level or more is reported."""
-        rgb = self.decode_batch_async([bytestream_list], devc)
+        compress() returned; the decoded planes are compared with them on the device and a difference of a grey level or more is reported.
+        reduce = r (0 .. the model's levels; not in the reference): float32 [1,3,ceil(H/2^r),ceil(W/2^r)] = the full result's [..., ::2^r, ::2^r],
+        decoded from the levels >= r alone (3 (levels - r) of the band-CNN launches).  A decimation, not a low-pass: fine texture aliases.  For
+        r >= 1 a rANS container's end-of-stream check is not run (it belongs to the last stage); xorg is compared at [..., ::2^r, ::2^r]."""
+        rgb = self.decode_batch_async([bytestream_list], devc, reduce=reduce)
         codec = self.codec()
         codec.check()
         if xorg is not None:
-            planes = codec.lift(rgb)[1]                            # (YCoCg - [127,0,0]) / 255 of the decoded image, as compress() returns it
+            if reduce:
+                # (a reduced image may be smaller than the 32 pixels the lift kernel takes: this diagnostic's few integer ops run in torch)
+                R, G, Bl = (rgb[:, k].to(torch.int32) for k in range(3))
+                Co = R - Bl
+                t = Bl + (Co >> 1)
+                Cg = G - t
+                planes = torch.stack((t + (Cg >> 1) - 127, Co, Cg), dim=1).to(torch.float32) / 255
+                xorg = xorg[..., ::1 << reduce, ::1 << reduce]
+            else:
+                planes = codec.lift(rgb)[1]                        # (YCoCg - [127,0,0]) / 255 of the decoded image, as compress() returns it
             maxx_abserr = float((xorg.to(planes.device) - planes).abs().max()) * 255
             if maxx_abserr >= 1.0:                                 # LLICTI_nets.py:169-171
                 print("Error: Decoded YCoCg img does NOT match original YCoCg image perfectly! The maximum of absolute error is {:.4f}".format(maxx_abserr))
         return rgb.to(torch.float32) / 255           # LLICTI_nets.py:87
 
     @torch.no_grad()
-    def decompres_batch(self, lists, devc=None):
+    def decompres_batch(self, lists, devc=None, reduce=0):
         """bytestream_lists of B images -> float32 [B,3,H,W] (equal sizes), or -- images of different sizes, rANS containers -- a LIST of B tensors
-        [1,3,H_b,W_b], each what decompres() returns for that image."""
-        res = self.decode_batch_async(lists, devc)
+        [1,3,H_b,W_b], each what decompres() returns for that image.  reduce: as for decompres(), one value for the call."""
+        res = self.decode_batch_async(lists, devc, reduce=reduce)
         self.codec().check()
         if isinstance(res, tuple):
             flat, Hs, Ws = res
@@ -309,10 +321,12 @@ class LLICTI(nn.Module):
         return res.to(torch.float32) / 255           # LLICTI_nets.py:87
 
     @torch.no_grad()
-    def decode_batch_async(self, lists, devc=None, slot=0, flat=False):
+    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0):
         """bytestream_lists of B images -> uint8 [B,3,H,W] on the device, enqueued (upload from a pinned buffer + decode); device-side
         failures are reported by codec().check() / image_status().  The images of a call share a container kind; in a rANS container their
-        SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each."""
+        SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each.
+        reduce = r: every image at 1 / 2^r (decompres()); H, W, Hs, Ws of the result are the REDUCED sizes.  (The pinned staging buffers hold the
+        call's INPUT -- containers and segment lengths, sized by the full image -- so a reduced and a full decode share them safely.)"""
         codec = self.codec(devc if (devc is not None and torch.device(devc).type == "cuda") else None)
         Hs, Ws, modes = [], [], []
         for bl in lists:
@@ -360,8 +374,11 @@ class LLICTI(nn.Module):
         cont_d.record_stream(cur)
         seg_d.record_stream(cur)
         if mixed or flat:
-            return codec.decode_v(cont_d, seg_d, Hs, Ws, mode), Hs, Ws
-        return codec.decode(cont_d, seg_d, Hs[0], Ws[0], mode=mode)
+            out = codec.decode_v(cont_d, seg_d, Hs, Ws, mode, reduce=reduce)
+            if reduce:
+                Hs, Ws = (list(v) for v in zip(*(reduced_dims(h, w, reduce) for h, w in zip(Hs, Ws))))
+            return out, Hs, Ws
+        return codec.decode(cont_d, seg_d, Hs[0], Ws[0], mode=mode, reduce=reduce)
 
 
 class EncodedBatch:
