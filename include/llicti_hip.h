@@ -263,6 +263,40 @@ int llicti_decode_images_reduced(llicti_ctx *ctx, const uint8_t *d_in, size_t in
                                  int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
                                  void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream);
 
+/* INTERLEAVED, PITCHED 8-bit pixels: the layout image sources deliver (decoded PNG / JPEG, video frames, screen captures, OpenCV and PIL arrays).
+ * The calls above take planar uint8 [3][H][W]; these two read and write the caller's interleaved buffer directly -- the lift is the first kernel
+ * of an encode, the unlift the last of a decode, so no separate conversion pass runs.  A container's bytes are a function of the pixel VALUES
+ * alone: the same image gives the same container through either layout.
+ *   format    LLICTI_PIX_*: three colour bytes per pixel in the named order, the 4-byte formats with a fourth byte behind them.  ALPHA IS NOT
+ *             CODED: the encoder ignores the fourth byte, the decoder writes 255 there.
+ *   px_off    host array of B byte offsets into d_pix: the first byte of the first pixel of image b's window.  Pixel (i, j) of the window is
+ *             at px_off[b] + i * pitch[b] + j * bpp, so a window may be a crop of a larger frame (offset of its corner, the frame's pitch).
+ *             NULL = the windows back to back in call order, each of llicti_pixel_span bytes
+ *   pitch     host array of B row pitches in bytes, >= W * bpp (LLICTI_EINVAL otherwise; at most 2^31 - 1).  NULL = tight rows, W * bpp
+ * No alignment is required.  Windows whose first byte (d_pix + px_off[b]) and pitch are multiples of 4 are read and written in dwords, the
+ * others byte by byte; the choice is per image, so one call may mix them.  The decoder writes the W * bpp bytes of each of the window's rows and
+ * nothing else: pitch padding and whatever surrounds a crop keep their bytes.  Windows of one decode must not overlap.
+ * An unknown format, a short pitch or a null array the call needs is LLICTI_EINVAL before anything is launched. */
+#define LLICTI_PIX_RGB8 0
+#define LLICTI_PIX_BGR8 1
+#define LLICTI_PIX_RGBA8 2
+#define LLICTI_PIX_BGRA8 3
+/* Host helpers (no device needed): bytes per pixel of a format (0: unknown format), and the bytes from the first pixel of an H x W window
+ * to the end of its last one, (H - 1) * pitch + W * bpp (pitch = 0: tight rows; 0: unknown format, H or W < 1, or pitch < W * bpp). */
+int llicti_pixel_bytes(int format);
+size_t llicti_pixel_span(int format, int H, int W, size_t pitch);
+/* llicti_encode_images_vm on interleaved pixels: modes holds B modes; every container and rule of that call (the reference format codes equal
+ * sizes per call).  Image b's container and segment lengths are those of the planar call on the same pixel values. */
+int llicti_encode_images_px(llicti_ctx *ctx, const uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch,
+                            int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
+                            uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream);
+/* llicti_decode_images_reduced into interleaved pixels (reduce = 0: the full decode): Hs, Ws are the FULL sizes the headers describe; with
+ * reduce >= 1 image b's window has the reduced size (llicti_reduced_dims).  Same launches, status words and integrity rule as that call. */
+int llicti_decode_images_px(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                            int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                            void *d_workspace, size_t workspace_bytes,
+                            uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream);
+
 /* Where llicti_encode_images / llicti_decode_images of B images of H x W in `mode` keep the YCoCg-R planes inside the caller's workspace
  * (byte offsets): int16 [B][3][H][W] (Y - 127, Co, Cg) and float32 [B][3][H][W] = planes / 255 -- the second is the `x_ycocg` the
  * reference's compress() returns beside the streams (LLICTI_nets.py:143-144, :159), so a caller that wants it reads it from the workspace

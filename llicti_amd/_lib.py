@@ -69,6 +69,10 @@ _SIGS = {
     "llicti_decode_images_v": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
     "llicti_reduced_dims": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "llicti_decode_images_reduced": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "llicti_pixel_bytes": (_i, [_i]),
+    "llicti_pixel_span": (_sz, [_i, _i, _i, _sz]),
+    "llicti_encode_images_px": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "llicti_decode_images_px": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_encode_images": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),

@@ -21,11 +21,18 @@ from ..loggers.rate import RateLogger
 from ..weights import load_reference_state_dict
 
 
-def _iter_test_images_u8(config, rank=0, world=1, with_index=False):
+def _files_are_source(config):
+    """test_data names a directory of image files (not "synthetic:..." and not an in-memory data set)"""
+    return isinstance(config.test_data, str) and not config.test_data.startswith("synthetic:")
+
+
+def _iter_test_images_u8(config, rank=0, world=1, with_index=False, layout="chw"):
     """The test images as uint8 [3,H,W] host arrays (the batched eval path uploads uint8: a quarter of the float32 bytes).  With several
     ranks (SURVEY section 8e): image i of the data set belongs to rank i mod world -- a rank reads and yields only its own, in order;
-    with_index: (index in the whole data set, image) pairs."""
+    with_index: (index in the whole data set, image) pairs.  layout="hwc" (a directory of files only, _files_are_source): uint8 [H,W,3], the
+    files' own interleaved rows -- the batched eval path codes them in that layout, so no image is transposed on the host."""
     src = config.test_data
+    assert layout == "chw" or _files_are_source(config)
 
     def out(i, rgb):
         return (i, rgb) if with_index else rgb
@@ -46,7 +53,7 @@ def _iter_test_images_u8(config, rank=0, world=1, with_index=False):
     from ..fileio import read_image
     files = sorted(f for f in os.listdir(src) if f.lower().endswith((".png", ".jpg", ".ppm")))
     for i in range(rank, len(files), world):
-        yield out(i, read_image(os.path.join(src, files[i])))
+        yield out(i, read_image(os.path.join(src, files[i]), layout=layout))
 
 
 def _iter_test_images(config, device, rank=0, world=1, with_index=False):
@@ -229,11 +236,14 @@ class LLICTIAgent:
         keep = bool(self.config["keep_streams"]) if "keep_streams" in self.config else False
         stream = torch.cuda.current_stream(self.device)
         one_size = self.model.mode is not None and self.model.mode == 0          # reference format: equal sizes per call
+        # image files are coded from and decoded to their own interleaved rows (encode_batch_async / decode_batch_async, pixels="rgb"): the same
+        # containers and the same byte-for-byte lossless check, on buffers of the same size, without a transpose per image on the host
+        px = {"pixels": "rgb"} if _files_are_source(self.config) else {}
 
         def batches():
             """(indices in the whole data set, images): this rank's images (all of them when it is alone), eval_batch at a time"""
             cur, ids = [], []
-            for i, rgb in _iter_test_images_u8(self.config, self.rank, self.world, with_index=True):
+            for i, rgb in _iter_test_images_u8(self.config, self.rank, self.world, with_index=True, layout="hwc" if px else "chw"):
                 if cur and (len(cur) == eval_batch or (one_size and rgb.shape != cur[0].shape)):
                     yield ids, cur
                     cur, ids = [], []
@@ -245,7 +255,7 @@ class LLICTIAgent:
         def start_encode(imgs, slot):
             B = len(imgs)
             e1 = torch.cuda.Event(enable_timing=True)
-            enc = self.model.encode_batch_async(imgs, slot=slot)        # list of uint8 host arrays: staged in pinned memory, uploaded on the model's copy stream
+            enc = self.model.encode_batch_async(imgs, slot=slot, **px)        # list of uint8 host arrays: staged in pinned memory, uploaded on the model's copy stream
             e1.record(stream)
             return {"enc": enc, "e_enc": (enc.t0, e1), "B": B, "Hs": enc.Hs, "Ws": enc.Ws}      # (t0: recorded by the list path behind the wait for its upload)
 
@@ -256,7 +266,7 @@ class LLICTIAgent:
             rates = [self.compr_loss.forward(3 * h * w, bl) for bl, h, w in zip(lists, job["Hs"], job["Ws"])]
             d0, d1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             d0.record(stream)
-            rec, _, _ = self.model.decode_batch_async(lists, self.device, slot=job["slot"], flat=True)
+            rec, _, _ = self.model.decode_batch_async(lists, self.device, slot=job["slot"], flat=True, **px)
             n = rec.numel()
             # the lossless check (llicti_agent.py:151-162) on the device, the images back to back: ONE comparison pass says per image whether any sub-pixel
             # differs -- the answer is "no" for every image of every run that is not broken, so the error's SIZE (the reference prints it) is only

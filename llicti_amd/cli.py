@@ -15,8 +15,6 @@ import argparse
 import sys
 import time
 
-import numpy as np
-
 
 def _model(container, checkpoint, config_path=None):
     import torch
@@ -67,26 +65,26 @@ def main(argv=None):
         print("decodable sizes (decode --reduce R): " + ", ".join(f"r={r} {w}x{h}" for r, (h, w) in enumerate(sizes)))
         return 0
     if a.cmd == "encode":
-        rgb = fileio.read_image(a.src)
+        hwc = fileio.read_image(a.src, layout="hwc")         # the file's interleaved rows: uploaded and lifted as they are (no transpose, no float copy)
         model, torch = _model(a.container, a.checkpoint, a.config)
-        x = torch.from_numpy(rgb.astype(np.float32) / np.float32(255)).unsqueeze(0).to("cuda:0")
         t0 = time.time()
-        bl, _ = model.compress(x)
+        bl = model.encode_batch_async([hwc], pixels="rgb").lists()[0]
         torch.cuda.synchronize()
         dt = time.time() - t0
         fileio.write_llic(a.dst, bl)
         n = sum(len(s) for r in bl for s in r)
-        print(f"{a.src} -> {a.dst}: {rgb.shape[2]}x{rgb.shape[1]}, {n} bytes, {8.0 * n / (rgb.shape[1] * rgb.shape[2]):.4f} bpp, {dt:.3f} s")
+        print(f"{a.src} -> {a.dst}: {hwc.shape[1]}x{hwc.shape[0]}, {n} bytes, {8.0 * n / (hwc.shape[0] * hwc.shape[1]):.4f} bpp, {dt:.3f} s")
         return 0
     bl = fileio.read_llic(a.src)
     model, torch = _model("ac", a.checkpoint, a.config)
     t0 = time.time()
-    x = model.decompres(bl, torch.device("cuda:0"), reduce=a.reduce)
+    hwc = model.decode_batch_async([bl], torch.device("cuda:0"), reduce=a.reduce, pixels="rgb")[0]      # uint8 [H, W, 3], written so by the decoder
+    model.codec().check()
     torch.cuda.synchronize()
     dt = time.time() - t0
-    fileio.write_image(a.dst, (x[0] * 255).round().to(torch.uint8).cpu().numpy())
+    fileio.write_image(a.dst, hwc.cpu().numpy(), layout="hwc")
     note = f" (reduce {a.reduce})" if a.reduce else ""
-    print(f"{a.src} -> {a.dst}: {x.shape[3]}x{x.shape[2]}{note}, {dt:.3f} s")
+    print(f"{a.src} -> {a.dst}: {hwc.shape[1]}x{hwc.shape[0]}{note}, {dt:.3f} s")
     return 0
 
 

@@ -227,6 +227,37 @@ def reduced_dims(H, W, reduce):
     return (H + (1 << r) - 1) >> r, (W + (1 << r) - 1) >> r
 
 
+# Interleaved pixel formats of encode_px / decode_px (LLICTI_PIX_*): three colour bytes in the named order; the 4-byte formats carry a fourth byte
+# that the encoder ignores and the decoder writes as 255 (alpha is not coded).
+PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8 = 0, 1, 2, 3
+PIX_FORMATS = {"rgb": PIX_RGB8, "bgr": PIX_BGR8, "rgba": PIX_RGBA8, "bgra": PIX_BGRA8}
+
+
+def pixel_format(fmt) -> int:
+    """"rgb" | "bgr" | "rgba" | "bgra" (or a PIX_* constant) -> the PIX_* constant."""
+    if isinstance(fmt, str):
+        if fmt.lower() not in PIX_FORMATS:
+            raise ValueError(f"unknown pixel format {fmt!r} (one of {', '.join(PIX_FORMATS)})")
+        return PIX_FORMATS[fmt.lower()]
+    return int(fmt)
+
+
+def pixel_bytes(fmt) -> int:
+    """Bytes per pixel of a format (llicti_pixel_bytes; works without a device)."""
+    n = int(_lib.lib().llicti_pixel_bytes(pixel_format(fmt)))
+    if n == 0:
+        raise ValueError(f"unknown pixel format {fmt!r}")
+    return n
+
+
+def pixel_span(fmt, H, W, pitch=0) -> int:
+    """Bytes from the first pixel of an H x W window to the end of its last one, (H - 1) * pitch + W * bpp (llicti_pixel_span; pitch 0: tight rows)."""
+    n = int(_lib.lib().llicti_pixel_span(pixel_format(fmt), int(H), int(W), int(pitch)))
+    if n == 0:
+        raise ValueError(f"pixel_span: format {fmt!r}, H={H}, W={W}, pitch={pitch} (need a known format, H, W >= 1 and pitch >= W * bpp)")
+    return n
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -531,6 +562,63 @@ class HipCodec:
         _lib.check(self.L.llicti_decode_images_reduced(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
                                                        _ptr(modes), len(modes), r, _ptr(ws), ws.numel(), _ptr(out), _ptr(offs),
                                                        _stream_ptr(self.device)))
+        return out
+
+    # ---- interleaved, pitched pixels (llicti_encode_images_px / llicti_decode_images_px): the layout image sources deliver
+    def _px_layout(self, fmt, dims, px_off, pitch):
+        """-> (format, offsets or None, pitches or None, bytes the windows reach into the buffer)"""
+        fmt = pixel_format(fmt)
+        bpp = pixel_bytes(fmt)
+        B = len(dims)
+        pt = None if pitch is None else np.ascontiguousarray(pitch, dtype=np.uint64)
+        offs = None if px_off is None else np.ascontiguousarray(px_off, dtype=np.uint64)
+        assert (pt is None or pt.shape == (B,)) and (offs is None or offs.shape == (B,))
+        # (a pitch the library will refuse counts as tight here: the call below reports it)
+        spans = [(h - 1) * max(int(pt[b]) if pt is not None else 0, w * bpp) + w * bpp for b, (h, w) in enumerate(dims)]
+        total = sum(spans) if offs is None else max(int(o) + n for o, n in zip(offs, spans))
+        return fmt, offs, pt, total
+
+    def encode_px(self, pix, Hs, Ws, mode, fmt=PIX_RGB8, px_off=None, pitch=None, out=None, seg_len=None):
+        """pix: flat uint8 device tensor of INTERLEAVED pixels (fmt: "rgb" | "bgr" | "rgba" | "bgra" or PIX_*); image b's Hs[b] x Ws[b] window
+        starts at byte px_off[b] with rows pitch[b] bytes apart (None: tight rows / the windows back to back), so a window may be a crop of a
+        larger frame -> (containers, seg_len) as encode_v: the bytes of the planar call on the same pixel values.  Alpha is ignored.  Async."""
+        assert pix.dtype == torch.uint8 and pix.is_cuda and pix.dim() == 1 and pix.is_contiguous()
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        fmt, offs, pt, total = self._px_layout(fmt, list(zip(Hs.tolist(), Ws.tolist())), px_off, pitch)
+        assert pix.numel() >= total
+        ws = self.workspace_v(Hs, Ws, mode)
+        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
+        if out is None:
+            out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
+        if seg_len is None:
+            seg_len = torch.zeros((B, NSEG), dtype=torch.int32, device=self.device)
+        assert out.shape[1] >= stride
+        one, per = self._modes_arg(mode, B)
+        modes = np.full(B, one, dtype=np.int32) if per is None else per
+        _lib.check(self.L.llicti_encode_images_px(self.ctx, _ptr(pix), fmt, _ptr(offs), _ptr(pt), B, _ptr(Hs), _ptr(Ws), _ptr(modes),
+                                                  _ptr(ws), ws.numel(), _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
+        return out, seg_len
+
+    def decode_px(self, containers, seg_len, Hs, Ws, mode, fmt=PIX_RGB8, reduce=0, out=None, px_off=None, pitch=None):
+        """device containers of B images of FULL sizes Hs[b] x Ws[b] -> flat uint8 device tensor of interleaved pixels: image b's window (of
+        reduced_dims(Hs[b], Ws[b], reduce)) at byte px_off[b] with rows pitch[b] bytes apart (None: back to back / tight).  Only the bytes of
+        the windows' rows are written -- `out` may be a canvas whose other bytes must stay; alpha is written as 255.  reduce as decode_reduced.  Async."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.shape[0] == B
+        r = int(reduce)
+        dims = [reduced_dims(h, w, r) if 0 <= r <= 5 else (int(h), int(w)) for h, w in zip(Hs, Ws)]      # (a bad r: the library says so)
+        fmt, offs, pt, total = self._px_layout(fmt, dims, px_off, pitch)
+        ws = self.workspace_v(Hs, Ws, mode)
+        if out is None:
+            out = torch.empty((total,), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.dim() == 1 and out.numel() >= total
+        one, per = self._modes_arg(mode, B)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        _lib.check(self.L.llicti_decode_images_px(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                                                  _ptr(modes), len(modes), r, _ptr(ws), ws.numel(), _ptr(out), fmt, _ptr(offs), _ptr(pt),
+                                                  _stream_ptr(self.device)))
         return out
 
     def decode_v(self, containers, seg_len, Hs, Ws, mode, out=None, reduce=0):

@@ -31,6 +31,36 @@ __global__ void header_write_kernel(const uint8_t *__restrict__ rgb, const int32
     }
 }
 
+// header_write_kernel of llicti_encode_images_px: the same header (thread 0's part to the letter); the raw DC band is read from the caller's
+// interleaved pixels through image b's window (PixGeo), colour c of a pixel at byte c of it (2 - c where blue comes first)
+__global__ void header_write_px_kernel(const uint8_t *__restrict__ pix, const PixGeo *__restrict__ pv, const int32_t *__restrict__ minmax,
+                                       const ImgGeo *__restrict__ iv, uint8_t *__restrict__ out, long out_stride, int32_t *__restrict__ seg_len,
+                                       unsigned long long *__restrict__ ssum)
+{
+    const int b = blockIdx.x;
+    if (ssum && threadIdx.x == 0) ssum[b] = 0ull;
+    uint8_t *o = out + (long)b * out_stride;
+    const ImgGeo ig = iv[b];
+    const PixGeo pg = pv[b];
+    const int byte0 = ig.byte0;
+    const int h4 = ig.h4, w4 = ig.w4, padint = ig.padint;
+    if (threadIdx.x == 0) {
+        o[0] = (uint8_t)byte0; o[1] = (uint8_t)h4; o[2] = (uint8_t)w4;
+        const int32_t *mm = minmax + 4 * b;
+        const int16_t v[6] = { 0, (int16_t)mm[0], (int16_t)mm[1], 255, (int16_t)mm[2], (int16_t)mm[3] };
+        for (int k = 0; k < 6; ++k) { o[3 + 2 * k] = (uint8_t)(v[k] & 0xFF); o[4 + 2 * k] = (uint8_t)((v[k] >> 8) & 0xFF); }
+        o[15] = (uint8_t)(padint & 0xFF); o[16] = (uint8_t)((padint >> 8) & 0xFF);
+        int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
+        sl[0] = 3; sl[1] = 12; sl[2] = 2; sl[3] = 3 * h4 * w4;
+        for (int k = ig.nseg; k < LLICTI_NSEG; ++k) sl[k] = 0;
+    }
+    const int dcs = ig.dcs, bpp = pix_bpp(pg.fmt);
+    for (int t = threadIdx.x; t < 3 * h4 * w4; t += blockDim.x) {
+        const int c = t / (h4 * w4), r = t - c * h4 * w4, i = r / w4, j = r - i * w4;
+        o[17 + t] = pix[pg.off + (long)(dcs * i) * pg.pitch + (long)(dcs * j) * bpp + (pix_bgr(pg.fmt) ? 2 - c : c)];
+    }
+}
+
 // encode: copy the 45 slots of image b behind its header, tightly; seg_len[b][4..48].  st0: the model's first stage (host_plan.hpp: first_stage;
 // 0 for 5 levels) -- stage st0 + x is segment 4 + x.
 __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ slots, const long *__restrict__ slot_off,

@@ -49,6 +49,10 @@ struct Plan {
     int reduce = 0;
     std::vector<RedGeo> red;            // [B], empty for reduce = 0
     size_t d_red = 0;
+    // interleaved pixel buffers (plan_add_pixels): every image's window in the caller's buffer
+    std::vector<PixGeo> pix;            // [B], empty for the planar calls
+    size_t d_pix = 0;
+    long pix_units = 0;                 // the largest window in 4-pixel row pieces, H * ceil(W / 4): sizes the grids of lift_px_kernel / unlift_px_kernel
 };
 
 // AC decode has two table forms.  Few images in flight (latency bound: every stream is one serial wave and the GPU is
@@ -387,6 +391,61 @@ static void plan_add_reduced(Plan &p, int reduce, const size_t *out_off)
     reduced_key_tail(p.key, p.B, Hs.data(), Ws.data(), reduce, out_off);
     p.d_red = p.d_total;
     p.d_total = align_up(p.d_total + p.red.size() * sizeof(RedGeo), 256);
+}
+
+// Interleaved pixel buffers (llicti_encode_images_px / llicti_decode_images_px).  Bytes per pixel of a format, 0: not a format.
+static int pix_format_bytes(int fmt) { return (fmt >= LLICTI_PIX_RGB8 && fmt <= LLICTI_PIX_BGRA8) ? pix_bpp(fmt) : 0; }
+// Bytes from the first pixel of an H x W window to the end of its last one: (H - 1) pitch + W bpp.  pitch = 0: tight rows.  0: bad argument.
+static size_t pix_window_span(int fmt, int H, int W, size_t pitch)
+{
+    const int bpp = pix_format_bytes(fmt);
+    if (!bpp || H < 1 || W < 1) return 0;
+    const size_t row = (size_t)W * bpp;
+    if (pitch == 0) pitch = row;
+    if (pitch < row || pitch > 0x7FFFFFFFu) return 0;
+    return (size_t)(H - 1) * pitch + row;
+}
+// The windows of a call, validated: image b's is Hw[b] x Ww[b] (a reduced decode: the reduced size).  pitch = nullptr: tight rows;
+// px_off = nullptr: the windows back to back in call order, each of its own span.
+static int resolve_pixels(const char *who, int B, const int *Hw, const int *Ww, int fmt, const size_t *px_off, const size_t *pitch, std::vector<PixGeo> &out)
+{
+    const int bpp = pix_format_bytes(fmt);
+    if (!bpp) return fail(LLICTI_EINVAL, "%s: unknown pixel format %d (LLICTI_PIX_RGB8, _BGR8, _RGBA8, _BGRA8)", who, fmt);
+    out.assign(B, PixGeo{});
+    size_t pos = 0;
+    for (int b = 0; b < B; ++b) {
+        const size_t row = (size_t)Ww[b] * bpp, pt = pitch ? pitch[b] : row;
+        if (pt < row || pt > 0x7FFFFFFFu)
+            return fail(LLICTI_EINVAL, "%s: pitch %zu of image %d (a row of its %d pixels has %zu bytes; at most 2^31 - 1)", who, pt, b, Ww[b], row);
+        out[b].off = (long)(px_off ? px_off[b] : pos);
+        out[b].pitch = (int)pt;
+        out[b].fmt = fmt;
+        pos += pix_window_span(fmt, Hw[b], Ww[b], pt);
+    }
+    return 0;
+}
+// The extra words a call on interleaved pixels adds to the cache key of its batch's plan, behind the reduced tail if there is one: a marker
+// no other key holds at that place (sizes are >= 32, a reduced tail starts with -1 .. -5), then every window's offset and pitch.  With B in
+// word 1, keys of 3 + 4 B (planar), 4 + 5 B (reduced), 4 + 6 B (pixels) and 5 + 7 B (both) words never compare equal.
+static void pixel_key_tail(std::vector<long> &key, const std::vector<PixGeo> &pix)
+{
+    key.push_back(-(16 + (long)pix[0].fmt));
+    for (const PixGeo &pg : pix) { key.push_back(pg.off); key.push_back(pg.pitch); }
+}
+// Turns the plan of a batch -- build_plan's, with plan_add_reduced's table for a reduced decode; tight PLANAR placement, whose fields
+// (`uniform`, `vec_ok`, ImgGeo::rgb_off, rgb_bytes, the tile lists) keep their meaning and are not read by the pixel kernels -- into the plan
+// of a call on interleaved pixels: the window table goes behind the other tables of the device block, the key gets its tail.
+static void plan_add_pixels(Plan &p, const std::vector<PixGeo> &pix)
+{
+    p.pix = pix;
+    p.pix_units = 0;
+    for (int b = 0; b < p.B; ++b) {
+        const long Hw = p.reduce ? p.red[b].Hr : p.img[b].H, Ww = p.reduce ? p.red[b].Wr : p.img[b].W;
+        p.pix_units = std::max(p.pix_units, Hw * ((Ww + 3) / 4));
+    }
+    pixel_key_tail(p.key, pix);
+    p.d_pix = p.d_total;
+    p.d_total = align_up(p.d_total + p.pix.size() * sizeof(PixGeo), 256);
 }
 
 // mode: 0 = AC container (torchac-compatible, the reference's format); 0x100 | M = rANS container (v3) with M

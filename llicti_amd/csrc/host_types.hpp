@@ -65,6 +65,16 @@ struct RedGeo {
     int Hr, Wr;                               // ceil(H / 2^r), ceil(W / 2^r)
 };
 LLICTI_HD int reduced_dim(int n, int r) { return (n + (1 << r) - 1) >> r; }
+// One image's window in the caller's INTERLEAVED pixel buffer (llicti_encode_images_px / llicti_decode_images_px; device table of the call's
+// plan, behind the tables above): pixel (i, j) of the window is the bpp bytes at off + i * pitch + j * bpp.  fmt: LLICTI_PIX_* -- bit 0 says
+// blue comes first, bit 1 that a fourth byte (alpha: ignored by the encoder, written as 255 by the decoder) follows the three colours.
+struct PixGeo {
+    long off;                                 // first byte of the window's first pixel
+    int pitch;                                // bytes from one row of the window to the next (>= W * bpp)
+    int fmt;
+};
+LLICTI_HD int pix_bpp(int fmt) { return 3 + (fmt >> 1); }            // of a VALID format (host: pix_format_bytes checks)
+LLICTI_HD bool pix_bgr(int fmt) { return (fmt & 1) != 0; }
 static Geom make_geom(int B, int H, int W, int lvl)
 {
     Geom g;

@@ -149,3 +149,195 @@ __global__ __launch_bounds__(256) void unlift_reduced_kernel(const int16_t *__re
     const int R = Bl + Co;
     dst[0] = (uint8_t)R; dst[rplane] = (uint8_t)G; dst[2 * rplane] = (uint8_t)Bl;
 }
+
+// ------------------------------------------------------------------------------------------------ interleaved, pitched pixels
+// llicti_encode_images_px / llicti_decode_images_px: the caller's buffer holds interleaved 8-bit pixels (PixGeo: window offset, row pitch,
+// format), the workspace the same planes as above.  ALPHA: the fourth byte of the 4-byte formats is ignored by the lift and written as 255
+// by the unlift.  The kernels walk the window's ROWS (a pitch breaks the flat index): a lane owns 4 consecutive pixels of one row -- 12 or
+// 16 contiguous bytes, so a wavefront covers 768 / 1024 contiguous bytes that are split into channels in registers.
+//   pixel side   dword accesses (3 or 4 per lane) when the window's first byte and its pitch are multiples of 4, and the lane has 4 pixels;
+//   plane side   short4 / float4 accesses when the image's W is a multiple of 4 (rows then start at multiples of 4 elements);
+//   otherwise    byte by byte / element by element, the W % 4 pixels that end a row included.
+// Both conditions are per IMAGE and come from its table entries (scalar loads, blockIdx.y): wave-uniform, and one call may hold an aligned
+// frame next to a crop that starts at an odd byte.  The unlift stores only bytes of the window's rows: no store straddles a row's end, nothing
+// of the canvas is read.
+
+// channel ch (0 R, 1 G, 2 B) of pixel k out of the BPP dwords of 4 pixels
+template <int BPP>
+__device__ __forceinline__ int px_byte(const uint32_t *d, int k, int ch) { const int t = k * BPP + ch; return (int)((d[t >> 2] >> (8 * (t & 3))) & 0xFFu); }
+
+template <int BPP>
+__device__ __forceinline__ void lift_px_rows(const uint8_t *__restrict__ src, int pitch, bool bgr, int H, int W, long plane,
+                                             int16_t *__restrict__ dst, float *__restrict__ fdst, int &mnCo, int &mnCg, int &mxCo, int &mxCg)
+{
+    const uint32_t Wq = (uint32_t)(W + 3) >> 2, units = (uint32_t)H * Wq;        // (<= 8160 * 2040)
+    const bool px_dw = (((uintptr_t)src | (uintptr_t)(uint32_t)pitch) & 3) == 0;
+    const bool pl_vec = (W & 3) == 0 && (((uintptr_t)dst & 7) | ((uintptr_t)fdst & 15)) == 0;
+    for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
+        const uint32_t i = u / Wq, j = (u - i * Wq) * 4;
+        const int n = min(4, W - (int)j);
+        const uint8_t *q = src + (long)i * pitch + (long)j * BPP;
+        int ch[4][3];
+        if (px_dw && n == 4) {
+            uint32_t d[BPP];
+#pragma unroll
+            for (int k = 0; k < BPP; ++k) d[k] = reinterpret_cast<const uint32_t *>(q)[k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { ch[k][0] = px_byte<BPP>(d, k, 0); ch[k][1] = px_byte<BPP>(d, k, 1); ch[k][2] = px_byte<BPP>(d, k, 2); }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                ch[k][0] = ch[k][1] = ch[k][2] = 0;
+                if (k < n) { ch[k][0] = q[k * BPP]; ch[k][1] = q[k * BPP + 1]; ch[k][2] = q[k * BPP + 2]; }
+            }
+        }
+        short y[4], co[4], cg[4];
+        float fy[4], fco[4], fcg[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int R = bgr ? ch[k][2] : ch[k][0], G = ch[k][1], Bl = bgr ? ch[k][0] : ch[k][2];
+            const int Co = R - Bl;
+            const int t = Bl + (Co >> 1);        // (lift_kernel's arithmetic, to the letter)
+            const int Cg = G - t;
+            const int Y = t + (Cg >> 1) - 127;
+            y[k] = (short)Y; co[k] = (short)Co; cg[k] = (short)Cg;
+            fy[k] = (float)Y / 255.0f; fco[k] = (float)Co / 255.0f; fcg[k] = (float)Cg / 255.0f;
+            if (k < n) { mnCo = min(mnCo, Co); mxCo = max(mxCo, Co); mnCg = min(mnCg, Cg); mxCg = max(mxCg, Cg); }
+        }
+        const long p = (long)i * W + j;
+        if (pl_vec) {
+            *reinterpret_cast<short4 *>(dst + p) = make_short4(y[0], y[1], y[2], y[3]);
+            *reinterpret_cast<short4 *>(dst + plane + p) = make_short4(co[0], co[1], co[2], co[3]);
+            *reinterpret_cast<short4 *>(dst + 2 * plane + p) = make_short4(cg[0], cg[1], cg[2], cg[3]);
+            *reinterpret_cast<float4 *>(fdst + p) = make_float4(fy[0], fy[1], fy[2], fy[3]);
+            *reinterpret_cast<float4 *>(fdst + plane + p) = make_float4(fco[0], fco[1], fco[2], fco[3]);
+            *reinterpret_cast<float4 *>(fdst + 2 * plane + p) = make_float4(fcg[0], fcg[1], fcg[2], fcg[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) {
+                    dst[p + k] = y[k]; dst[plane + p + k] = co[k]; dst[2 * plane + p + k] = cg[k];
+                    fdst[p + k] = fy[k]; fdst[plane + p + k] = fco[k]; fdst[2 * plane + p + k] = fcg[k];
+                }
+        }
+    }
+}
+
+// lift_kernel on interleaved pixels: the same int16 planes, float planes (the same (float)v / 255.0f), min / max partials and clearing of the
+// call's status words; image b's size and plane placement from iv[b], its window from pv[b].
+__global__ __launch_bounds__(256) void lift_px_kernel(const uint8_t *__restrict__ pix, int16_t *__restrict__ planes, float *__restrict__ fplanes,
+                                                      int32_t *__restrict__ part, int32_t *__restrict__ zero, int n_zero,
+                                                      const ImgGeo *__restrict__ iv, const PixGeo *__restrict__ pv)
+{
+    const int b = blockIdx.y;
+    if (zero && blockIdx.x == 0 && b == 0)
+        for (int i = threadIdx.x; i < n_zero; i += blockDim.x) zero[i] = 0;
+    const int H = iv[b].H, W = iv[b].W, pitch = pv[b].pitch, fmt = pv[b].fmt;
+    const long plane = iv[b].plane;
+    const uint8_t *src = pix + pv[b].off;
+    int16_t *dst = planes + iv[b].pix_off;
+    float *fdst = fplanes + iv[b].pix_off;
+    int mnCo = 32767, mnCg = 32767, mxCo = -32768, mxCg = -32768;
+    if (pix_bpp(fmt) == 4) lift_px_rows<4>(src, pitch, pix_bgr(fmt), H, W, plane, dst, fdst, mnCo, mnCg, mxCo, mxCg);
+    else lift_px_rows<3>(src, pitch, pix_bgr(fmt), H, W, plane, dst, fdst, mnCo, mnCg, mxCo, mxCg);
+    for (int o = 32; o > 0; o >>= 1) {
+        mnCo = min(mnCo, __shfl_xor(mnCo, o)); mxCo = max(mxCo, __shfl_xor(mxCo, o));
+        mnCg = min(mnCg, __shfl_xor(mnCg, o)); mxCg = max(mxCg, __shfl_xor(mxCg, o));
+    }
+    __shared__ int red[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        const int wv = threadIdx.x >> 6;
+        red[wv][0] = mnCo; red[wv][1] = mnCg; red[wv][2] = mxCo; red[wv][3] = mxCg;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        int v = red[0][k];
+        for (int wv = 1; wv < 4; ++wv) v = (k < 2) ? min(v, red[wv][k]) : max(v, red[wv][k]);
+        part[((long)b * gridDim.x + blockIdx.x) * 4 + k] = v;
+    }
+}
+
+// r: 0 = every pixel of the planes; r >= 1 = the pixels whose row and column are multiples of 2^r (unlift_reduced_kernel's gather) -- Ho x Wo
+// is the window either way
+template <int BPP>
+__device__ __forceinline__ void unlift_px_rows(const int16_t *__restrict__ src, long plane, int W, int r, int Ho, int Wo,
+                                               uint8_t *__restrict__ dst, int pitch, bool bgr)
+{
+    const uint32_t Wq = (uint32_t)(Wo + 3) >> 2, units = (uint32_t)Ho * Wq;
+    const bool px_dw = (((uintptr_t)dst | (uintptr_t)(uint32_t)pitch) & 3) == 0;
+    const bool pl_vec = r == 0 && (W & 3) == 0 && ((uintptr_t)src & 7) == 0;
+    for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
+        const uint32_t i = u / Wq, j = (u - i * Wq) * 4;
+        const int n = min(4, Wo - (int)j);
+        short y[4], co[4], cg[4];
+        if (pl_vec) {
+            const long p = (long)i * W + j;
+            const short4 a = *reinterpret_cast<const short4 *>(src + p);
+            const short4 c = *reinterpret_cast<const short4 *>(src + plane + p);
+            const short4 d = *reinterpret_cast<const short4 *>(src + 2 * plane + p);
+            y[0] = a.x; y[1] = a.y; y[2] = a.z; y[3] = a.w;
+            co[0] = c.x; co[1] = c.y; co[2] = c.z; co[3] = c.w;
+            cg[0] = d.x; cg[1] = d.y; cg[2] = d.z; cg[3] = d.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                y[k] = co[k] = cg[k] = 0;
+                if (k < n) {
+                    const int16_t *s = src + ((long)(i << r) * W + ((long)(j + k) << r));
+                    y[k] = s[0]; co[k] = s[plane]; cg[k] = s[2 * plane];
+                }
+            }
+        }
+        uint32_t c3[4][3];          // the pixel's bytes in the buffer's order
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int Y = y[k] + 127, Co = co[k], Cg = cg[k];
+            const int t = Y - (Cg >> 1);
+            const int G = Cg + t;
+            const int Bl = t - (Co >> 1);
+            const int R = Bl + Co;
+            c3[k][0] = (uint32_t)(uint8_t)(bgr ? Bl : R); c3[k][1] = (uint32_t)(uint8_t)G; c3[k][2] = (uint32_t)(uint8_t)(bgr ? R : Bl);
+        }
+        uint8_t *q = dst + (long)i * pitch + (long)j * BPP;
+        if (px_dw && n == 4) {
+            uint32_t d[BPP];
+#pragma unroll
+            for (int k = 0; k < BPP; ++k) d[k] = 0;
+#pragma unroll
+            for (int t = 0; t < 4 * BPP; ++t) {
+                const int k = t / BPP, ch = t - k * BPP;
+                d[t >> 2] |= (ch == 3 ? 255u : c3[k][ch == 3 ? 0 : ch]) << (8 * (t & 3));
+            }
+#pragma unroll
+            for (int k = 0; k < BPP; ++k) reinterpret_cast<uint32_t *>(q)[k] = d[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) {
+                    q[k * BPP] = (uint8_t)c3[k][0]; q[k * BPP + 1] = (uint8_t)c3[k][1]; q[k * BPP + 2] = (uint8_t)c3[k][2];
+                    if (BPP == 4) q[k * BPP + 3] = 255;
+                }
+        }
+    }
+}
+
+// unlift_kernel (rv == nullptr, r = 0) and unlift_reduced_kernel (rv: the reduced sizes, r >= 1) into interleaved pixels: the last kernel of
+// llicti_decode_images_px.  Latches the call's status words exactly as they do.
+__global__ __launch_bounds__(256) void unlift_px_kernel(const int16_t *__restrict__ planes, uint8_t *__restrict__ pix, int r,
+                                                        const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                        int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
+                                                        const RedGeo *__restrict__ rv, const PixGeo *__restrict__ pv)
+{
+    const int b = blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (b == 0 && status[0] != 0) *latched = status[0];
+        if (img_latched) img_latched[b] = status[status_head + b];
+    }
+    const int W = iv[b].W, Ho = rv ? rv[b].Hr : iv[b].H, Wo = rv ? rv[b].Wr : W, pitch = pv[b].pitch, fmt = pv[b].fmt;
+    const long plane = iv[b].plane;
+    const int16_t *src = planes + iv[b].pix_off;
+    uint8_t *dst = pix + pv[b].off;
+    if (pix_bpp(fmt) == 4) unlift_px_rows<4>(src, plane, W, r, Ho, Wo, dst, pitch, pix_bgr(fmt));
+    else unlift_px_rows<3>(src, plane, W, r, Ho, Wo, dst, pitch, pix_bgr(fmt));
+}

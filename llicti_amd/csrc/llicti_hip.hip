@@ -4,6 +4,7 @@
 //
 // Kernels (reference call sites in include/llicti_hip.h):
 //   lift_kernel / unlift_kernel       integer YCoCg-R lift, min/max, float planes          (HBM bound)
+//   lift_px_kernel / unlift_px_kernel the same on the caller's interleaved, pitched pixels (RGB8 / BGR8 / RGBA8 / BGRA8) (HBM bound)
 //   band_params_kernel<BAND>          interpolator CNN: 3 chained fp32-MFMA GEMMs per pixel tile,
 //                                     weights of one 88-channel head resident in LDS        (MFMA bound)
 //   cdf_pairs_kernel                  encoder: the two table entries per symbol (10 erfc)   (VALU)
@@ -401,6 +402,19 @@ static int launch_lift(const uint8_t *d_rgb, int B, long plane, bool vec_ok, int
     return 0;
 }
 
+// launch_lift on interleaved pixels: image b's window is pv[b]; units: the largest window in 4-pixel row pieces (Plan::pix_units)
+static int launch_lift_px(const uint8_t *d_pix, int B, long units, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part, hipStream_t s,
+                          int32_t *zero, int n_zero, const ImgGeo *iv, const PixGeo *pv)
+{
+    const long want = (units + 255) / 256;
+    const int gx = (int)std::max<long>(1, std::min<long>(std::min<long>(want, std::max(8, 4096 / B)), kLiftMaxParts / B));
+    if ((long)B * gx > kLiftMaxParts) return fail(LLICTI_EINVAL, "lift: batch of %d images exceeds the partials scratch", B);
+    lift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(d_pix, planes, fplanes, part, zero, n_zero, iv, pv);
+    minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // The band CNN of config B (60-wide heads): the 18 forms of config A's, same grid and tile lists (launch_band_params decides them).
 static int launch_band_params_h60(llicti_ctx *c, const float *fplanes, const Geom &g, int band, float *params, hipStream_t s, const Geom *gv,
                                   const TileRef *tiles, int form, int gx, int lds_bytes, int tiles_x, int tiles_y, int n_tiles)
@@ -676,8 +690,12 @@ static int acquire_block(llicti_ctx *c, size_t need, PlanBlock *out)
 // enqueues ONE asynchronous upload on the call's stream -- no device synchronisation, no allocation once the pool is warm.
 // reduce >= 1 (llicti_decode_images_reduced): rgb_off places the REDUCED outputs; the plan itself is the batch's full-size one with tight
 // placement (the unused default of its full-size fields) plus the reduced output table, under a key of its own (host_plan.hpp: plan_add_reduced).
-static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, const int *Ms, hipStream_t s, PlanDev **out, int reduce = 0)
+// pix (llicti_encode_images_px / llicti_decode_images_px): the call's windows in the caller's interleaved buffer; rgb_off is unused (the planar
+// fields of the plan keep their tight default), the window table and its key tail go behind everything else (host_plan.hpp: plan_add_pixels).
+static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, const int *Ms, hipStream_t s, PlanDev **out, int reduce = 0,
+                    const std::vector<PixGeo> *pix = nullptr)
 {
+    if (pix) rgb_off = nullptr;
     const size_t *red_off = reduce > 0 ? rgb_off : nullptr;
     if (reduce > 0) rgb_off = nullptr;
     std::vector<long> key;
@@ -691,6 +709,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
         }
     }
     if (reduce > 0) reduced_key_tail(key, B, Hs, Ws, reduce, red_off);
+    if (pix) pixel_key_tail(key, *pix);
     auto it = c->plans.find(key);
     if (it != c->plans.end()) {
         PlanDev *pd = it->second;
@@ -706,6 +725,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     ++c->n_plan_build;
     build_plan(p, B, Hs, Ws, rgb_off, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms, c->nlev);
     if (reduce > 0) plan_add_reduced(p, reduce, red_off);
+    if (pix) plan_add_pixels(p, *pix);
     if (p.key != key) return fail(LLICTI_EINVAL, "plan: key mismatch");
     if (p.rslot_off.size() != (size_t)p.nstreams || p.sref.size() != (size_t)p.nstreams)
         return fail(LLICTI_EINVAL, "plan: stream tables have %zu / %zu entries, expected %d", p.rslot_off.size(), p.sref.size(), p.nstreams);
@@ -722,6 +742,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     put(p.d_tiles, p.tiles.data(), p.tiles.size() * sizeof(TileRef));
     put(p.d_sref, p.sref.data(), p.sref.size() * sizeof(StreamRef));
     put(p.d_red, p.red.data(), p.red.size() * sizeof(RedGeo));
+    put(p.d_pix, p.pix.data(), p.pix.size() * sizeof(PixGeo));
     bool ok = hipMemcpyAsync(pd->blk.dev, h, p.d_total, hipMemcpyHostToDevice, s) == hipSuccess;
     ok = ok && hipEventRecord(pd->blk.uploaded, s) == hipSuccess;
     ok = ok && hipEventRecord(pd->blk.done, s) == hipSuccess;      // (so that the block is never recycled in front of its own upload)
@@ -783,6 +804,9 @@ struct PlanUse {
     ~PlanUse() { if (pd && hipEventRecord(pd->blk.done, s) == hipSuccess) { pd->blk.used = true; pd->blk.done_stream = s; } }
 };
 
+// the pixel arguments of llicti_encode_images_px / llicti_decode_images_px as the caller gave them (host_plan.hpp: resolve_pixels)
+struct PixArgs { int fmt; const size_t *off, *pitch; };
+
 // modes: one container mode for the call (n_modes = 1) or one per image (n_modes = B: rANS containers of ONE lane kind whose stream counts may differ,
 // fixed and "auto" xwide counts mixed); -> ME of the call (the lane kind, with the first image's count, | 0x1000 if any image is "auto") and, for
 // per-image modes, Ms (count | 0x1000 for an "auto" image: build_plan)
@@ -837,10 +861,12 @@ extern "C" int llicti_workspace_params_v(llicti_ctx *c, int B, const int *Hs, co
 }
 
 static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_off, int B, const int *Hs, const int *Ws, const int *modes, int n_modes,
-                        void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
+                        void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream, const PixArgs *px = nullptr)
 {
     if (!c || !d_rgb || !d_workspace || !d_out || !d_seg_len) return fail(LLICTI_EINVAL, "encode_images: null pointer");
     if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
+    std::vector<PixGeo> pix;
+    if (px) if (int rc = resolve_pixels("encode_images_px", B, Hs, Ws, px->fmt, px->off, px->pitch, pix)) return rc;
     int ME = 0;
     std::vector<int> Ms;
     if (int rc = resolve_modes("encode_images", modes, n_modes, B, &ME, Ms)) return rc;
@@ -858,7 +884,7 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
     PlanDev *pd = nullptr;
-    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd)) return rc;
+    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd, 0, px ? &pix : nullptr)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     const int M = p.M;
@@ -885,8 +911,15 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
     {
         ProfSpan span(c, PROF_MISC, s);
         // (the lift is the call's first kernel and sets no status: it clears the call's status words on the way)
-        if (int rc = launch_lift(d_rgb, B, p.max_plane, p.vec_ok, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img)) return rc;
-        header_write_kernel<<<B, 256, 0, s>>>(d_rgb, mm, d_img, d_out, (long)out_stride, d_seg_len, autoM ? (unsigned long long *)(ws + p.off_rpos) : nullptr);
+        unsigned long long *ssum0 = autoM ? (unsigned long long *)(ws + p.off_rpos) : nullptr;
+        if (px) {
+            const PixGeo *d_pv = pd->dev<PixGeo>(p.d_pix);
+            if (int rc = launch_lift_px(d_rgb, B, p.pix_units, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img, d_pv)) return rc;
+            header_write_px_kernel<<<B, 256, 0, s>>>(d_rgb, d_pv, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
+        } else {
+            if (int rc = launch_lift(d_rgb, B, p.max_plane, p.vec_ok, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img)) return rc;
+            header_write_kernel<<<B, 256, 0, s>>>(d_rgb, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
+        }
     }
     // The encoder has no dependency between stages: every (level, band) reads only original pixels.  With llicti_set_tuning("enc_side_levels", 1)
     // levels 4..1 (twelve CNN + twelve pairs launches, a quarter of the work) run on a side stream next to level 0's, with their own
@@ -1103,6 +1136,15 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
             }
         }
     }
+    if (!p.pix.empty()) {
+        // interleaved output (llicti_decode_images_px), full size or reduced: one kernel, the window table behind the others
+        const int gxp = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
+        ProfSpan span(c, PROF_MISC, s);
+        unlift_px_kernel<<<dim3(gxp, B), 256, 0, s>>>(planes, d_rgb, reduce, status, kStatusHead, c->d_status, c->d_img_status, d_img,
+                                                      reduce > 0 ? pd->dev<RedGeo>(p.d_red) : nullptr, pd->dev<PixGeo>(p.d_pix));
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     if (reduce > 0) {
         // (every side stream of the reference-format pipeline was joined back onto `s` at the end of its band: nothing is pending here)
         long max_rplane = 0;
@@ -1125,7 +1167,8 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
 }
 
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
-                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0)
+                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0,
+                        const PixArgs *px = nullptr)
 {
     if (!c || !d_in || !d_seg_len || !d_workspace || !d_rgb) return fail(LLICTI_EINVAL, "decode_images: null pointer");
     if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
@@ -1134,12 +1177,18 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
     std::vector<int> Ms;
     if (int rc = resolve_modes("decode_images", modes, n_modes, B, &ME, Ms)) return rc;
     if (int rc = check_model(c, "decode_images", ME, Ms)) return rc;
+    std::vector<PixGeo> pix;
+    if (px) {
+        std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes
+        for (int b = 0; b < B; ++b) { Hw[b] = reduced_dim(Hs[b], reduce); Ww[b] = reduced_dim(Ws[b], reduce); }
+        if (int rc = resolve_pixels("decode_images_px", B, Hw.data(), Ww.data(), px->fmt, px->off, px->pitch, pix)) return rc;
+    }
     if (ME & 0x1000) return fail(LLICTI_EINVAL, "decode_images: LLICTI_MODE_RANS_X_AUTO is an encoder's mode -- a container says how many streams it has (header: llicti_header_mode)");
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
     PlanDev *pd = nullptr;
-    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd, reduce)) return rc;
+    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd, reduce, px ? &pix : nullptr)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     if (!p.uniform && p.M == 0) return fail(LLICTI_EINVAL, "decode_images: a batch of mixed sizes needs a rANS container (the reference-format container codes equal sizes per call)");
@@ -1192,6 +1241,26 @@ extern "C" int llicti_decode_images_reduced(llicti_ctx *c, const uint8_t *d_in, 
                                             void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
     return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, d_rgb, rgb_off, stream, reduce);
+}
+
+extern "C" int llicti_pixel_bytes(int format) { return pix_format_bytes(format); }
+extern "C" size_t llicti_pixel_span(int format, int H, int W, size_t pitch) { return pix_window_span(format, H, W, pitch); }
+
+extern "C" int llicti_encode_images_px(llicti_ctx *c, const uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch,
+                                       int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
+                                       uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
+{
+    const PixArgs px{ format, px_off, pitch };
+    return encode_batch(c, d_pix, nullptr, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream, &px);
+}
+
+extern "C" int llicti_decode_images_px(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                       int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                       void *d_workspace, size_t workspace_bytes,
+                                       uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream)
+{
+    const PixArgs px{ format, px_off, pitch };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, d_pix, nullptr, stream, reduce, &px);
 }
 
 extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,

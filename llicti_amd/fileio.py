@@ -72,7 +72,7 @@ def read_llic(path):
 
 
 # ---------------------------------------------------------------------------------------------- images
-def _read_ppm(buf: bytes):
+def _read_ppm(buf: bytes, layout="chw"):
     # P6 <ws> W <ws> H <ws> maxval <single ws> data ; '#' comments allowed in the header
     pos, toks = 0, []
     while len(toks) < 4:
@@ -92,31 +92,49 @@ def _read_ppm(buf: bytes):
     if mx != 255:
         raise ValueError("only 8-bit PPM (maxval 255) is supported")
     data = np.frombuffer(buf, dtype=np.uint8, count=3 * H * W, offset=pos + 1)
+    if layout == "hwc":
+        return data.reshape(H, W, 3)               # (the file's own layout: a read-only view of its bytes)
     return np.ascontiguousarray(data.reshape(H, W, 3).transpose(2, 0, 1))
 
 
-def read_image(path) -> np.ndarray:
-    """-> uint8 [3, H, W] (RGB).  The reference's loader does PIL .convert('RGB') + ToTensor (uint8 / 255)."""
+def _check_layout(layout):
+    if layout not in ("chw", "hwc"):
+        raise ValueError(f"layout must be 'chw' or 'hwc', got {layout!r}")
+
+
+def read_image(path, layout="chw") -> np.ndarray:
+    """-> uint8 [3, H, W] (RGB).  The reference's loader does PIL .convert('RGB') + ToTensor (uint8 / 255).
+    layout="hwc": uint8 [H, W, 3], the interleaved rows image files and PIL hold -- no transpose; what LLICTI.encode_batch_async(pixels="rgb")
+    and HipCodec.encode_px take."""
+    _check_layout(layout)
     with open(path, "rb") as fh:
         head = fh.read(2)
     if head == b"P6":
         with open(path, "rb") as fh:
-            return _read_ppm(fh.read())
+            return _read_ppm(fh.read(), layout)
     try:
         from PIL import Image
     except ImportError as e:                                     # pragma: no cover
         raise RuntimeError(f"{path}: PNG/JPG input needs PIL; binary PPM works without it") from e
-    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8).transpose(2, 0, 1))
+    hwc = np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+    return np.ascontiguousarray(hwc if layout == "hwc" else hwc.transpose(2, 0, 1))
 
 
-def write_image(path, rgb: np.ndarray):
+def write_image(path, rgb: np.ndarray, layout="chw"):
+    """rgb: uint8 [3, H, W], or with layout="hwc" uint8 [H, W, 3] (what decode_batch_async(pixels="rgb") returns): written without a transpose."""
+    _check_layout(layout)
     rgb = np.asarray(rgb)
-    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[0] != 3:
-        raise ValueError("expected uint8 [3, H, W]")
-    hwc = np.ascontiguousarray(rgb.transpose(1, 2, 0))
+    if layout == "hwc":
+        if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("expected uint8 [H, W, 3]")
+        hwc = np.ascontiguousarray(rgb)
+    else:
+        if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[0] != 3:
+            raise ValueError("expected uint8 [3, H, W]")
+        hwc = np.ascontiguousarray(rgb.transpose(1, 2, 0))
     if os.path.splitext(path)[1].lower() in (".ppm", ".pnm"):
         with open(path, "wb") as fh:
-            fh.write(b"P6\n%d %d\n255\n" % (rgb.shape[2], rgb.shape[1]))
+            fh.write(b"P6\n%d %d\n255\n" % (hwc.shape[1], hwc.shape[0]))
             fh.write(hwc.tobytes())
         return
     from PIL import Image

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ...codec import (MODE_AC, MODE_RANS, NSEG, HipCodec, auto_modes, bytestream_list_to_container, container_to_bytestream_list, header_dims, mode_of_header, mode_of_name, reduced_dims)
+from ...codec import (MODE_AC, MODE_RANS, NSEG, HipCodec, auto_modes, bytestream_list_to_container, container_to_bytestream_list, header_dims, mode_of_header, mode_of_name, pixel_bytes, pixel_format, reduced_dims)
 from ...config import check_supported, model_shape
 
 
@@ -202,25 +202,37 @@ class LLICTI(nn.Module):
         return enc.lists(), enc.x_ycocg
 
     @torch.no_grad()
-    def encode_batch_async(self, x, want_ycocg=False, slot=0):
+    def encode_batch_async(self, x, want_ycocg=False, slot=0, pixels=None):
         """Enqueue the encode of a batch and the download of its containers (pinned host buffers); returns an EncodedBatch whose lists() waits
         for the download and cuts the containers into the reference's bytestream_lists.  Nothing here blocks the host: a caller can enqueue
         the next batch before it converts this one (LLICTIAgent.eval_model with eval_batch > 1).  `slot` selects one of the staging buffer
         sets (two batches in flight need two).
         x: a tensor [B,3,H,W] (float32 in {k/255} or uint8; host or device), or a LIST of B uint8 host arrays [3,H_b,W_b] whose sizes may
-        differ (the reference's test loader yields arbitrary sizes, dataloaders/image_dl.py:40-45): one call, one upload, one download."""
+        differ (the reference's test loader yields arbitrary sizes, dataloaders/image_dl.py:40-45): one call, one upload, one download.
+        pixels = "rgb" | "bgr" | "rgba" | "bgra": x is a LIST of uint8 host arrays [H_b, W_b, 3 | 4], interleaved as image files, PIL and OpenCV
+        hold them -- uploaded as they are and lifted from that layout on the device (HipCodec.encode_px; alpha is ignored): the same containers
+        as the planar list, without a transpose on the host.  EncodedBatch.rgb is then the flat INTERLEAVED device buffer."""
+        if pixels is not None and not isinstance(x, (list, tuple)):
+            raise ValueError("pixels=...: the batch is a list of uint8 [H, W, C] arrays")
         if isinstance(x, (list, tuple)):
             imgs = [np.ascontiguousarray(a) for a in x]
-            for a in imgs:
-                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[0] != 3:
+            if pixels is not None:
+                fmt = pixel_format(pixels)
+                bpp = pixel_bytes(fmt)
+                if any(a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != bpp for a in imgs):
+                    raise ValueError(f"a pixels={pixels!r} batch holds uint8 [H, W, {bpp}] arrays")
+                Hs, Ws = [int(a.shape[0]) for a in imgs], [int(a.shape[1]) for a in imgs]
+            else:
+                if any(a.dtype != np.uint8 or a.ndim != 3 or a.shape[0] != 3 for a in imgs):
                     raise ValueError("a list batch holds uint8 [3, H, W] arrays")
+                Hs, Ws = [int(a.shape[1]) for a in imgs], [int(a.shape[2]) for a in imgs]
             codec = self.codec(None)
-            Hs, Ws = [int(a.shape[1]) for a in imgs], [int(a.shape[2]) for a in imgs]
-            offs, total = codec.flat_offsets(Hs, Ws)
+            total = sum(a.size for a in imgs)            # the images back to back, tightly packed: flat_offsets() / encode_px's default placement
             host = self._pinned(("rgb_in", slot), total)
-            hv = host.numpy()
-            for a, o in zip(imgs, offs):
-                hv[int(o):int(o) + a.size] = a.reshape(-1)
+            hv, o = host.numpy(), 0
+            for a in imgs:
+                hv[o:o + a.size] = a.reshape(-1)
+                o += a.size
             cur = torch.cuda.current_stream(codec.device)
             up, down = self._copy_streams(codec.device)
             with torch.cuda.stream(up):
@@ -232,7 +244,7 @@ class LLICTI(nn.Module):
             t0.record(cur)
             B = len(imgs)
             mode = self.mode_for_batch(B, codec.device, sizes=list(zip(Hs, Ws)))
-            cont, seg = codec.encode_v(rgb, Hs, Ws, mode)
+            cont, seg = codec.encode_v(rgb, Hs, Ws, mode) if pixels is None else codec.encode_px(rgb, Hs, Ws, mode, fmt)
             x_ycocg = None
         else:
             t0 = None
@@ -321,12 +333,15 @@ class LLICTI(nn.Module):
         return res.to(torch.float32) / 255           # LLICTI_nets.py:87
 
     @torch.no_grad()
-    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0):
+    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0, pixels=None):
         """bytestream_lists of B images -> uint8 [B,3,H,W] on the device, enqueued (upload from a pinned buffer + decode); device-side
         failures are reported by codec().check() / image_status().  The images of a call share a container kind; in a rANS container their
         SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each.
         reduce = r: every image at 1 / 2^r (decompres()); H, W, Hs, Ws of the result are the REDUCED sizes.  (The pinned staging buffers hold the
-        call's INPUT -- containers and segment lengths, sized by the full image -- so a reduced and a full decode share them safely.)"""
+        call's INPUT -- containers and segment lengths, sized by the full image -- so a reduced and a full decode share them safely.)
+        pixels = "rgb" | "bgr" | "rgba" | "bgra": the result is a LIST of B uint8 device tensors [H_b, W_b, 3 | 4], interleaved (alpha 255), written
+        in that layout by the decode's last kernel (HipCodec.decode_px) -- views of one flat buffer, the images back to back; with flat=True
+        (that flat buffer, Hs, Ws) instead."""
         codec = self.codec(devc if (devc is not None and torch.device(devc).type == "cuda") else None)
         Hs, Ws, modes = [], [], []
         for bl in lists:
@@ -373,6 +388,15 @@ class LLICTI(nn.Module):
         cur.wait_stream(up)
         cont_d.record_stream(cur)
         seg_d.record_stream(cur)
+        if pixels is not None:
+            bpp = pixel_bytes(pixels)
+            out = codec.decode_px(cont_d, seg_d, Hs, Ws, mode, pixels, reduce=reduce)
+            if reduce:
+                Hs, Ws = (list(v) for v in zip(*(reduced_dims(h, w, reduce) for h, w in zip(Hs, Ws))))
+            if flat:
+                return out, Hs, Ws
+            offs = np.concatenate(([0], np.cumsum([h * w * bpp for h, w in zip(Hs, Ws)])))
+            return [out[int(o):int(o) + h * w * bpp].view(h, w, bpp) for o, h, w in zip(offs, Hs, Ws)]
         if mixed or flat:
             out = codec.decode_v(cont_d, seg_d, Hs, Ws, mode, reduce=reduce)
             if reduce:
