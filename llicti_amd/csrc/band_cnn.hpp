@@ -45,14 +45,58 @@ template <int BAND, int TH> inline constexpr KTab kKTab = make_ktab(BAND, CnnGeo
 #ifndef CNN_EXP_NO_WFRAG
 #define CNN_EXP_NO_WFRAG 0
 #endif
+// Round 9's ladder (profiles/r9/cnn_tile_ladder.json, tools/cnn_tile_ladder.sh): each removes ONE thing from the tile loop; TIMING ONLY as above.
+//   CNN_EXP_L0_B_ONCE = 1     layer 0's B fragments (the two pixel tiles' input reads) are read for the first k-step only; the others reuse the registers;
+//   CNN_EXP_REM_B_ONCE = 1    the same for the 4x4x1 remainder path's four B reads per k-step (its chain of MFMAs stays);
+//   CNN_EXP_NO_BPERM = 1      the remainder path's result goes to layer 1 without the 16 ds_bpermute per tile;
+//   CNN_EXP_NO_RELU_BIAS = 3  no ReLU (bit 0) and no bias load (bit 1: accumulators start from zero);
+//   CNN_EXP_NO_STORE = 1      the params stores stay in the code and are never executed (an opaque scalar condition).
+#ifndef CNN_EXP_L0_B_ONCE
+#define CNN_EXP_L0_B_ONCE 0
+#endif
+#ifndef CNN_EXP_REM_B_ONCE
+#define CNN_EXP_REM_B_ONCE 0
+#endif
+#ifndef CNN_EXP_NO_BPERM
+#define CNN_EXP_NO_BPERM 0
+#endif
+#ifndef CNN_EXP_NO_RELU_BIAS
+#define CNN_EXP_NO_RELU_BIAS 0
+#endif
+#ifndef CNN_EXP_NO_STORE
+#define CNN_EXP_NO_STORE 0
+#endif
 
 template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F>
 __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
-__device__ __forceinline__ float relu(float x) { return (x > 0.0f) ? x : 0.0f; }
-__device__ __forceinline__ f32x4 relu4(f32x4 v) { v[0] = relu(v[0]); v[1] = relu(v[1]); v[2] = relu(v[2]); v[3] = relu(v[3]); return v; }
+// relu(x) = x > 0 ? x : +0.  Written as that select -- or as fmaxf -- it costs TWO vector instructions per value: the compiler puts
+// a canonicalising v_max_f32 x, x in front of the v_max_f32 0, x, because it cannot tell that an MFMA result is no signalling NaN.  A vector
+// instruction beside the MFMAs is not free: it takes the SIMD's vector issue for 4 cycles, and the 176 per wave and tile (88 values) cost 2.7 % of a pass
+// (profiles/r9/cnn_tile_ladder.json).  v_med3_f32(x, 0, +inf) is the same function in ONE instruction, for every x an accumulator can hold: x > 0 (and
+// +inf) -> x; x < 0, -0, +0 -> +0; a quiet NaN -> +0, the instruction's min3 rule (tools/hipchecks/check_relu_med3.hip holds it against the select, bit for
+// bit).  The +inf has to be opaque -- med3 of (x, 0, a constant +inf) is folded back into the two-instruction max -- and is made so per call, not per
+// kernel: an s_mov_b32 beside four v_med3 instead of a scalar register live across the tile loop (the kernel is at its SGPR budget).
+#ifndef CNN_RELU_MED3
+#define CNN_RELU_MED3 1
+#endif
+__device__ __forceinline__ f32x4 relu4(f32x4 v)
+{
+    if constexpr (CNN_EXP_NO_RELU_BIAS & 1) return v;
+#if CNN_RELU_MED3
+    int inf_bits = 0x7f800000;
+    asm volatile("" : "+s"(inf_bits));
+    const float inf = __int_as_float(inf_bits);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_fmed3f(v[i], 0.0f, inf);
+#else
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (v[i] > 0.0f) ? v[i] : 0.0f;
+#endif
+    return v;
+}
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 // 16 blocks of D[4x4] = A[4x1] * B[1x4] + C: A[i] in lane 4b + i, B[j] in lane 4b + j, D[i][j] in lane 4b + j, register i; one
 // fmaf per element (tools/hipchecks/check_mfma4x4.hip)
@@ -328,7 +372,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
         f32x4 a0[kMT][kNT];
 #pragma unroll
         for (int T = 0; T < kMT0; ++T) {
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(lds + PO::bias0 + (T * 4 + q) * 4);
+            const f32x4 bv = (CNN_EXP_NO_RELU_BIAS & 2) ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : *reinterpret_cast<const f32x4 *>(lds + PO::bias0 + (T * 4 + q) * 4);
 #pragma unroll
             for (int n = 0; n < kNT; ++n) a0[T][n] = bv;
         }
@@ -347,7 +391,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
             const float *rb_base = lds_cur + ((wave * kNT) >> 1) * kInPitch + rpix;
             const float *ra_base = lds + PO::w0r + (4 * rcg + rsub) * 4;
             f32x4 dR = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
-            if constexpr (kRem) dR = *reinterpret_cast<const f32x4 *>(lds + PO::bias0r + 4 * rcg);
+            if constexpr (kRem && !(CNN_EXP_NO_RELU_BIAS & 2)) dR = *reinterpret_cast<const f32x4 *>(lds + PO::bias0r + 4 * rcg);
             f32x4 ar_c;
             float br_c[4];
 #endif
@@ -379,14 +423,14 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
                     constexpr int U = kKTab<BAND, TH>.s[t + 1].U, S = kKTab<BAND, TH>.s[t + 1].S;
                     const float *bp = lds_cur + U + pix0 + (S == 1 ? q : q_row);
 #pragma unroll
-                    for (int n = 0; n < kNT; ++n) b_n[n] = bp[(n >> 1) * kInPitch + 16 * (n & 1)];
+                    for (int n = 0; n < kNT; ++n) b_n[n] = CNN_EXP_L0_B_ONCE ? b_c[n] : bp[(n >> 1) * kInPitch + 16 * (n & 1)];
 #pragma unroll
                     for (int T = 0; T < kMT0; ++T) a_n[T] = CNN_EXP_NO_WFRAG ? a_c[T] : lds[PO::w0 + (T * NK0 + t + 1) * 64 + lane];
 #if CNN_REM4X4
                     if constexpr (kRem) {
                         ar_n = CNN_EXP_NO_WFRAG ? ar_c : *reinterpret_cast<const f32x4 *>(ra_base + (t + 1) * 32);
 #pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) br_n[kk] = rb_base[U + (S == 1 ? kk : kk * kInPitch)];
+                        for (int kk = 0; kk < 4; ++kk) br_n[kk] = CNN_EXP_REM_B_ONCE ? br_c[kk] : rb_base[U + (S == 1 ? kk : kk * kInPitch)];
                     }
 #endif
                 }
@@ -441,6 +485,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
             for (int n = 0; n < kNT; ++n)
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
+                    if constexpr (CNN_EXP_NO_BPERM) { a0[5][n][r] = dR[2 * n + r]; continue; }
                     const int src = 4 * (32 * r + 16 * n + px);
                     const float t0 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(dR[0])));
                     const float t1 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(dR[1])));
@@ -478,7 +523,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
         //      the B fragments of the next (k-step tt of the consumer = tile tt>>2, register tt&3)
         f32x4 a2[kNT];
         {
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(lds + PO::bias2 + q * 4);
+            const f32x4 bv = (CNN_EXP_NO_RELU_BIAS & 2) ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : *reinterpret_cast<const f32x4 *>(lds + PO::bias2 + q * 4);
 #pragma unroll
             for (int n = 0; n < kNT; ++n) a2[n] = bv;
         }
@@ -501,7 +546,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
             if constexpr (T == 2 * kMT / 3 && CNN_STAGE_SITES > 2) stage_next(3);
             f32x4 a1[kNT];
             {
-                const f32x4 bv = *reinterpret_cast<const f32x4 *>(lds + PO::bias1 + (T * 4 + q) * 4);
+                const f32x4 bv = (CNN_EXP_NO_RELU_BIAS & 2) ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : *reinterpret_cast<const f32x4 *>(lds + PO::bias1 + (T * 4 + q) * 4);
 #pragma unroll
                 for (int n = 0; n < kNT; ++n) a1[n] = bv;
             }
@@ -546,6 +591,9 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 
         // D row 4q + r = output 4q + r of this head -> channel plane head * 16 + 4q + r of params[img][64][h * w] (numerics.hpp: ParRow).
         // A store instruction writes 16 consecutive positions (64 bytes) of four planes; plane 15 of a head does not exist (15 outputs).
+        int store = 1;
+        if constexpr (CNN_EXP_NO_STORE) { store = 0; asm volatile("" : "+s"(store)); }
+        if (!store) { /* (timing-only variant) */ } else
         if constexpr (RAGGED) {
             const Geom gi = gv[img];                            // this image's
             const long npos = (long)gi.h * gi.w;
