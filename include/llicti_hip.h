@@ -297,6 +297,30 @@ int llicti_decode_images_px(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stri
                             void *d_workspace, size_t workspace_bytes,
                             uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream);
 
+/* TRANSCODE: containers of one kind into containers of another, on the device, at the cost of ONE decode.  Image b's output container and its 49
+ * segment lengths are byte for byte what llicti_encode_images_vm (B = 1) writes, in dst_modes[b], for the pixels container b decodes to -- without
+ * the pixels ever being made: behind each (level, band) stage of the decoder the stage's CNN outputs and symbols become the encoder's
+ * (c_low, c_high) pairs (one cdf_pairs launch), and the target's entropy coder runs on them.  3 x levels band-CNN launches instead of the
+ * 6 x levels of a decode followed by an encode, neither an unlift nor a lift.
+ *   src_modes  one mode (n_src = 1) or one per image (n_src = B), under llicti_decode_images_vm's rules: every container the decoder reads
+ *              (llicti_header_mode names it); LLICTI_MODE_RANS_X_AUTO is not a source
+ *   dst_modes  one mode (n_dst = 1) or one per image (n_dst = B), under llicti_encode_images_vm's rules, LLICTI_MODE_RANS_X_AUTO included
+ *   d_out      image b's container at d_out + b * out_stride (out_stride as for llicti_encode_images_v), its segment lengths in d_seg_len_out[b];
+ *              must not overlap d_in
+ *   workspace  llicti_transcode_workspace_bytes of the same arguments (ctx = NULL: config A): the source call's layout, then the target's
+ * LLICTI_EINVAL before anything is launched: an auto mode as a source, mixed lane kinds on either side, the reference format on either side with
+ * images of different sizes, a null pointer, a size outside 32 .. 8160, an in_stride below the header bytes, overlapping buffers;
+ * LLICTI_ENOSPACE: a workspace or out_stride that is too small.  llicti_transcode_workspace_bytes gives 0 for a refused combination.
+ * Asynchronous on `stream`, no device synchronisation or allocation on a warm context.  STATUS as after a decode: what the decoder's kernels flag
+ * (header, unpack, init, every stage, the rANS end-of-stream check) and the coder's LLICTI_ENOSPACE are latched by the call's last kernel
+ * (llicti_check_status, llicti_image_status).  A flagged image does not disturb the others; its own row of d_seg_len_out is 49 zeros. */
+size_t llicti_transcode_workspace_bytes(const llicti_ctx *ctx, int B, const int *Hs, const int *Ws,
+                                        const int *src_modes, int n_src, const int *dst_modes, int n_dst);
+int llicti_transcode_images(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len_in,
+                            int B, const int *Hs, const int *Ws, const int *src_modes, int n_src,
+                            const int *dst_modes, int n_dst, void *d_workspace, size_t workspace_bytes,
+                            uint8_t *d_out, size_t out_stride, int32_t *d_seg_len_out, void *stream);
+
 /* Where llicti_encode_images / llicti_decode_images of B images of H x W in `mode` keep the YCoCg-R planes inside the caller's workspace
  * (byte offsets): int16 [B][3][H][W] (Y - 127, Co, Cg) and float32 [B][3][H][W] = planes / 255 -- the second is the `x_ycocg` the
  * reference's compress() returns beside the streams (LLICTI_nets.py:143-144, :159), so a caller that wants it reads it from the workspace

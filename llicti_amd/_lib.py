@@ -74,6 +74,8 @@ _SIGS = {
     "llicti_encode_images_px": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images_px": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
+    "llicti_transcode_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
+    "llicti_transcode_images": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_encode_images": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "llicti_check_status": (_i, [_vp, _vp]),

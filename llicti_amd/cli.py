@@ -1,6 +1,7 @@
 """python -m llicti_amd.cli encode IN.(png|ppm|jpg) OUT.llic [--container ac|auto|rans<M>|wrans<M>|xrans<M>] [--checkpoint model_best.pth.tar]
                                 [--config llicti_B.json]
    python -m llicti_amd.cli decode IN.llic OUT.(png|ppm) [--reduce R] [--checkpoint model_best.pth.tar] [--config llicti_B.json]
+   python -m llicti_amd.cli transcode IN.llic OUT.llic [--container ac|auto|rans<M>|wrans<M>|xrans<M>] [--checkpoint model_best.pth.tar] [--config llicti_B.json]
    python -m llicti_amd.cli info   IN.llic
 
 File-level front end of the MI355X hot path (needs a GPU: there is no CPU fallback).  Without a checkpoint the
@@ -8,7 +9,9 @@ seed-1337 default init is used, as the reference does when `model_best.pth.tar` 
 reference's JSON file the model was trained with (configs/llicti_A.json -- the default -- or llicti_B.json): as the reference's README says,
 compress and decompress with the json file that was used to train the model.  decode --reduce R writes the image at 1 / 2^R of its size
 (R = 0 .. the model's levels: 5 for config A, 2 for config B; `info` lists the sizes): exactly every 2^R-th pixel of every 2^R-th row, decoded
-from the coarse levels alone -- a decimation without smoothing, so fine texture aliases."""
+from the coarse levels alone -- a decimation without smoothing, so fine texture aliases.  transcode rewrites a file in another container
+(default "auto") -- the bytes `encode --container ...` gives for the image the file holds -- on the device, at the cost of one decode: no pixels
+are made (it needs the model the file was written with, like decode)."""
 from __future__ import annotations
 
 import argparse
@@ -47,6 +50,8 @@ def build_parser():
     d = sub.add_parser("decode"); d.add_argument("src"); d.add_argument("dst"); d.add_argument("--checkpoint", default=None)
     d.add_argument("--config", default=None)
     d.add_argument("--reduce", type=_reduce_arg, default=0, metavar="R", help="decode at 1 / 2^R of the size (every 2^R-th pixel; no smoothing)")
+    t = sub.add_parser("transcode"); t.add_argument("src"); t.add_argument("dst")
+    t.add_argument("--container", default="auto"); t.add_argument("--checkpoint", default=None); t.add_argument("--config", default=None)
     i = sub.add_parser("info"); i.add_argument("src")
     return ap
 
@@ -74,6 +79,17 @@ def main(argv=None):
         fileio.write_llic(a.dst, bl)
         n = sum(len(s) for r in bl for s in r)
         print(f"{a.src} -> {a.dst}: {hwc.shape[1]}x{hwc.shape[0]}, {n} bytes, {8.0 * n / (hwc.shape[0] * hwc.shape[1]):.4f} bpp, {dt:.3f} s")
+        return 0
+    if a.cmd == "transcode":
+        from .codec import mode_of_header, name_of_mode
+        bl = fileio.read_llic(a.src)
+        model, torch = _model(a.container, a.checkpoint, a.config)
+        t0 = time.time()
+        out = model.transcode_batch([bl])[0]
+        dt = time.time() - t0
+        fileio.write_llic(a.dst, out)
+        n0, n = (sum(len(s) for r in x for s in r) for x in (bl, out))
+        print(f"{a.src} -> {a.dst}: container {name_of_mode(mode_of_header(bl))} -> {name_of_mode(mode_of_header(out))}, {n0} -> {n} bytes, {dt:.3f} s")
         return 0
     bl = fileio.read_llic(a.src)
     model, torch = _model("ac", a.checkpoint, a.config)

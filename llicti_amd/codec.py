@@ -643,6 +643,48 @@ class HipCodec:
                                                       _ptr(ws), ws.numel(), _ptr(out), None, _stream_ptr(self.device)))
         return out
 
+    # ---- transcode (llicti_transcode_images): containers of one kind into containers of another at the cost of one decode
+    def transcode_workspace(self, Hs, Ws, src_mode, dst_mode):
+        """(the cached workspace, grown to the running maximum like the other workspaces, for a transcode of these sizes and modes --
+        llicti_transcode_workspace_bytes: the source call's layout followed by the target's --, [source modes, target modes] as the int32
+        arrays the C-ABI takes: one entry, or one per image)"""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        sides = []
+        for mode in (src_mode, dst_mode):
+            one, per = self._modes_arg(mode, B)
+            sides.append(np.array([one], dtype=np.int32) if per is None else per)
+        key = ("transcode", Hs.tobytes(), Ws.tobytes(), sides[0].tobytes(), sides[1].tobytes())
+        n = self._ws_need.get(key)
+        if n is None:
+            if len(self._ws_need) > 256:
+                self._ws_need.clear()
+            n = self._ws_need[key] = int(self.L.llicti_transcode_workspace_bytes(self.ctx, B, _ptr(Hs), _ptr(Ws), _ptr(sides[0]), len(sides[0]),
+                                                                                 _ptr(sides[1]), len(sides[1])))
+        if n == 0:
+            raise _lib.LlictiError(_lib.EINVAL, "transcode: a combination of sizes and container modes the call refuses (an \"auto\" source, mixed lane kinds, "
+                                                "the reference format with images of different sizes, a mode the model does not take)")
+        return self._workspace_of(n), sides
+
+    def transcode(self, containers, seg_len, Hs, Ws, src_mode, dst_mode, out=None, seg_len_out=None):
+        """device containers of B images of sizes Hs[b] x Ws[b] in src_mode (one mode or one per image: what container_modes() / mode_of_header say)
+        -> (containers uint8 [B, stride], seg_len int32 [B, 49]) in dst_mode (one or one per image, MODE_RANS_AUTO included), async: image b's
+        bytes are those of encode() of its pixels in dst_mode[b], made from ONE pass of the band CNN and without the pixels.  Status as after a
+        decode: check() / image_status(); a flagged image's seg_len row is zeros."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.dtype == torch.uint8 and containers.is_cuda and containers.dim() == 2 and containers.shape[0] == B and containers.is_contiguous()
+        ws, (src, dst) = self.transcode_workspace(Hs, Ws, src_mode, dst_mode)
+        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
+        if out is None:
+            out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
+        if seg_len_out is None:
+            seg_len_out = torch.zeros((B, NSEG), dtype=torch.int32, device=self.device)
+        _lib.check(self.L.llicti_transcode_images(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                                                  _ptr(src), len(src), _ptr(dst), len(dst), _ptr(ws), ws.numel(),
+                                                  _ptr(out), out.shape[1], _ptr(seg_len_out), _stream_ptr(self.device)))
+        return out, seg_len_out
+
     def container_modes(self, containers):
         """The modes the headers of device containers [B, stride] name (a small download: 17 bytes per image; synchronises the current stream) --
         what decode() / decode_v() take for containers that came out of an "auto" encode (MODE_RANS_AUTO: the encoder picked the stream counts)."""

@@ -61,6 +61,42 @@ __global__ void header_write_px_kernel(const uint8_t *__restrict__ pix, const Pi
     }
 }
 
+// header_write_kernel of llicti_transcode_images, which has no pixels: the same header (thread 0's part to the letter) in the TARGET container's
+// form (iv: the target plan's table); the min / max words are the ones the decoder read from the source header, and the raw DC band is the
+// decoder's planes at the DC stride, taken back through the integer lift (header_read_kernel's forward form; a rejected source header left
+// mid grey there).  The call's first kernel on the target side: it clears the target plan's n_zero status words (block 0).
+__global__ void header_transcode_kernel(const int16_t *__restrict__ planes, const int32_t *__restrict__ minmax, const ImgGeo *__restrict__ iv,
+                                        uint8_t *__restrict__ out, long out_stride, int32_t *__restrict__ seg_len, unsigned long long *__restrict__ ssum,
+                                        int32_t *__restrict__ zero, int n_zero)
+{
+    const int b = blockIdx.x;
+    if (b == 0) for (int t = threadIdx.x; t < n_zero; t += blockDim.x) zero[t] = 0;
+    if (ssum && threadIdx.x == 0) ssum[b] = 0ull;
+    uint8_t *o = out + (long)b * out_stride;
+    const ImgGeo ig = iv[b];
+    const int byte0 = ig.byte0;
+    const int W = ig.W, h4 = ig.h4, w4 = ig.w4, padint = ig.padint;
+    const long plane = ig.plane;
+    if (threadIdx.x == 0) {
+        o[0] = (uint8_t)byte0; o[1] = (uint8_t)h4; o[2] = (uint8_t)w4;
+        const int32_t *mm = minmax + 4 * b;
+        const int16_t v[6] = { 0, (int16_t)mm[0], (int16_t)mm[1], 255, (int16_t)mm[2], (int16_t)mm[3] };
+        for (int k = 0; k < 6; ++k) { o[3 + 2 * k] = (uint8_t)(v[k] & 0xFF); o[4 + 2 * k] = (uint8_t)((v[k] >> 8) & 0xFF); }
+        o[15] = (uint8_t)(padint & 0xFF); o[16] = (uint8_t)((padint >> 8) & 0xFF);
+        int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
+        sl[0] = 3; sl[1] = 12; sl[2] = 2; sl[3] = 3 * h4 * w4;
+        for (int k = ig.nseg; k < LLICTI_NSEG; ++k) sl[k] = 0;
+    }
+    const int dcs = ig.dcs;
+    for (int t = threadIdx.x; t < h4 * w4; t += blockDim.x) {
+        const int i = t / w4, j = t - i * w4;
+        const long off = ig.pix_off + (long)(dcs * i) * W + dcs * j;
+        const int Y = planes[off] + 127, Co = planes[off + plane], Cg = planes[off + 2 * plane];
+        const int tt = Y - (Cg >> 1), G = Cg + tt, Bl = tt - (Co >> 1), R = Bl + Co;
+        o[17 + t] = (uint8_t)R; o[17 + h4 * w4 + t] = (uint8_t)G; o[17 + 2 * h4 * w4 + t] = (uint8_t)Bl;
+    }
+}
+
 // encode: copy the 45 slots of image b behind its header, tightly; seg_len[b][4..48].  st0: the model's first stage (host_plan.hpp: first_stage;
 // 0 for 5 levels) -- stage st0 + x is segment 4 + x.
 __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ slots, const long *__restrict__ slot_off,

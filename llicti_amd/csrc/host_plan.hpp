@@ -583,3 +583,94 @@ static int plan_header_dims(const uint8_t *h, int *H, int *W)
     return LLICTI_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ transcode
+// llicti_transcode_images runs the decoder of the source containers and the entropy-coder back end of the target ones in ONE call, on two
+// plans of the same batch (sizes, tight placement) that differ in their container modes: the caller's workspace is [source plan | target plan],
+// each part laid out as for a call of its own.  The decoder's planes, min/max words and CNN outputs stay where the source plan puts them; the
+// target's kernels (cdf_pairs_kernel behind every stage, the rANS coder's seed symbols) address them through the TARGET plan's tables -- so
+// the two plans must place every image's planes and CNN outputs identically, which they do because both are functions of the sizes and the
+// `uniform` form alone (tests/sanitize_transcode_host.cpp checks it over random batches; the call checks it again, it costs nothing).
+struct TranscodeLayout { size_t off_dst = 0, total = 0; };
+static TranscodeLayout transcode_layout(const Plan &src, const Plan &dst)
+{
+    TranscodeLayout t;
+    t.off_dst = align_up(src.total, 256);
+    t.total = t.off_dst + dst.total;
+    return t;
+}
+static bool transcode_plans_agree(const Plan &src, const Plan &dst)
+{
+    if (src.B != dst.B || src.nlev != dst.nlev || src.uniform != dst.uniform) return false;
+    const int B = src.B;
+    for (int b = 0; b < B; ++b) {
+        const ImgGeo &a = src.img[b], &d = dst.img[b];
+        if (a.H != d.H || a.W != d.W || a.plane != d.plane || a.pix_off != d.pix_off || a.h4 != d.h4 || a.w4 != d.w4 || a.dcs != d.dcs || a.hdr_bytes != d.hdr_bytes) return false;
+    }
+    for (int lvl = 0; lvl < src.nlev; ++lvl) {
+        if (src.lev_maxpos[lvl] != dst.lev_maxpos[lvl]) return false;
+        for (int b = 0; b < B; ++b) {
+            const Geom &a = src.geo[(size_t)lvl * B + b], &d = dst.geo[(size_t)lvl * B + b];
+            if (a.pix_off != d.pix_off || a.par_off != d.par_off || a.h != d.h || a.w != d.w) return false;
+            for (int band = 0; band < 3; ++band) {
+                const StageGeom &sa = src.sg[(size_t)(lvl * 3 + band) * B + b], &sd = dst.sg[(size_t)(lvl * 3 + band) * B + b];
+                if (sa.img_off != sd.img_off || sa.par_off != sd.par_off || sa.hc != sd.hc || sa.wc != sd.wc || sa.plane != sd.plane) return false;
+            }
+        }
+    }
+    return true;
+}
+// The container modes of one side of a whole-batch call -> ME and, where the images' modes differ, Ms (build_plan's arguments); false: a
+// combination the calls refuse (an unknown mode, mixed lane kinds, the reference format beside a rANS container).
+static bool plan_side_modes(const int *modes, int n_modes, int B, int *ME_out, std::vector<int> &Ms)
+{
+    Ms.clear();
+    if (!modes || (n_modes != 1 && n_modes != B)) return false;
+    int ME = mode_streams(modes[0]);
+    if (ME < 0) return false;
+    if (n_modes == B && B > 1) {
+        bool any_auto = false, differ = false;
+        for (int b = 0; b < B; ++b) {
+            const int MEb = mode_streams(modes[b]);
+            if (MEb < 0 || ((MEb >> 8) & 3) != ((ME >> 8) & 3) || ((MEb & 0xFF) == 0) != ((ME & 0xFF) == 0)) return false;
+            Ms.push_back(MEb & 0x10FF);
+            any_auto = any_auto || (MEb & 0x1000);
+            differ = differ || MEb != ME;
+        }
+        if (!differ) Ms.clear();
+        else if (any_auto) ME |= 0x1000;
+    }
+    *ME_out = ME;
+    return true;
+}
+// Bytes of workspace llicti_transcode_images needs; 0: a combination it refuses (bad sizes or modes, an "auto" mode as the source, mixed lane
+// kinds on a side, a mode the model does not take, the reference format on either side with images of different sizes).
+static size_t plan_transcode_workspace_bytes(int B, const int *Hs, const int *Ws, const int *src_modes, int n_src, const int *dst_modes, int n_dst,
+                                             int nlev = LLICTI_NLEVELS)
+{
+    if (check_dims_v(B, Hs, Ws)) return 0;
+    int MEs = 0, MEd = 0;
+    std::vector<int> Mss, Msd;
+    if (!plan_side_modes(src_modes, n_src, B, &MEs, Mss) || !plan_side_modes(dst_modes, n_dst, B, &MEd, Msd)) return 0;
+    if (MEs & 0x1000) return 0;
+    for (int m : Mss) if (m & 0x1000) return 0;
+    bool ok = model_takes(nlev, MEs) && model_takes(nlev, MEd);
+    for (int m : Mss) ok = ok && model_takes(nlev, (MEs & 0x300) | m);
+    for (int m : Msd) ok = ok && model_takes(nlev, (MEd & 0x300) | m);
+    if (!ok) return 0;
+    bool mixed = false;
+    for (int b = 1; b < B; ++b) mixed = mixed || Hs[b] != Hs[0] || Ws[b] != Ws[0];
+    if (mixed && ((MEs & 0xFF) == 0 || (MEd & 0xFF) == 0)) return 0;
+    if (nlev < LLICTI_NLEVELS)
+        for (int b = 0; b < B; ++b) {
+            const Geom gl = make_geom(1, Hs[b], Ws[b], nlev - 1);
+            if (gl.h > 255 || gl.w > 255) return 0;
+        }
+    size_t total = 0;
+    for (int ragged = 0; ragged < 2; ++ragged) {      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)
+        Plan s, d;
+        build_plan(s, B, Hs, Ws, nullptr, MEs, 256, 0, ragged != 0, Mss.empty() ? nullptr : Mss.data(), nlev);
+        build_plan(d, B, Hs, Ws, nullptr, MEd, 256, 0, ragged != 0, Msd.empty() ? nullptr : Msd.data(), nlev);
+        total = std::max(total, transcode_layout(s, d).total);
+    }
+    return total;
+}

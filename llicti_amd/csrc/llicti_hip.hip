@@ -686,6 +686,20 @@ static int acquire_block(llicti_ctx *c, size_t need, PlanBlock *out)
     return 0;
 }
 
+// the cache key of a full-size planar plan (build_plan writes the same words into Plan::key)
+static std::vector<long> plan_key(const llicti_ctx *c, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, const int *Ms)
+{
+    std::vector<long> key;
+    key.reserve(3 + 4 * (size_t)B);
+    key.push_back(ME); key.push_back(B); key.push_back(c->cnn_tile_rows * 2 + (c->force_ragged ? 1 : 0));
+    long pos = 0;
+    for (int b = 0; b < B; ++b) {
+        key.push_back(Hs[b]); key.push_back(Ws[b]); key.push_back(rgb_off ? (long)rgb_off[b] : pos); key.push_back((Ms && (ME & 0xFF)) ? Ms[b] : (ME & 0xFF));
+        pos += 3L * Hs[b] * Ws[b];
+    }
+    return key;
+}
+
 // The plan of a batch: cached by (mode, sizes, placement).  A miss builds the tables on the host, copies them into a pinned block and
 // enqueues ONE asynchronous upload on the call's stream -- no device synchronisation, no allocation once the pool is warm.
 // reduce >= 1 (llicti_decode_images_reduced): rgb_off places the REDUCED outputs; the plan itself is the batch's full-size one with tight
@@ -698,16 +712,7 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     if (pix) rgb_off = nullptr;
     const size_t *red_off = reduce > 0 ? rgb_off : nullptr;
     if (reduce > 0) rgb_off = nullptr;
-    std::vector<long> key;
-    key.reserve(3 + 4 * (size_t)B);
-    key.push_back(ME); key.push_back(B); key.push_back(c->cnn_tile_rows * 2 + (c->force_ragged ? 1 : 0));
-    {
-        long pos = 0;
-        for (int b = 0; b < B; ++b) {
-            key.push_back(Hs[b]); key.push_back(Ws[b]); key.push_back(rgb_off ? (long)rgb_off[b] : pos); key.push_back((Ms && (ME & 0xFF)) ? Ms[b] : (ME & 0xFF));
-            pos += 3L * Hs[b] * Ws[b];
-        }
-    }
+    std::vector<long> key = plan_key(c, B, Hs, Ws, rgb_off, ME, Ms);
     if (reduce > 0) reduced_key_tail(key, B, Hs, Ws, reduce, red_off);
     if (pix) pixel_key_tail(key, *pix);
     auto it = c->plans.find(key);
@@ -776,6 +781,22 @@ __global__ void latch_status_kernel(const int32_t *status, int32_t *latched, int
 {
     if (threadIdx.x == 0 && *status != 0) *latched = *status;
     if (img_latched) for (int b = threadIdx.x; b < B; b += blockDim.x) img_latched[b] = status[kStatusHead + b];
+}
+
+// The last kernel of llicti_transcode_images (which launches no unlift): the source plan's status words -- what the decoder's kernels flagged,
+// per call and per image -- and the target plan's (LLICTI_ENOSPACE) merged into the context's, as latch_status_kernel / unlift_kernel do for
+// an encode / a decode.  A flagged image's row of the output segment lengths becomes 49 zeros: what the coder made of its (deterministic)
+// garbage pixels is no container.
+__global__ void transcode_latch_kernel(const int32_t *src_status, const int32_t *dst_status, int32_t *latched, int32_t *img_latched, int B,
+                                       int32_t *__restrict__ seg_len)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0) {
+        const int32_t st = src_status[0] != 0 ? src_status[0] : dst_status[0];
+        if (st != 0) *latched = st;
+    }
+    if (t < B) img_latched[t] = src_status[kStatusHead + t];
+    if (t < B * LLICTI_NSEG && src_status[kStatusHead + t / LLICTI_NSEG] != 0) seg_len[t] = 0;
 }
 
 // The profiled extent of one whole-batch call: the closing event is recorded on EVERY way out (an early error return
@@ -860,6 +881,48 @@ extern "C" int llicti_workspace_params_v(llicti_ctx *c, int B, const int *Hs, co
     return LLICTI_OK;
 }
 
+// The entropy-coder back end of an encode, from the plan's pairs to the containers behind their headers: the range coder of the reference format,
+// or the rANS coder (with the encoder's stream-count pick for "auto" images).  ws: the workspace part laid out by pd's plan (pairs, slots, status);
+// planes, mm: the call's planes and min/max words (an encode's own; a transcode's decoder's, which sit in the source plan's part).
+static int encode_back_end(llicti_ctx *c, PlanDev *pd, uint8_t *ws, const int16_t *planes, const int32_t *mm, uint8_t *d_out, size_t out_stride,
+                           int32_t *d_seg_len, hipStream_t s)
+{
+    const Plan &p = pd->p;
+    const int B = p.B, M = p.M, Q = p.Q;
+    const bool autoM = (p.ME & 0x1000) != 0;
+    int32_t *status = (int32_t *)(ws + p.off_status);
+    uint32_t *pairs = (uint32_t *)(ws + p.off_pairs);
+    uint8_t *slots = ws + p.off_slots;
+    int32_t *slot_len = (int32_t *)(ws + p.off_slot_len);
+    const ImgGeo *d_img = pd->dev<ImgGeo>(p.d_img);
+    const StageGeom *d_sg = pd->dev<StageGeom>(p.d_sg);
+    const StreamDesc *d_desc = pd->dev<StreamDesc>(p.d_desc);
+    const long *d_rslot_off = pd->dev<long>(p.d_rslot_off);
+    const StreamRef *d_sref = pd->dev<StreamRef>(p.d_sref);
+    if (M == 0) {
+        ProfSpan span(c, PROF_AC, s);
+        const int st0 = first_stage(p.nlev), nst = LLICTI_NSTREAMS - st0;      // (the model's stages)
+        const int n_streams = nst * B;
+        ac_encode_pairs_kernel<<<n_streams, 64, 0, s>>>(pairs, d_desc + (size_t)st0 * B, n_streams, slots, slot_len + (size_t)st0 * B, status);
+        pack_kernel<<<dim3(nst, B), 256, 0, s>>>(slots, pd->dev<long>(p.d_slot_off), slot_len, B, p.img[0].hdr_bytes, d_out, (long)out_stride, d_seg_len, status, st0);
+    } else {
+        ProfSpan span(c, PROF_RANS_ENC, s);
+        int32_t *rinfo = (int32_t *)(ws + p.off_rinfo);
+        const StageGeom *sglv = d_sg + (size_t)(0 * 3 + 2) * B;      // the last stage: an xwide stream's seed symbols are read from its pixels
+        const int NS = p.nstreams;                                   // the streams of all images (an image's count is its own: ImgGeo::M)
+        // LLICTI_MODE_RANS_X_AUTO: each image's stream count is picked here, on the device, from what its last stage costs (a pure function of
+        // the image); the table holds the most it may get, the streams it does not get are empty segments
+        unsigned long long *ssum = autoM ? (unsigned long long *)(ws + p.off_rpos) : nullptr;      // (the decoder's cursor array: unused by an encode; B x 8 bytes of its >= B x 128)
+        if (autoM) choose_streams_kernel<<<dim3(kAutoSlices, B), 256, 0, s>>>(pairs, d_desc, B, ssum);
+        if (Q == 4) rans_encode_kernel<4><<<NS, 256, 0, s>>>(pairs, d_desc, B, d_sref, slots, d_rslot_off, p.rslot_cap, rinfo, status, sglv, planes, mm, ssum, d_img);
+        else if (Q == 2) rans_encode_kernel<2><<<NS, 128, 0, s>>>(pairs, d_desc, B, d_sref, slots, d_rslot_off, p.rslot_cap, rinfo, status, sglv, planes, mm, ssum, d_img);
+        else rans_encode_kernel<1><<<NS, 64, 0, s>>>(pairs, d_desc, B, d_sref, slots, d_rslot_off, p.rslot_cap, rinfo, status, sglv, planes, mm, ssum, d_img);
+        rans_pack_kernel<<<NS, 256, 0, s>>>(slots, d_rslot_off, rinfo, d_sref, d_img, d_out, (long)out_stride, d_seg_len, status, ssum, d_desc, B);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_off, int B, const int *Hs, const int *Ws, const int *modes, int n_modes,
                         void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream, const PixArgs *px = nullptr)
 {
@@ -878,7 +941,6 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
                 return fail(LLICTI_EINVAL, "encode_images: image %d is %dx%d; a %d-level model's header stores its level-%d grid (%dx%d) in one byte each "
                             "(at most %d pixels per side)", b, Ws[b], Hs[b], c->nlev, c->nlev - 1, gl.w, gl.h, 255 << c->nlev);
         }
-    const int Q = 1 << ((ME >> 8) & 3);
     const bool autoM = (ME & 0x1000) != 0;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
@@ -897,14 +959,9 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
     int32_t *mm = (int32_t *)(ws + p.off_minmax);
     int32_t *status = (int32_t *)(ws + p.off_status);
     uint32_t *pairs = (uint32_t *)(ws + p.off_pairs);
-    uint8_t *slots = ws + p.off_slots;
-    int32_t *slot_len = (int32_t *)(ws + p.off_slot_len);
     const ImgGeo *d_img = pd->dev<ImgGeo>(p.d_img);
     const Geom *d_geo = pd->dev<Geom>(p.d_geo);
     const StageGeom *d_sg = pd->dev<StageGeom>(p.d_sg);
-    const StreamDesc *d_desc = pd->dev<StreamDesc>(p.d_desc);
-    const long *d_rslot_off = pd->dev<long>(p.d_rslot_off);
-    const StreamRef *d_sref = pd->dev<StreamRef>(p.d_sref);
     const TileRef *d_tiles = p.uniform ? nullptr : pd->dev<TileRef>(p.d_tiles);
 
     CallScope call(c, s);
@@ -970,26 +1027,7 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
         HIPCHK(hipEventRecord(c->ev_enc[1], s2));
         HIPCHK(hipStreamWaitEvent(s, c->ev_enc[1], 0));
     }
-    if (M == 0) {
-        ProfSpan span(c, PROF_AC, s);
-        const int st0 = first_stage(p.nlev), nst = LLICTI_NSTREAMS - st0;      // (the model's stages)
-        const int n_streams = nst * B;
-        ac_encode_pairs_kernel<<<n_streams, 64, 0, s>>>(pairs, d_desc + (size_t)st0 * B, n_streams, slots, slot_len + (size_t)st0 * B, status);
-        pack_kernel<<<dim3(nst, B), 256, 0, s>>>(slots, pd->dev<long>(p.d_slot_off), slot_len, B, p.img[0].hdr_bytes, d_out, (long)out_stride, d_seg_len, status, st0);
-    } else {
-        ProfSpan span(c, PROF_RANS_ENC, s);
-        int32_t *rinfo = (int32_t *)(ws + p.off_rinfo);
-        const StageGeom *sglv = d_sg + (size_t)(0 * 3 + 2) * B;      // the last stage: an xwide stream's seed symbols are read from its pixels
-        const int NS = p.nstreams;                                   // the streams of all images (an image's count is its own: ImgGeo::M)
-        // LLICTI_MODE_RANS_X_AUTO: each image's stream count is picked here, on the device, from what its last stage costs (a pure function of
-        // the image); the table holds the most it may get, the streams it does not get are empty segments
-        unsigned long long *ssum = autoM ? (unsigned long long *)(ws + p.off_rpos) : nullptr;      // (the decoder's cursor array: unused by an encode; B x 8 bytes of its >= B x 128)
-        if (autoM) choose_streams_kernel<<<dim3(kAutoSlices, B), 256, 0, s>>>(pairs, d_desc, B, ssum);
-        if (Q == 4) rans_encode_kernel<4><<<NS, 256, 0, s>>>(pairs, d_desc, B, d_sref, slots, d_rslot_off, p.rslot_cap, rinfo, status, sglv, planes, mm, ssum, d_img);
-        else if (Q == 2) rans_encode_kernel<2><<<NS, 128, 0, s>>>(pairs, d_desc, B, d_sref, slots, d_rslot_off, p.rslot_cap, rinfo, status, sglv, planes, mm, ssum, d_img);
-        else rans_encode_kernel<1><<<NS, 64, 0, s>>>(pairs, d_desc, B, d_sref, slots, d_rslot_off, p.rslot_cap, rinfo, status, sglv, planes, mm, ssum, d_img);
-        rans_pack_kernel<<<NS, 256, 0, s>>>(slots, d_rslot_off, rinfo, d_sref, d_img, d_out, (long)out_stride, d_seg_len, status, ssum, d_desc, B);
-    }
+    if (int rc = encode_back_end(c, pd, ws, planes, mm, d_out, out_stride, d_seg_len, s)) return rc;
     latch_status_kernel<<<1, 64, 0, s>>>(status, c->d_status, nullptr, 0);
     HIPCHK(hipGetLastError());
     return LLICTI_OK;
@@ -1018,8 +1056,12 @@ extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, 
     return encode_batch(c, d_rgb, nullptr, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
 }
 
+// llicti_transcode_images: the target plan of the call and its part of the workspace.  decode_stages then launches cdf_pairs_kernel behind every
+// (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
+struct TranscodeTarget { PlanDev *pd; uint8_t *ws; };
+
 static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
-                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce)
+                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce, const TranscodeTarget *tc = nullptr)
 {
     const Plan &p = pd->p;
     const int B = p.B, M = p.M, Q = p.Q;
@@ -1134,8 +1176,19 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
                     }
                 }
             }
+            if (tc) {
+                // (the reference format's colour queues have been joined back onto `s` above; the next band's CNN launch, which overwrites
+                // `params`, follows on `s`)
+                const Plan &q = tc->pd->p;
+                const int k = lvl * 3 + band;
+                ProfSpan span(c, PROF_PAIRS, s);
+                cdf_pairs_kernel<<<dim3((unsigned)((q.lev_maxpos[lvl] + kPairsThreads - 1) / kPairsThreads), B), kPairsThreads, 0, s>>>(
+                    planes, params, mm, q.sg[(size_t)k * B], tc->pd->dev<StageGeom>(q.d_sg) + (size_t)k * B, (uint32_t *)(tc->ws + q.off_pairs) + q.pair_base[k]);
+                HIPCHK(hipGetLastError());
+            }
         }
     }
+    if (tc) return 0;      // (no pixels: the caller goes on with the target's header and coder, and latches the status words itself)
     if (!p.pix.empty()) {
         // interleaved output (llicti_decode_images_px), full size or reduced: one kernel, the window table behind the others
         const int gxp = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
@@ -1270,6 +1323,109 @@ extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t i
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
     std::vector<int> Hs(B, H), Ws(B, W);
     return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, d_rgb, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ transcode
+// total and max_container of the plan a call on (sizes, ME, Ms) would use: the cached plan's, or a host-only build -- so that a call can refuse
+// a short workspace before it takes a plan (a new plan's tables are uploaded, and may allocate a block)
+static void plan_need(llicti_ctx *c, int B, const int *Hs, const int *Ws, int ME, const int *Ms, size_t *total, size_t *max_container)
+{
+    auto it = c->plans.find(plan_key(c, B, Hs, Ws, nullptr, ME, Ms));
+    if (it != c->plans.end()) { *total = it->second->p.total; *max_container = it->second->p.max_container; return; }
+    Plan p;
+    build_plan(p, B, Hs, Ws, nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms, c->nlev);
+    *total = p.total; *max_container = p.max_container;
+}
+
+extern "C" size_t llicti_transcode_workspace_bytes(const llicti_ctx *c, int B, const int *Hs, const int *Ws, const int *src_modes, int n_src,
+                                                   const int *dst_modes, int n_dst)
+{
+    return plan_transcode_workspace_bytes(B, Hs, Ws, src_modes, n_src, dst_modes, n_dst, c ? c->nlev : LLICTI_NLEVELS);
+}
+
+extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len_in,
+                                       int B, const int *Hs, const int *Ws, const int *src_modes, int n_src, const int *dst_modes, int n_dst,
+                                       void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len_out, void *stream)
+{
+    if (!c || !d_in || !d_seg_len_in || !d_workspace || !d_out || !d_seg_len_out) return fail(LLICTI_EINVAL, "transcode_images: null pointer");
+    if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
+    int MEs = 0, MEd = 0;
+    std::vector<int> Mss, Msd;
+    if (int rc = resolve_modes("transcode_images (source)", src_modes, n_src, B, &MEs, Mss)) return rc;
+    if (int rc = check_model(c, "transcode_images (source)", MEs, Mss)) return rc;
+    bool src_auto = (MEs & 0x1000) != 0;
+    for (int m : Mss) src_auto = src_auto || (m & 0x1000);
+    if (src_auto) return fail(LLICTI_EINVAL, "transcode_images: LLICTI_MODE_RANS_X_AUTO is an encoder's mode -- a source container says how many streams it has (header: llicti_header_mode)");
+    if (int rc = resolve_modes("transcode_images (target)", dst_modes, n_dst, B, &MEd, Msd)) return rc;
+    if (int rc = check_model(c, "transcode_images (target)", MEd, Msd)) return rc;
+    bool mixed = c->force_ragged != 0;
+    for (int b = 1; b < B; ++b) mixed = mixed || Hs[b] != Hs[0] || Ws[b] != Ws[0];
+    if (mixed && ((MEs & 0xFF) == 0 || (MEd & 0xFF) == 0))
+        return fail(LLICTI_EINVAL, "transcode_images: a batch of mixed sizes needs rANS containers on both sides (the reference-format container codes equal sizes per call)");
+    for (int b = 0; b < B; ++b) {
+        const Geom gl = make_geom(1, Hs[b], Ws[b], c->nlev - 1);
+        if (c->nlev < LLICTI_NLEVELS && (gl.h > 255 || gl.w > 255))
+            return fail(LLICTI_EINVAL, "transcode_images: image %d is %dx%d; a %d-level model's header stores its level-%d grid (%dx%d) in one byte each "
+                        "(at most %d pixels per side)", b, Ws[b], Hs[b], c->nlev, c->nlev - 1, gl.w, gl.h, 255 << c->nlev);
+        const size_t hdr = 17 + 3 * (size_t)gl.h * gl.w;
+        if (in_stride < hdr)
+            return fail(LLICTI_EINVAL, "transcode_images: in_stride %zu is smaller than the %zu header bytes of a %dx%d image", in_stride, hdr, Ws[b], Hs[b]);
+    }
+    {
+        const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)B * in_stride, o0 = (uintptr_t)d_out, o1 = o0 + (size_t)B * out_stride;
+        if (i0 < o1 && o0 < i1) return fail(LLICTI_EINVAL, "transcode_images: d_out overlaps d_in");
+    }
+    for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
+    DeviceGuard guard(c);
+    hipStream_t s = (hipStream_t)stream;
+    const int *ms_src = Mss.empty() ? nullptr : Mss.data(), *ms_dst = Msd.empty() ? nullptr : Msd.data();
+    {
+        size_t tot_s = 0, tot_d = 0, mc_s = 0, mc_d = 0;
+        plan_need(c, B, Hs, Ws, MEs, ms_src, &tot_s, &mc_s);
+        plan_need(c, B, Hs, Ws, MEd, ms_dst, &tot_d, &mc_d);
+        const size_t need = align_up(tot_s, 256) + tot_d;
+        if (workspace_bytes < need) return fail(LLICTI_ENOSPACE, "transcode_images: workspace %zu < %zu", workspace_bytes, need);
+        if (out_stride < mc_d) return fail(LLICTI_ENOSPACE, "transcode_images: out_stride %zu < %zu", out_stride, mc_d);
+    }
+    PlanDev *pds = nullptr, *pdd = nullptr;
+    if (int rc = get_plan(c, B, Hs, Ws, nullptr, MEs, ms_src, s, &pds)) return rc;
+    PlanUse use_src{ pds, s };
+    if (int rc = get_plan(c, B, Hs, Ws, nullptr, MEd, ms_dst, s, &pdd)) return rc;      // (the source plan is the most recently used one: it stays cached)
+    PlanUse use_dst{ pdd, s };
+    const Plan &ps = pds->p, &pt = pdd->p;
+    if (!transcode_plans_agree(ps, pt)) return fail(LLICTI_EINVAL, "transcode_images: the two plans place the planes differently");
+    const TranscodeLayout lay = transcode_layout(ps, pt);
+    if (workspace_bytes < lay.total) return fail(LLICTI_ENOSPACE, "transcode_images: workspace %zu < %zu", workspace_bytes, lay.total);
+    uint8_t *ws = (uint8_t *)d_workspace;
+    const TranscodeTarget tc{ pdd, ws + lay.off_dst };
+
+    c->img_status_n = 0;
+    if (c->img_status_cap < B) {          // grows rarely (a larger batch than any before): blocking is fine here
+        ++c->n_device_sync; ++c->n_device_alloc;
+        HIPCHK(hipDeviceSynchronize());
+        if (c->d_img_status) { (void)hipFree(c->d_img_status); c->d_img_status = nullptr; c->img_status_cap = 0; }
+        const int cap = std::max(B, 64);
+        HIPCHK(hipMalloc(&c->d_img_status, (size_t)cap * sizeof(int32_t)));
+        c->img_status_cap = cap;
+    }
+    CallScope call(c, s);
+    if (int rc = decode_stages(c, pds, d_in, in_stride, d_seg_len_in, ws, nullptr, s, 0, &tc)) return rc;
+    const int16_t *planes = (const int16_t *)(ws + ps.off_planes);
+    const int32_t *mm = (const int32_t *)(ws + ps.off_minmax);
+    int32_t *status_dst = (int32_t *)(tc.ws + pt.off_status);
+    {
+        ProfSpan span(c, PROF_MISC, s);
+        unsigned long long *ssum0 = (pt.ME & 0x1000) ? (unsigned long long *)(tc.ws + pt.off_rpos) : nullptr;
+        header_transcode_kernel<<<B, 256, 0, s>>>(planes, mm, pdd->dev<ImgGeo>(pt.d_img), d_out, (long)out_stride, d_seg_len_out, ssum0, status_dst, kStatusHead + B);
+    }
+    if (int rc = encode_back_end(c, pdd, tc.ws, planes, mm, d_out, out_stride, d_seg_len_out, s)) return rc;
+    {
+        ProfSpan span(c, PROF_MISC, s);
+        transcode_latch_kernel<<<(B * LLICTI_NSEG + 255) / 256, 256, 0, s>>>((const int32_t *)(ws + ps.off_status), status_dst, c->d_status, c->d_img_status, B, d_seg_len_out);
+    }
+    HIPCHK(hipGetLastError());
+    c->img_status_n = B;
+    return LLICTI_OK;
 }
 
 extern "C" int llicti_check_status(llicti_ctx *c, void *stream)

@@ -332,16 +332,10 @@ class LLICTI(nn.Module):
             return [flat[int(o):int(o) + 3 * h * w].view(1, 3, h, w).to(torch.float32) / 255 for o, h, w in zip(offs, Hs, Ws)]
         return res.to(torch.float32) / 255           # LLICTI_nets.py:87
 
-    @torch.no_grad()
-    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0, pixels=None):
-        """bytestream_lists of B images -> uint8 [B,3,H,W] on the device, enqueued (upload from a pinned buffer + decode); device-side
-        failures are reported by codec().check() / image_status().  The images of a call share a container kind; in a rANS container their
-        SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each.
-        reduce = r: every image at 1 / 2^r (decompres()); H, W, Hs, Ws of the result are the REDUCED sizes.  (The pinned staging buffers hold the
-        call's INPUT -- containers and segment lengths, sized by the full image -- so a reduced and a full decode share them safely.)
-        pixels = "rgb" | "bgr" | "rgba" | "bgra": the result is a LIST of B uint8 device tensors [H_b, W_b, 3 | 4], interleaved (alpha 255), written
-        in that layout by the decode's last kernel (HipCodec.decode_px) -- views of one flat buffer, the images back to back; with flat=True
-        (that flat buffer, Hs, Ws) instead."""
+    def _upload_lists(self, lists, devc=None, slot=0):
+        """bytestream_lists of B images -> their containers and segment lengths on the device (one upload from the pinned staging buffers, on the copy
+        stream; the compute stream waits for it): (codec, containers [B, stride], seg_len [B, 49], Hs, Ws, mode -- one int or one per image, read from
+        the headers --, mixed)."""
         codec = self.codec(devc if (devc is not None and torch.device(devc).type == "cuda") else None)
         Hs, Ws, modes = [], [], []
         for bl in lists:
@@ -388,6 +382,52 @@ class LLICTI(nn.Module):
         cur.wait_stream(up)
         cont_d.record_stream(cur)
         seg_d.record_stream(cur)
+        return codec, cont_d, seg_d, Hs, Ws, mode, mixed
+
+    @torch.no_grad()
+    def transcode_batch(self, lists, container=None, devc=None, slot=0):
+        """bytestream_lists of B images -> their bytestream_lists in `container` ("ac", "rans<M>", "wrans<M>", "xrans<M>", "auto"; default: the
+        model's set_container value), each what compress() of the decoded image gives in that container -- without decoding to pixels and coding
+        again: one pass of the band CNN instead of two (HipCodec.transcode).  The source containers' kinds and the sizes are read from the
+        headers as decode_batch_async does; "auto" gives every image the mode of its size (auto_modes).  Synchronous; device-side failures
+        (a malformed source container) raise through codec().check()."""
+        codec, cont_d, seg_d, Hs, Ws, src_mode, _ = self._upload_lists(lists, devc, slot)
+        name = self.container if container is None else str(container)
+        B = len(lists)
+        if name == "auto":
+            modes = auto_modes(list(zip(Hs, Ws)), self.num_scales)
+            dst_mode = modes[0] if all(m == modes[0] for m in modes) else modes
+        else:
+            dst_mode = mode_of_name(name)
+        cur = torch.cuda.current_stream(codec.device)
+        _, down = self._copy_streams(codec.device)
+        cont, seg = codec.transcode(cont_d, seg_d, Hs, Ws, src_mode, dst_mode)
+        nb = cont.numel()
+        seg_h = self._pinned(("seg", slot), B * NSEG * 4)[:B * NSEG * 4].view(torch.int32).view(B, NSEG)
+        cont_h = self._pinned(("cont_out", slot), nb)[:nb].view(tuple(cont.shape))
+        down.wait_stream(cur)
+        with torch.cuda.stream(down):
+            seg_h.copy_(seg, non_blocking=True)
+            cont_h.copy_(cont, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(down)
+        self._pinned_mark(("seg", slot), down)
+        self._pinned_mark(("cont_out", slot), down)
+        cont.record_stream(down)
+        seg.record_stream(down)
+        return EncodedBatch(codec, None, cont_h, seg_h, ev, None, dst_mode, Hs, Ws).lists()
+
+    @torch.no_grad()
+    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0, pixels=None):
+        """bytestream_lists of B images -> uint8 [B,3,H,W] on the device, enqueued (upload from a pinned buffer + decode); device-side
+        failures are reported by codec().check() / image_status().  The images of a call share a container kind; in a rANS container their
+        SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each.
+        reduce = r: every image at 1 / 2^r (decompres()); H, W, Hs, Ws of the result are the REDUCED sizes.  (The pinned staging buffers hold the
+        call's INPUT -- containers and segment lengths, sized by the full image -- so a reduced and a full decode share them safely.)
+        pixels = "rgb" | "bgr" | "rgba" | "bgra": the result is a LIST of B uint8 device tensors [H_b, W_b, 3 | 4], interleaved (alpha 255), written
+        in that layout by the decode's last kernel (HipCodec.decode_px) -- views of one flat buffer, the images back to back; with flat=True
+        (that flat buffer, Hs, Ws) instead."""
+        codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
         if pixels is not None:
             bpp = pixel_bytes(pixels)
             out = codec.decode_px(cont_d, seg_d, Hs, Ws, mode, pixels, reduce=reduce)
