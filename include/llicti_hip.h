@@ -297,6 +297,47 @@ int llicti_decode_images_px(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stri
                             void *d_workspace, size_t workspace_bytes,
                             uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream);
 
+/* FLOAT TENSORS: decode straight into the dense, normalised, cropped batch tensor a network is fed with, and encode from planar float32 in
+ * {k/255} (the reference's compress() input) -- the unlift is the last kernel of a decode, the lift the first of an encode, so no conversion,
+ * crop, flip, normalise or stack pass runs around the call and a batch of MIXED sizes comes out as one uniform tensor.
+ *   d_out     ONE dense planar tensor [B][3][Ho][Wo] of `dtype` (LLICTI_T_*), channels R, G, B; nothing outside
+ *             [d_out, d_out + B * 3 * Ho * Wo * llicti_tensor_elem_bytes(dtype)) is written.  Stores are 4 elements wide when Wo % 4 == 0 and d_out
+ *             is aligned to 4 elements, element by element otherwise
+ *   y0, x0    host arrays of B window origins in the coordinates of the decoded image -- the REDUCED one for reduce >= 1 (llicti_reduced_dims:
+ *             Hr x Wr); NULL = 0.  Image b's window must lie inside it: 0 <= y0[b], y0[b] + Ho <= Hr, 0 <= x0[b], x0[b] + Wo <= Wr
+ *             (llicti_tensor_window_ok).  No padding, no resampling
+ *   flip      host array of B flags, NULL = none: a set flag mirrors the window, output column j is window column Wo - 1 - j
+ *   mean, std host arrays of 3 floats (R, G, B); both NULL = no normalisation
+ * ARITHMETIC, to the operation (torchvision's ToTensor + Normalize on the CPU, bit for bit): x = (float)v / 255.0f, one IEEE fp32 division; with
+ * mean and std y = (x - mean[c]) / std[c], one rounded fp32 subtraction and one correctly rounded fp32 division (no reciprocal, no contraction);
+ * LLICTI_T_F16 / LLICTI_T_BF16 round that fp32 value to nearest even.
+ * THE WINDOWS ARE PER CALL, NOT PER PLAN: origins and flips travel as kernel arguments, so the plan of the call is the one
+ * llicti_decode_images_reduced builds for the same sizes, modes and reduce with tight placement -- a loop that draws new crops and flips for
+ * every batch hits that one cached plan and neither synchronises the device nor allocates.  Same launches, status words and integrity rule as
+ * llicti_decode_images_reduced; the tensor is written by the call's last kernel.
+ * LLICTI_EINVAL before anything is launched, naming the image: an unknown dtype, Ho or Wo < 1, a window that leaves its image, exactly one of
+ * mean / std NULL, a std that is zero, negative or not finite, a null pointer the call needs, and whatever llicti_decode_images_reduced refuses. */
+#define LLICTI_T_F32 0
+#define LLICTI_T_F16 1
+#define LLICTI_T_BF16 2
+/* Host helpers (no device needed): bytes per element of a dtype (0: unknown dtype), and whether an Ho x Wo window at (y0, x0) lies inside an
+ * H x W image decoded at `reduce` (1 / 0; 0 for H, W, Ho or Wo < 1 or a reduce outside 0 .. LLICTI_NLEVELS). */
+int llicti_tensor_elem_bytes(int dtype);
+int llicti_tensor_window_ok(int H, int W, int reduce, int y0, int x0, int Ho, int Wo);
+int llicti_decode_images_tensor(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                void *d_workspace, size_t workspace_bytes,
+                                void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
+                                const float *mean, const float *std, void *stream);
+/* llicti_encode_images_vm on planar float32: image b's [3][Hs[b]][Ws[b]] block at ELEMENT offset x_off[b] of d_x (NULL = the blocks back to back
+ * in call order).  A sample x becomes the pixel value v = (int)rintf(x * 255.0f) -- one rounded fp32 product, rounded half to even
+ * (torch.round) --, clamped to 0 .. 255, a NaN gives 0; containers and segment lengths are byte for byte those of the uint8 call on v, under
+ * every rule of that call.  Loads are 4 floats wide when d_x, the offsets and the plane sizes allow.  float32 is the only input type (bfloat16
+ * cannot hold k/255). */
+int llicti_encode_images_f32(llicti_ctx *ctx, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,
+                             void *d_workspace, size_t workspace_bytes,
+                             uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream);
+
 /* TRANSCODE: containers of one kind into containers of another, on the device, at the cost of ONE decode.  Image b's output container and its 49
  * segment lengths are byte for byte what llicti_encode_images_vm (B = 1) writes, in dst_modes[b], for the pixels container b decodes to -- without
  * the pixels ever being made: behind each (level, band) stage of the decoder the stage's CNN outputs and symbols become the encoder's

@@ -73,6 +73,10 @@ _SIGS = {
     "llicti_pixel_span": (_sz, [_i, _i, _i, _sz]),
     "llicti_encode_images_px": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images_px": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
+    "llicti_tensor_elem_bytes": (_i, [_i]),
+    "llicti_tensor_window_ok": (_i, [_i] * 7),
+    "llicti_decode_images_tensor": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "llicti_encode_images_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_transcode_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
     "llicti_transcode_images": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp, _vp]),

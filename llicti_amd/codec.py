@@ -258,6 +258,24 @@ def pixel_span(fmt, H, W, pitch=0) -> int:
     return n
 
 
+# Element types of decode_tensor's output (LLICTI_T_*)
+T_F32, T_F16, T_BF16 = 0, 1, 2
+TENSOR_DTYPES = {torch.float32: T_F32, torch.float16: T_F16, torch.bfloat16: T_BF16}
+
+
+def tensor_elem_bytes(dtype) -> int:
+    """Bytes per element of a decode_tensor dtype (a torch dtype or LLICTI_T_*; llicti_tensor_elem_bytes, works without a device)."""
+    n = int(_lib.lib().llicti_tensor_elem_bytes(int(TENSOR_DTYPES.get(dtype, dtype))))
+    if n == 0:
+        raise ValueError(f"unknown tensor dtype {dtype!r} (torch.float32, torch.float16, torch.bfloat16)")
+    return n
+
+
+def tensor_window_ok(H, W, reduce, y0, x0, Ho, Wo) -> bool:
+    """Whether an Ho x Wo window at (y0, x0) lies inside an H x W image decoded at `reduce` (llicti_tensor_window_ok, works without a device)."""
+    return bool(_lib.lib().llicti_tensor_window_ok(int(H), int(W), int(reduce), int(y0), int(x0), int(Ho), int(Wo)))
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -642,6 +660,65 @@ class HipCodec:
             _lib.check(self.L.llicti_decode_images_vm(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws), _ptr(per),
                                                       _ptr(ws), ws.numel(), _ptr(out), None, _stream_ptr(self.device)))
         return out
+
+    # ---- float tensors (llicti_decode_images_tensor / llicti_encode_images_f32): the batch tensor a network is fed with, planar float32 in
+    def decode_tensor(self, containers, seg_len, Hs, Ws, mode, size, dtype=torch.float32, origin=None, flip=None, mean=None, std=None, reduce=0, out=None):
+        """device containers of B images of FULL sizes Hs[b] x Ws[b] (they may differ) -> ONE device tensor [B, 3, Ho, Wo] of `dtype` (float32,
+        float16, bfloat16), written by the decode's last kernel, async.  size = (Ho, Wo); origin = (y0s, x0s): every image's window origin in the
+        decoded image (the reduced one for reduce >= 1; None: 0) -- the window must lie inside the image, nothing is padded or resampled;
+        flip: B flags, a set one mirrors that window left to right; mean, std: 3 floats each (both or neither).  The values are those of
+        torchvision's ToTensor + Normalize on the CPU, bit for bit: v / 255 (one fp32 division), then (x - mean[c]) / std[c], then dtype's
+        round-to-nearest-even.  Origins and flips are per-call data: calls that differ only in them share one cached plan.  `out`: a contiguous
+        [B, 3, Ho, Wo] tensor of that dtype to write into (nothing outside it is touched).  reduce as decode_reduced."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.shape[0] == B
+        Ho, Wo = int(size[0]), int(size[1])
+        dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
+        tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
+        ws = self.workspace_v(Hs, Ws, mode)
+        if out is None:
+            out = torch.empty((B, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= B * 3 * Ho * Wo
+        y0 = x0 = None
+        if origin is not None:
+            y0, x0 = (np.ascontiguousarray(v, dtype=np.int32) for v in origin)
+            assert y0.shape == (B,) and x0.shape == (B,)
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        assert fl is None or fl.shape == (B,)
+        mn = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
+        sd = None if std is None else np.ascontiguousarray(std, dtype=np.float32)
+        assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
+        one, per = self._modes_arg(mode, B)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        _lib.check(self.L.llicti_decode_images_tensor(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                                                      _ptr(modes), len(modes), int(reduce), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
+                                                      _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
+        return out
+
+    def encode_f32(self, x_flat, Hs, Ws, mode, x_off=None, out=None, seg_len=None):
+        """encode_v on planar float32: x_flat is a flat float32 device tensor holding image b's [3][Hs[b]][Ws[b]] block at ELEMENT x_off[b] (None:
+        back to back) -> (containers, seg_len), async.  A sample x is the pixel round(x * 255) (half to even, as torch.round), clamped to
+        0 .. 255, NaN -> 0; the bytes are those of encode_v on these pixel values."""
+        assert x_flat.dtype == torch.float32 and x_flat.is_cuda and x_flat.dim() == 1 and x_flat.is_contiguous()
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        sizes = 3 * Hs.astype(np.int64) * Ws.astype(np.int64)
+        offs = None if x_off is None else np.ascontiguousarray(x_off, dtype=np.uint64)
+        assert offs is None or offs.shape == (B,)
+        assert x_flat.numel() >= (int(sizes.sum()) if offs is None else max(int(o) + int(n) for o, n in zip(offs, sizes)))
+        ws = self.workspace_v(Hs, Ws, mode)
+        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
+        if out is None:
+            out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
+        if seg_len is None:
+            seg_len = torch.zeros((B, NSEG), dtype=torch.int32, device=self.device)
+        assert out.shape[1] >= stride
+        one, per = self._modes_arg(mode, B)
+        modes = np.full(B, one, dtype=np.int32) if per is None else per
+        _lib.check(self.L.llicti_encode_images_f32(self.ctx, _ptr(x_flat), _ptr(offs), B, _ptr(Hs), _ptr(Ws), _ptr(modes), _ptr(ws), ws.numel(),
+                                                   _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
+        return out, seg_len
 
     # ---- transcode (llicti_transcode_images): containers of one kind into containers of another at the cost of one decode
     def transcode_workspace(self, Hs, Ws, src_mode, dst_mode):

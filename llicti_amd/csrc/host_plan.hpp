@@ -4,6 +4,7 @@
 // use plus malformed input (tests/sanitize_host.sh, tests/sanitize_host.cpp).  In the HIP build it is part of llicti_hip.hip.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "cnn_pack.hpp"
@@ -446,6 +447,34 @@ static void plan_add_pixels(Plan &p, const std::vector<PixGeo> &pix)
     pixel_key_tail(p.key, pix);
     p.d_pix = p.d_total;
     p.d_total = align_up(p.d_total + p.pix.size() * sizeof(PixGeo), 256);
+}
+
+// Float tensor output (llicti_decode_images_tensor): the output description as the caller gave it ...
+struct TensorArgs { int dtype, Ho, Wo; const int *y0, *x0; const uint8_t *flip; const float *mean, *std; };
+// ... and validated against the call's images (FULL sizes Hs, Ws, decoded at `reduce`): every image's packed window word (tensor_win_pack) and
+// the normalisation constants.  These are the call's kernel arguments -- nothing of them enters the plan or its key.
+static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, int reduce, const TensorArgs &t, std::vector<uint32_t> &wins, TensorNorm &nm)
+{
+    if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
+    if (t.Ho < 1 || t.Wo < 1) return fail(LLICTI_EINVAL, "%s: output size %dx%d (need Ho, Wo >= 1)", who, t.Wo, t.Ho);
+    if ((t.mean == nullptr) != (t.std == nullptr)) return fail(LLICTI_EINVAL, "%s: mean and std go together (both, or both NULL)", who);
+    memset(&nm, 0, sizeof nm);
+    if (t.mean) {
+        for (int k = 0; k < 3; ++k) {
+            if (!(t.std[k] > 0.0f) || !std::isfinite(t.std[k])) return fail(LLICTI_EINVAL, "%s: std[%d] = %g (need a finite value above zero)", who, k, (double)t.std[k]);
+            nm.mean[k] = t.mean[k]; nm.std[k] = t.std[k];
+        }
+        nm.on = 1;
+    }
+    wins.assign(B, 0u);
+    for (int b = 0; b < B; ++b) {
+        const int y0 = t.y0 ? t.y0[b] : 0, x0 = t.x0 ? t.x0[b] : 0;
+        if (!tensor_window_ok(Hs[b], Ws[b], reduce, y0, x0, t.Ho, t.Wo))
+            return fail(LLICTI_EINVAL, "%s: the %dx%d window at (y %d, x %d) leaves image %d (%dx%d at reduce %d)", who, t.Wo, t.Ho, y0, x0, b,
+                        reduced_dim(Ws[b], reduce), reduced_dim(Hs[b], reduce), reduce);
+        wins[b] = tensor_win_pack(y0, x0, t.flip && t.flip[b]);
+    }
+    return 0;
 }
 
 // mode: 0 = AC container (torchac-compatible, the reference's format); 0x100 | M = rANS container (v3) with M

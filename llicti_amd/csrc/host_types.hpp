@@ -75,6 +75,20 @@ struct PixGeo {
 };
 LLICTI_HD int pix_bpp(int fmt) { return 3 + (fmt >> 1); }            // of a VALID format (host: pix_format_bytes checks)
 LLICTI_HD bool pix_bgr(int fmt) { return (fmt & 1) != 0; }
+// Float tensor output (llicti_decode_images_tensor).  The windows of a call -- origin and flip flag of every image -- are PER CALL data: a
+// training loop draws new ones for every batch, so they are no part of the plan (a plan per call would thrash the cache) but KERNEL ARGUMENTS
+// of unlift_tensor_kernel: one packed word per image, kTensorWinMax images per launch (a larger batch takes several launches).
+constexpr int kTensorWinMax = 256;
+struct TensorWins { uint32_t w[kTensorWinMax]; };                    // y0 | x0 << 13 | flip << 26 (origins are below 8160 < 2^13)
+struct TensorNorm { float mean[3], std[3]; int on; };                // on = 0: no normalisation
+LLICTI_HD uint32_t tensor_win_pack(int y0, int x0, bool flip) { return (uint32_t)y0 | ((uint32_t)x0 << 13) | ((flip ? 1u : 0u) << 26); }
+LLICTI_HD int tensor_elem_bytes(int dtype) { return dtype == LLICTI_T_F32 ? 4 : (dtype == LLICTI_T_F16 || dtype == LLICTI_T_BF16) ? 2 : 0; }
+// an Ho x Wo window at (y0, x0) of an H x W image decoded at reduce r lies inside it
+LLICTI_HD bool tensor_window_ok(int H, int W, int r, int y0, int x0, int Ho, int Wo)
+{
+    if (H < 1 || W < 1 || r < 0 || r > LLICTI_NLEVELS || Ho < 1 || Wo < 1 || y0 < 0 || x0 < 0) return false;
+    return (long)y0 + Ho <= reduced_dim(H, r) && (long)x0 + Wo <= reduced_dim(W, r);
+}
 static Geom make_geom(int B, int H, int W, int lvl)
 {
     Geom g;

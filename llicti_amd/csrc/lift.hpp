@@ -341,3 +341,177 @@ __global__ __launch_bounds__(256) void unlift_px_kernel(const int16_t *__restric
     if (pix_bpp(fmt) == 4) unlift_px_rows<4>(src, plane, W, r, Ho, Wo, dst, pitch, pix_bgr(fmt));
     else unlift_px_rows<3>(src, plane, W, r, Ho, Wo, dst, pitch, pix_bgr(fmt));
 }
+
+// ------------------------------------------------------------------------------------------------ float tensors
+// llicti_encode_images_f32 / llicti_decode_images_tensor: planar float32 in {k/255} on the way in, the dense [B][3][Ho][Wo] tensor a network is
+// fed with on the way out.  The arithmetic is specified to the operation (include/llicti_hip.h) so that both ends are held EXACTLY against
+// PyTorch on the CPU: one rounded product and a half-to-even rounding in, one IEEE division (and, normalised, one rounded subtraction and one
+// correctly rounded division) out; -ffp-contract=off, no reciprocal anywhere.
+
+// the pixel value of a float sample: round(x * 255) half to even, clamped to 0 .. 255; a NaN compares false and gives 0
+__device__ __forceinline__ int f32_pixel(float x)
+{
+    const float t = rintf(__fmul_rn(x, 255.0f));
+    return (t >= 0.0f) ? (int)fminf(t, 255.0f) : 0;
+}
+
+// lift_kernel on planar float32 (image b's [3][H][W] block at ELEMENT iv[b].rgb_off of x): every sample becomes its pixel value first, then
+// lift_kernel's arithmetic to the letter -- int16 planes, float planes, min / max partials, clearing of the call's status words.
+template <int VEC>
+__global__ __launch_bounds__(256) void lift_f32_kernel(const float *__restrict__ x, int16_t *__restrict__ planes, float *__restrict__ fplanes,
+                                                       int32_t *__restrict__ part, int32_t *__restrict__ zero, int n_zero,
+                                                       const ImgGeo *__restrict__ iv)
+{
+    const int b = blockIdx.y;
+    if (zero && blockIdx.x == 0 && b == 0)
+        for (int i = threadIdx.x; i < n_zero; i += blockDim.x) zero[i] = 0;
+    const long plane = iv[b].plane;
+    const float *src = x + iv[b].rgb_off;
+    int16_t *dst = planes + iv[b].pix_off;
+    float *fdst = fplanes + iv[b].pix_off;
+    int mnCo = 32767, mnCg = 32767, mxCo = -32768, mxCg = -32768;
+    for (long p = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC; p < plane; p += (long)gridDim.x * blockDim.x * VEC) {
+        int r[VEC], gch[VEC], bl[VEC];
+        if constexpr (VEC == 4) {
+            const float4 a = *reinterpret_cast<const float4 *>(src + p);
+            const float4 c = *reinterpret_cast<const float4 *>(src + plane + p);
+            const float4 d = *reinterpret_cast<const float4 *>(src + 2 * plane + p);
+            r[0] = f32_pixel(a.x); r[1] = f32_pixel(a.y); r[2] = f32_pixel(a.z); r[3] = f32_pixel(a.w);
+            gch[0] = f32_pixel(c.x); gch[1] = f32_pixel(c.y); gch[2] = f32_pixel(c.z); gch[3] = f32_pixel(c.w);
+            bl[0] = f32_pixel(d.x); bl[1] = f32_pixel(d.y); bl[2] = f32_pixel(d.z); bl[3] = f32_pixel(d.w);
+        } else {
+            r[0] = f32_pixel(src[p]); gch[0] = f32_pixel(src[plane + p]); bl[0] = f32_pixel(src[2 * plane + p]);
+        }
+        short y[VEC], co[VEC], cg[VEC];
+        float fy[VEC], fco[VEC], fcg[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const int R = r[k], G = gch[k], Bl = bl[k];
+            const int Co = R - Bl;
+            const int t = Bl + (Co >> 1);        // (lift_kernel's arithmetic, to the letter)
+            const int Cg = G - t;
+            const int Y = t + (Cg >> 1) - 127;
+            y[k] = (short)Y; co[k] = (short)Co; cg[k] = (short)Cg;
+            fy[k] = (float)Y / 255.0f; fco[k] = (float)Co / 255.0f; fcg[k] = (float)Cg / 255.0f;
+            mnCo = min(mnCo, Co); mxCo = max(mxCo, Co); mnCg = min(mnCg, Cg); mxCg = max(mxCg, Cg);
+        }
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<short4 *>(dst + p) = make_short4(y[0], y[1], y[2], y[3]);
+            *reinterpret_cast<short4 *>(dst + plane + p) = make_short4(co[0], co[1], co[2], co[3]);
+            *reinterpret_cast<short4 *>(dst + 2 * plane + p) = make_short4(cg[0], cg[1], cg[2], cg[3]);
+            *reinterpret_cast<float4 *>(fdst + p) = make_float4(fy[0], fy[1], fy[2], fy[3]);
+            *reinterpret_cast<float4 *>(fdst + plane + p) = make_float4(fco[0], fco[1], fco[2], fco[3]);
+            *reinterpret_cast<float4 *>(fdst + 2 * plane + p) = make_float4(fcg[0], fcg[1], fcg[2], fcg[3]);
+        } else {
+            dst[p] = y[0]; dst[plane + p] = co[0]; dst[2 * plane + p] = cg[0];
+            fdst[p] = fy[0]; fdst[plane + p] = fco[0]; fdst[2 * plane + p] = fcg[0];
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mnCo = min(mnCo, __shfl_xor(mnCo, o)); mxCo = max(mxCo, __shfl_xor(mxCo, o));
+        mnCg = min(mnCg, __shfl_xor(mnCg, o)); mxCg = max(mxCg, __shfl_xor(mxCg, o));
+    }
+    __shared__ int red[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        const int wv = threadIdx.x >> 6;
+        red[wv][0] = mnCo; red[wv][1] = mnCg; red[wv][2] = mxCo; red[wv][3] = mxCg;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        int v = red[0][k];
+        for (int wv = 1; wv < 4; ++wv) v = (k < 2) ? min(v, red[wv][k]) : max(v, red[wv][k]);
+        part[((long)b * gridDim.x + blockIdx.x) * 4 + k] = v;
+    }
+}
+
+// the element types of the output tensor: float, _Float16, and bfloat16 as its 16 bits
+struct bf16_bits { uint16_t u; };
+template <typename T> __device__ __forceinline__ T tensor_elem(float v);
+template <> __device__ __forceinline__ float tensor_elem<float>(float v) { return v; }
+template <> __device__ __forceinline__ _Float16 tensor_elem<_Float16>(float v) { return (_Float16)v; }      // round to nearest even, subnormals kept
+template <> __device__ __forceinline__ bf16_bits tensor_elem<bf16_bits>(float v)
+{
+    const uint32_t u = __float_as_uint(v);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return bf16_bits{ (uint16_t)0x7FC0 };                                // (a NaN, as torch writes it)
+    return bf16_bits{ (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16) };                                   // round to nearest even
+}
+template <typename T> struct alignas(4 * sizeof(T)) TensorQuad { T e[4]; };
+
+// The last kernel of llicti_decode_images_tensor, in the place of unlift_kernel / unlift_reduced_kernel / unlift_px_kernel: image b's Ho x Wo
+// window (origin and flip: word blockIdx.y of `wins`, the call's kernel arguments -- images b0 .. b0 + gridDim.y - 1 of the batch) through the
+// inverse YCoCg-R into out[b][3][Ho][Wo].  Output pixel (i, j) is the plane pixel ((y0 + i) << r, (x0 + j') << r), j' = Wo - 1 - j where
+// flipped.  A lane owns 4 consecutive output pixels of one row: one 4-element store per channel when Wo % 4 == 0 and `out` is aligned to
+// 4 elements (every row then is), element by element otherwise; short4 plane loads when the window's rows are aligned in unflipped full-size
+// planes.  Latches the call's status words exactly as the other unlift kernels do.
+template <typename T>
+__global__ __launch_bounds__(256) void unlift_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
+                                                            const TensorWins wins, const TensorNorm nm,
+                                                            const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                            int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv)
+{
+    const int b = b0 + blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (b == 0 && status[0] != 0) *latched = status[0];
+        if (img_latched) img_latched[b] = status[status_head + b];
+    }
+    const uint32_t wd = wins.w[blockIdx.y];
+    const int y0 = (int)(wd & 0x1FFFu), x0 = (int)((wd >> 13) & 0x1FFFu);
+    const bool flip = ((wd >> 26) & 1u) != 0;
+    const int W = iv[b].W;
+    const long plane = iv[b].plane, oplane = (long)Ho * Wo;
+    const int16_t *src = planes + iv[b].pix_off;
+    T *dst = out + (long)b * 3 * oplane;
+    const uint32_t Wq = (uint32_t)(Wo + 3) >> 2, units = (uint32_t)Ho * Wq;
+    const bool out_vec = (Wo & 3) == 0 && ((uintptr_t)out & (4 * sizeof(T) - 1)) == 0;
+    const bool src_vec = r == 0 && !flip && ((W | x0) & 3) == 0 && ((uintptr_t)src & 7) == 0;
+    for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
+        const uint32_t i = u / Wq, j = (u - i * Wq) * 4;
+        const int n = min(4, Wo - (int)j);
+        short y[4], co[4], cg[4];
+        if (src_vec && n == 4) {
+            const long p = (long)(y0 + (int)i) * W + (x0 + (int)j);
+            const short4 a = *reinterpret_cast<const short4 *>(src + p);
+            const short4 c = *reinterpret_cast<const short4 *>(src + plane + p);
+            const short4 d = *reinterpret_cast<const short4 *>(src + 2 * plane + p);
+            y[0] = a.x; y[1] = a.y; y[2] = a.z; y[3] = a.w;
+            co[0] = c.x; co[1] = c.y; co[2] = c.z; co[3] = c.w;
+            cg[0] = d.x; cg[1] = d.y; cg[2] = d.z; cg[3] = d.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                y[k] = co[k] = cg[k] = 0;
+                if (k < n) {
+                    const int jw = flip ? Wo - 1 - ((int)j + k) : (int)j + k;
+                    const int16_t *s = src + ((long)((y0 + (int)i) << r) * W + ((long)(x0 + jw) << r));
+                    y[k] = s[0]; co[k] = s[plane]; cg[k] = s[2 * plane];
+                }
+            }
+        }
+        TensorQuad<T> q[3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int Y = y[k] + 127, Co = co[k], Cg = cg[k];
+            const int t = Y - (Cg >> 1);
+            const int G = Cg + t;
+            const int Bl = t - (Co >> 1);
+            const int R = Bl + Co;
+            const int v[3] = { (int)(uint8_t)R, (int)(uint8_t)G, (int)(uint8_t)Bl };
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float f = (float)v[c] / 255.0f;
+                if (nm.on) f = __fdiv_rn(__fsub_rn(f, nm.mean[c]), nm.std[c]);
+                q[c].e[k] = tensor_elem<T>(f);
+            }
+        }
+        T *o = dst + (long)i * Wo + j;
+        if (out_vec) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) *reinterpret_cast<TensorQuad<T> *>(o + c * oplane) = q[c];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) { o[k] = q[0].e[k]; o[oplane + k] = q[1].e[k]; o[2 * oplane + k] = q[2].e[k]; }
+        }
+    }
+}

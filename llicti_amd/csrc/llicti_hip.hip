@@ -5,6 +5,7 @@
 // Kernels (reference call sites in include/llicti_hip.h):
 //   lift_kernel / unlift_kernel       integer YCoCg-R lift, min/max, float planes          (HBM bound)
 //   lift_px_kernel / unlift_px_kernel the same on the caller's interleaved, pitched pixels (RGB8 / BGR8 / RGBA8 / BGRA8) (HBM bound)
+//   lift_f32_kernel / unlift_tensor_kernel  planar float32 in, the dense float / half / bfloat16 batch tensor (crop, flip, normalise) out (HBM bound)
 //   band_params_kernel<BAND>          interpolator CNN: 3 chained fp32-MFMA GEMMs per pixel tile,
 //                                     weights of one 88-channel head resident in LDS        (MFMA bound)
 //   cdf_pairs_kernel                  encoder: the two table entries per symbol (10 erfc)   (VALU)
@@ -410,6 +411,22 @@ static int launch_lift_px(const uint8_t *d_pix, int B, long units, int16_t *plan
     const int gx = (int)std::max<long>(1, std::min<long>(std::min<long>(want, std::max(8, 4096 / B)), kLiftMaxParts / B));
     if ((long)B * gx > kLiftMaxParts) return fail(LLICTI_EINVAL, "lift: batch of %d images exceeds the partials scratch", B);
     lift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(d_pix, planes, fplanes, part, zero, n_zero, iv, pv);
+    minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// launch_lift on planar float32 (llicti_encode_images_f32): image b's block at element iv[b].rgb_off of d_x; plane: the batch's largest H * W
+static int launch_lift_f32(const float *d_x, int B, long plane, bool vec_ok, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part, hipStream_t s,
+                           int32_t *zero, int n_zero, const ImgGeo *iv)
+{
+    // vec_ok: every image's plane size and ELEMENT offset are multiples of 4 (build_plan, on the offsets as given)
+    const bool vec = vec_ok && (((uintptr_t)d_x | (uintptr_t)planes | (uintptr_t)fplanes) % 16 == 0);
+    const long want = vec ? (plane / 4 + 255) / 256 : (plane + 255) / 256;
+    const int gx = (int)std::max<long>(1, std::min<long>(std::min<long>(want, std::max(8, 4096 / B)), kLiftMaxParts / B));
+    if ((long)B * gx > kLiftMaxParts) return fail(LLICTI_EINVAL, "lift: batch of %d images exceeds the partials scratch", B);
+    if (vec) lift_f32_kernel<4><<<dim3(gx, B), 256, 0, s>>>(d_x, planes, fplanes, part, zero, n_zero, iv);
+    else lift_f32_kernel<1><<<dim3(gx, B), 256, 0, s>>>(d_x, planes, fplanes, part, zero, n_zero, iv);
     minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
     HIPCHK(hipGetLastError());
     return 0;
@@ -923,8 +940,10 @@ static int encode_back_end(llicti_ctx *c, PlanDev *pd, uint8_t *ws, const int16_
     return 0;
 }
 
+// f32 (llicti_encode_images_f32): d_rgb is planar float32 and rgb_off counts ELEMENTS -- the plan is the uint8 call's on the same numbers
 static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_off, int B, const int *Hs, const int *Ws, const int *modes, int n_modes,
-                        void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream, const PixArgs *px = nullptr)
+                        void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream, const PixArgs *px = nullptr,
+                        bool f32 = false)
 {
     if (!c || !d_rgb || !d_workspace || !d_out || !d_seg_len) return fail(LLICTI_EINVAL, "encode_images: null pointer");
     if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
@@ -973,6 +992,10 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
             const PixGeo *d_pv = pd->dev<PixGeo>(p.d_pix);
             if (int rc = launch_lift_px(d_rgb, B, p.pix_units, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img, d_pv)) return rc;
             header_write_px_kernel<<<B, 256, 0, s>>>(d_rgb, d_pv, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
+        } else if (f32) {
+            // (the header's raw DC band: the planes just made, back through the integer lift -- the pixel values, without a second conversion)
+            if (int rc = launch_lift_f32((const float *)d_rgb, B, p.max_plane, p.vec_ok, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img)) return rc;
+            header_transcode_kernel<<<B, 256, 0, s>>>(planes, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0, nullptr, 0);
         } else {
             if (int rc = launch_lift(d_rgb, B, p.max_plane, p.vec_ok, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img)) return rc;
             header_write_kernel<<<B, 256, 0, s>>>(d_rgb, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
@@ -1056,12 +1079,15 @@ extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, 
     return encode_batch(c, d_rgb, nullptr, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
 }
 
+// llicti_decode_images_tensor: the validated output description of the call (host_plan.hpp: resolve_tensor) -- kernel arguments of its last kernel
+struct TensorOut { int dtype, Ho, Wo; std::vector<uint32_t> wins; TensorNorm nm; };
+
 // llicti_transcode_images: the target plan of the call and its part of the workspace.  decode_stages then launches cdf_pairs_kernel behind every
 // (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
 struct TranscodeTarget { PlanDev *pd; uint8_t *ws; };
 
 static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
-                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce, const TranscodeTarget *tc = nullptr)
+                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce, const TranscodeTarget *tc = nullptr, const TensorOut *tn = nullptr)
 {
     const Plan &p = pd->p;
     const int B = p.B, M = p.M, Q = p.Q;
@@ -1189,6 +1215,26 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
         }
     }
     if (tc) return 0;      // (no pixels: the caller goes on with the target's header and coder, and latches the status words itself)
+    if (tn) {
+        // float tensor output (llicti_decode_images_tensor), full size or reduced: the windows are this call's kernel arguments, kTensorWinMax
+        // images per launch; every launch latches its own images' status words, the first one the call's
+        const int gxt = (int)std::min<long>(((long)tn->Ho * ((tn->Wo + 3) / 4) + 255) / 256, 1024);
+        ProfSpan span(c, PROF_MISC, s);
+        for (int b0 = 0; b0 < B; b0 += kTensorWinMax) {
+            const int nb = std::min(kTensorWinMax, B - b0);
+            TensorWins tw;
+            memset(&tw, 0, sizeof tw);
+            memcpy(tw.w, tn->wins.data() + b0, (size_t)nb * sizeof(uint32_t));
+#define LLICTI_TENSOR_LAUNCH(T) unlift_tensor_kernel<T><<<dim3(gxt, nb), 256, 0, s>>>(planes, (T *)d_rgb, reduce, tn->Ho, tn->Wo, b0, tw, tn->nm, status, kStatusHead, \
+                                                                                    c->d_status, c->d_img_status, d_img)
+            if (tn->dtype == LLICTI_T_F32) LLICTI_TENSOR_LAUNCH(float);
+            else if (tn->dtype == LLICTI_T_F16) LLICTI_TENSOR_LAUNCH(_Float16);
+            else LLICTI_TENSOR_LAUNCH(bf16_bits);
+#undef LLICTI_TENSOR_LAUNCH
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     if (!p.pix.empty()) {
         // interleaved output (llicti_decode_images_px), full size or reduced: one kernel, the window table behind the others
         const int gxp = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
@@ -1221,7 +1267,7 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
 
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
                         const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0,
-                        const PixArgs *px = nullptr)
+                        const PixArgs *px = nullptr, const TensorArgs *tensor = nullptr)
 {
     if (!c || !d_in || !d_seg_len || !d_workspace || !d_rgb) return fail(LLICTI_EINVAL, "decode_images: null pointer");
     if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
@@ -1235,6 +1281,11 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
         std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes
         for (int b = 0; b < B; ++b) { Hw[b] = reduced_dim(Hs[b], reduce); Ww[b] = reduced_dim(Ws[b], reduce); }
         if (int rc = resolve_pixels("decode_images_px", B, Hw.data(), Ww.data(), px->fmt, px->off, px->pitch, pix)) return rc;
+    }
+    TensorOut tn;
+    if (tensor) {
+        if (int rc = resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, *tensor, tn.wins, tn.nm)) return rc;
+        tn.dtype = tensor->dtype; tn.Ho = tensor->Ho; tn.Wo = tensor->Wo;
     }
     if (ME & 0x1000) return fail(LLICTI_EINVAL, "decode_images: LLICTI_MODE_RANS_X_AUTO is an encoder's mode -- a container says how many streams it has (header: llicti_header_mode)");
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
@@ -1262,7 +1313,7 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
         c->img_status_cap = cap;
     }
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce)) return rc;
+    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce, nullptr, tensor ? &tn : nullptr)) return rc;
     c->img_status_n = B;
     return LLICTI_OK;
 }
@@ -1314,6 +1365,28 @@ extern "C" int llicti_decode_images_px(llicti_ctx *c, const uint8_t *d_in, size_
 {
     const PixArgs px{ format, px_off, pitch };
     return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, d_pix, nullptr, stream, reduce, &px);
+}
+
+extern "C" int llicti_tensor_elem_bytes(int dtype) { return tensor_elem_bytes(dtype); }
+extern "C" int llicti_tensor_window_ok(int H, int W, int reduce, int y0, int x0, int Ho, int Wo) { return tensor_window_ok(H, W, reduce, y0, x0, Ho, Wo) ? 1 : 0; }
+
+// (the plan: rgb_off = nullptr -- llicti_decode_images_reduced's for the same sizes, modes and reduce with tight placement; the windows are
+// kernel arguments, so calls that differ only in them share it)
+extern "C" int llicti_decode_images_tensor(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                           int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                           void *d_workspace, size_t workspace_bytes,
+                                           void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
+                                           const float *mean, const float *std, void *stream)
+{
+    const TensorArgs tensor{ dtype, Ho, Wo, y0, x0, flip, mean, std };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, (uint8_t *)d_out, nullptr, stream, reduce, nullptr, &tensor);
+}
+
+extern "C" int llicti_encode_images_f32(llicti_ctx *c, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,
+                                        void *d_workspace, size_t workspace_bytes,
+                                        uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
+{
+    return encode_batch(c, (const uint8_t *)d_x, x_off, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream, nullptr, true);
 }
 
 extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,

@@ -211,7 +211,12 @@ class LLICTI(nn.Module):
         differ (the reference's test loader yields arbitrary sizes, dataloaders/image_dl.py:40-45): one call, one upload, one download.
         pixels = "rgb" | "bgr" | "rgba" | "bgra": x is a LIST of uint8 host arrays [H_b, W_b, 3 | 4], interleaved as image files, PIL and OpenCV
         hold them -- uploaded as they are and lifted from that layout on the device (HipCodec.encode_px; alpha is ignored): the same containers
-        as the planar list, without a transpose on the host.  EncodedBatch.rgb is then the flat INTERLEAVED device buffer."""
+        as the planar list, without a transpose on the host.  EncodedBatch.rgb is then the flat INTERLEAVED device buffer.
+        pixels = "f32": x is a float32 DEVICE tensor [B,3,H,W] in {k/255}, or a list of such tensors [3,H_b,W_b] (or [1,3,H_b,W_b]) whose sizes may
+        differ; the encode's first kernel reads the floats (HipCodec.encode_f32: round(x * 255) half to even, clamped, as _to_u8) -- no conversion
+        pass, the same containers.  EncodedBatch.rgb is then the flat float32 device buffer."""
+        if pixels == "f32":
+            return self._encode_f32_async(x, slot)
         if pixels is not None and not isinstance(x, (list, tuple)):
             raise ValueError("pixels=...: the batch is a list of uint8 [H, W, C] arrays")
         if isinstance(x, (list, tuple)):
@@ -285,6 +290,44 @@ class LLICTI(nn.Module):
         enc = EncodedBatch(codec, rgb, cont_h, seg_h, ev, x_ycocg, mode, Hs, Ws)
         enc.t0 = t0
         return enc
+
+    def _encode_f32_async(self, x, slot):
+        """encode_batch_async(pixels="f32"): float32 device tensors in, EncodedBatch out."""
+        imgs = list(x) if isinstance(x, (list, tuple)) else [x]
+        if any(not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype != torch.float32 for a in imgs):
+            raise ValueError('a pixels="f32" batch holds float32 device tensors')
+        if isinstance(x, torch.Tensor):
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError('a pixels="f32" tensor is [B, 3, H, W]')
+            B, _, H, W = x.shape
+            Hs, Ws = [H] * B, [W] * B
+            flat = x.contiguous().view(-1)
+        else:
+            imgs = [a[0] if a.dim() == 4 and a.shape[0] == 1 else a for a in imgs]
+            if any(a.dim() != 3 or a.shape[0] != 3 for a in imgs):
+                raise ValueError('a pixels="f32" list holds tensors [3, H, W]')
+            Hs, Ws = [int(a.shape[1]) for a in imgs], [int(a.shape[2]) for a in imgs]
+            flat = torch.cat([a.reshape(-1) for a in imgs])
+            B = len(imgs)
+        codec = self.codec(flat.device)
+        cur = torch.cuda.current_stream(codec.device)
+        _, down = self._copy_streams(codec.device)
+        mode = self.mode_for_batch(B, codec.device, sizes=list(zip(Hs, Ws)))
+        cont, seg = codec.encode_f32(flat, Hs, Ws, mode)
+        nb = cont.numel()
+        seg_h = self._pinned(("seg", slot), B * NSEG * 4)[:B * NSEG * 4].view(torch.int32).view(B, NSEG)
+        cont_h = self._pinned(("cont_out", slot), nb)[:nb].view(tuple(cont.shape))
+        down.wait_stream(cur)
+        with torch.cuda.stream(down):
+            seg_h.copy_(seg, non_blocking=True)
+            cont_h.copy_(cont, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(down)
+        self._pinned_mark(("seg", slot), down)
+        self._pinned_mark(("cont_out", slot), down)
+        cont.record_stream(down)
+        seg.record_stream(down)
+        return EncodedBatch(codec, flat, cont_h, seg_h, ev, None, mode, Hs, Ws)
 
     def _copy_streams(self, device):
         """(upload, download) HIP streams of a device for the batched calls' transfers (created once): PCIe copies next to the kernels, not
@@ -418,7 +461,7 @@ class LLICTI(nn.Module):
         return EncodedBatch(codec, None, cont_h, seg_h, ev, None, dst_mode, Hs, Ws).lists()
 
     @torch.no_grad()
-    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0, pixels=None):
+    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0, pixels=None, tensor=None):
         """bytestream_lists of B images -> uint8 [B,3,H,W] on the device, enqueued (upload from a pinned buffer + decode); device-side
         failures are reported by codec().check() / image_status().  The images of a call share a container kind; in a rANS container their
         SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each.
@@ -426,8 +469,15 @@ class LLICTI(nn.Module):
         call's INPUT -- containers and segment lengths, sized by the full image -- so a reduced and a full decode share them safely.)
         pixels = "rgb" | "bgr" | "rgba" | "bgra": the result is a LIST of B uint8 device tensors [H_b, W_b, 3 | 4], interleaved (alpha 255), written
         in that layout by the decode's last kernel (HipCodec.decode_px) -- views of one flat buffer, the images back to back; with flat=True
-        (that flat buffer, Hs, Ws) instead."""
+        (that flat buffer, Hs, Ws) instead.
+        tensor = dict(size=(Ho, Wo), dtype=, origin=, flip=, mean=, std=) (only size is required): the result is ONE device tensor [B,3,Ho,Wo] of
+        dtype (float32 by default), every image's window cropped, flipped and normalised by the decode's last kernel (HipCodec.decode_tensor) --
+        the images' sizes may differ.  Not together with pixels= or flat=."""
+        if tensor is not None and (pixels is not None or flat):
+            raise ValueError("tensor=... gives one dense float tensor: it goes with neither pixels= nor flat=")
         codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
+        if tensor is not None:
+            return codec.decode_tensor(cont_d, seg_d, Hs, Ws, mode, reduce=reduce, **tensor)
         if pixels is not None:
             bpp = pixel_bytes(pixels)
             out = codec.decode_px(cont_d, seg_d, Hs, Ws, mode, pixels, reduce=reduce)
