@@ -94,6 +94,13 @@ static int pad_int(int H, int W, int nlev = LLICTI_NLEVELS)
     return v;
 }
 
+// Bytes of a container's header: 17 + one raw byte per colour and position of the last level's grid (LLICTI_nets.py:347-350)
+static int header_bytes(int H, int W, int nlev)
+{
+    const Geom g = make_geom(1, H, W, nlev - 1);
+    return 17 + 3 * g.h * g.w;
+}
+
 // Tile height of a band-CNN launch (16, 8 or 4 rows; one wavefront per row, so 16 / 8 / 4 wavefronts per workgroup): the form whose launch is
 // shortest under a two-parameter model of the persistent grid -- rounds = ceil(tiles / workgroups that fit the chip), a round = a fixed part
 // (halo rows, staging the head's weights, barrier) + a part per tile row; the constants are the measured 46 / 25 / 15 us of a band-2
@@ -146,19 +153,47 @@ static TileForm choose_tile_form(int n_cu, int tile_rows, int band, COUNT &&coun
     return f;
 }
 
-// ME: streams per image, | 0x100 for wide (128-lane) streams, | 0x200 for xwide (256-lane) streams -- what mode_streams() returns.
-// Hs, Ws: B sizes; rgb_off: B byte offsets of the images in the caller's RGB buffer, or nullptr = tightly packed in call order.
-// n_cu, tile_rows: the band CNN's tile forms of a mixed-size plan are chosen (and its tile lists written) here.
 static int rans_byte0(int M, int Q, int nlev = LLICTI_NLEVELS);
 static int rans_pad_hi(int M, int Q);
 
-// Ms: B stream counts (rANS containers: the images of a call may have different ones -- every header carries its own -- so that larger images
-// get more streams and a stage launch does not wait for its largest image), each | 0x1000 if that image is "auto" (ME then has 0x1000 if any
-// image is), or nullptr = ME's count and kind for every image.  Fixed and "auto" xwide images may share a call: a fixed one has Mlo = 0.
-// nlev: the model's levels (LLICTI_NLEVELS: config A; kLevelsB: config B).
-static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, int n_cu = 256, int tile_rows = 0, bool force_ragged = false,
-                       const int *Ms = nullptr, int nlev = LLICTI_NLEVELS)
+// What a plan is built from, and nothing else: two calls with equal specs get equal plans.
+struct PlanSpec {
+    int B = 0;
+    const int *Hs = nullptr, *Ws = nullptr;      // B sizes
+    // ME: streams per image, | 0x100 for wide (128-lane) streams, | 0x200 for xwide (256-lane) streams -- what mode_streams() returns.
+    // Ms: B stream counts (rANS containers: the images of a call may have different ones -- every header carries its own -- so that larger images
+    // get more streams and a stage launch does not wait for its largest image), each | 0x1000 if that image is "auto" (ME then has 0x1000 if any
+    // image is), or nullptr = ME's count and kind for every image.  Fixed and "auto" xwide images may share a call: a fixed one has Mlo = 0.
+    int ME = 0;
+    const int *Ms = nullptr;
+    int nlev = LLICTI_NLEVELS;                   // the model's levels (LLICTI_NLEVELS: config A; kLevelsB: config B)
+    bool force_ragged = false;                   // llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries
+    const size_t *rgb_off = nullptr;             // B byte offsets of the images in the caller's RGB buffer, or nullptr = tightly packed in call order
+    int n_cu = 256, tile_rows = 0;               // the band CNN's tile forms of a mixed-size plan are chosen (and its tile lists written) in build_plan
+};
+static const int *modes_ptr(const std::vector<int> &Ms) { return Ms.empty() ? nullptr : Ms.data(); }      // resolve_modes' Ms as PlanSpec::Ms
+
+// The cache key of a full-size planar plan, Plan::key: (ME, B, tile-form tuning, then H, W, rgb offset and stream count per image).  nlev and n_cu are
+// the context's, whose cache it is (llicti_set_model drops the plans); reduced_key_tail and pixel_key_tail follow for the other plan kinds.
+static std::vector<long> plan_key(const PlanSpec &sp)
 {
+    std::vector<long> key;
+    key.reserve(3 + 4 * (size_t)sp.B);
+    key.push_back(sp.ME); key.push_back(sp.B); key.push_back(sp.tile_rows * 2 + (sp.force_ragged ? 1 : 0));
+    long pos = 0;
+    for (int b = 0; b < sp.B; ++b) {
+        key.push_back(sp.Hs[b]); key.push_back(sp.Ws[b]); key.push_back(sp.rgb_off ? (long)sp.rgb_off[b] : pos);
+        key.push_back((sp.Ms && (sp.ME & 0xFF)) ? sp.Ms[b] : (sp.ME & 0xFF));
+        pos += 3L * sp.Hs[b] * sp.Ws[b];
+    }
+    return key;
+}
+
+static void build_plan(Plan &p, const PlanSpec &sp)
+{
+    const int B = sp.B, ME = sp.ME, nlev = sp.nlev, n_cu = sp.n_cu, tile_rows = sp.tile_rows;
+    const int *Hs = sp.Hs, *Ws = sp.Ws, *Ms = sp.Ms;
+    const size_t *rgb_off = sp.rgb_off;
     const int Q = 1 << ((ME >> 8) & 3);
     const bool per_image = Ms && (ME & 0xFF) > 0;
     auto m_of = [&](int b) -> int { return per_image ? (Ms[b] & 0xFF) : (ME & 0xFF); };
@@ -167,7 +202,7 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     int M = 0;
     for (int b = 0; b < B; ++b) M = std::max(M, auto_of(b) ? rans_auto_hi(m_of(b)) : m_of(b));
     p.B = B; p.ME = ME; p.M = M; p.Q = Q; p.nlev = nlev;
-    p.uniform = !force_ragged;
+    p.uniform = !sp.force_ragged;
     for (int b = 1; b < B; ++b) if (Hs[b] != Hs[0] || Ws[b] != Ws[0]) p.uniform = false;
     {
         long pos = 0;
@@ -175,9 +210,7 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
     }
     p.vec_ok = true;
     p.rgb_bytes = 0;
-    p.key.clear();
-    p.key.reserve(3 + 4 * (size_t)B);
-    p.key.push_back(ME); p.key.push_back(B); p.key.push_back(tile_rows * 2 + (force_ragged ? 1 : 0));
+    p.key = plan_key(sp);
     // images: sizes, header constants, placement (mixed sizes: planes / fplanes blocks start at multiples of 64 elements; equal sizes: tightly
     // packed, [B][3][H][W] -- what the division form of the band CNN and the AC container's kernels index)
     p.img.assign(B, ImgGeo{});
@@ -187,7 +220,7 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
         ImgGeo &ig = p.img[b];
         ig.H = Hs[b]; ig.W = Ws[b];
         const Geom g4 = make_geom(1, ig.H, ig.W, nlev - 1);          // the last level's grid: the header's size bytes and the raw DC band
-        ig.h4 = g4.h; ig.w4 = g4.w; ig.hdr_bytes = 17 + 3 * g4.h * g4.w;
+        ig.h4 = g4.h; ig.w4 = g4.w; ig.hdr_bytes = header_bytes(ig.H, ig.W, nlev);
         ig.dcs = 2 << (nlev - 1);
         ig.nseg = model_segments(nlev);
         ig.plane = (long)ig.H * ig.W;
@@ -202,7 +235,6 @@ static void build_plan(Plan &p, int B, const int *Hs, const int *Ws, const size_
         ig.M = auto_of(b) ? rans_auto_hi(ig.Mlo) : m_of(b);
         ig.byte0 = ig.M ? rans_byte0(ig.M, Q, nlev) : nlev;
         ig.padint = pad_int(ig.H, ig.W, nlev) | ((ig.M ? rans_pad_hi(ig.M, Q) : 0) << 10);      // the header's int16 pad field (xwide v4: its high bits carry the stream count; an "auto" encode writes the count it picked)
-        p.key.push_back(ig.H); p.key.push_back(ig.W); p.key.push_back(ig.rgb_off); p.key.push_back(per_image ? Ms[b] : (ME & 0xFF));
     }
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
@@ -549,26 +581,107 @@ static int check_dims_v(int B, const int *Hs, const int *Ws)
         if (Hs[b] < 32 || Ws[b] < 32 || Hs[b] > 8160 || Ws[b] > 8160) return fail(LLICTI_EINVAL, "bad shape of image %d: H=%d W=%d (need 32<=H,W<=8160)", b, Hs[b], Ws[b]);
     return 0;
 }
+// ------------------------------------------------------------------------------------------------ admission
+// What the whole-batch calls refuse before they take a plan, each rule stated once: the entry points (llicti_hip.hip) report the reason, the size
+// queries below turn a refusal into 0 (the reason stays in llicti_last_error).  who: the caller's name, in front of every message.
+//
+// modes: one container mode for the call (n_modes = 1) or one per image (n_modes = B: rANS containers of ONE lane kind whose stream counts may differ,
+// fixed and "auto" xwide counts mixed); -> ME of the call (the lane kind, with the first image's count, | 0x1000 if any image is "auto") and, for
+// per-image modes that differ, Ms (count | 0x1000 for an "auto" image: PlanSpec)
+static int resolve_modes(const char *who, const int *modes, int n_modes, int B, int *ME_out, std::vector<int> &Ms)
+{
+    Ms.clear();
+    if (!modes || (n_modes != 1 && n_modes != B)) return fail(LLICTI_EINVAL, "%s: modes must hold one mode or one per image", who);
+    const int ME0 = mode_streams(modes[0]);
+    if (ME0 < 0) return fail(LLICTI_EINVAL, "%s: unknown mode 0x%x", who, modes[0]);
+    *ME_out = ME0;
+    if (n_modes == 1) return 0;
+    bool differ = false, any_auto = false;
+    for (int b = 0; b < B; ++b) {
+        const int ME = mode_streams(modes[b]);
+        if (ME < 0) return fail(LLICTI_EINVAL, "%s: unknown mode 0x%x of image %d", who, modes[b], b);
+        if (((ME >> 8) & 3) != ((ME0 >> 8) & 3) || ((ME & 0xFF) == 0) != ((ME0 & 0xFF) == 0))
+            return fail(LLICTI_EINVAL, "%s: the images of one call share a container kind (reference format, or rANS streams of one lane count); image %d differs", who, b);
+        Ms.push_back(ME & 0x10FF);
+        differ = differ || ME != ME0;
+        any_auto = any_auto || (ME & 0x1000);
+    }
+    if (!differ) Ms.clear();
+    else if (any_auto) *ME_out |= 0x1000;      // (the call runs the encoder's stream-count pick; images with Mlo = 0 keep their fixed count)
+    return 0;
+}
+// the container modes a model of nlev levels takes (model_takes)
+static int check_model(int nlev, const char *who, int ME, const std::vector<int> &Ms)
+{
+    bool ok = model_takes(nlev, ME);
+    for (int m : Ms) ok = ok && model_takes(nlev, (ME & 0x300) | m);
+    if (!ok)
+        return fail(LLICTI_EINVAL, "%s: a %d-level model (config B) codes the reference-format container or xwide v4 streams, at most %d per image "
+                    "(\"auto\": a size-rule count of at most 13)", who, nlev, 9 * nlev);
+    return 0;
+}
+// a decoder's or a transcode source's modes name containers that exist: no "auto" (resolve_modes sets ME's 0x1000 if any image's mode has it)
+static int check_source_modes(const char *who, const char *container, int ME)
+{
+    if (ME & 0x1000)
+        return fail(LLICTI_EINVAL, "%s: LLICTI_MODE_RANS_X_AUTO is an encoder's mode -- a %s says how many streams it has (header: llicti_header_mode)", who, container);
+    return 0;
+}
+// config B's header stores the last level's grid in one byte per side (config A's sizes, at most 8160, always fit)
+static int check_header_grid(const char *who, int nlev, int B, const int *Hs, const int *Ws)
+{
+    if (nlev >= LLICTI_NLEVELS) return 0;
+    for (int b = 0; b < B; ++b) {
+        const Geom gl = make_geom(1, Hs[b], Ws[b], nlev - 1);
+        if (gl.h > 255 || gl.w > 255)
+            return fail(LLICTI_EINVAL, "%s: image %d is %dx%d; a %d-level model's header stores its level-%d grid (%dx%d) in one byte each "
+                        "(at most %d pixels per side)", who, b, Ws[b], Hs[b], nlev, nlev - 1, gl.w, gl.h, 255 << nlev);
+    }
+    return 0;
+}
+// every container slot of a decode holds at least its image's header
+static int check_in_stride(const char *who, int nlev, int B, const int *Hs, const int *Ws, size_t in_stride)
+{
+    for (int b = 0; b < B; ++b) {
+        const int hdr = header_bytes(Hs[b], Ws[b], nlev);
+        if (in_stride < (size_t)hdr)
+            return fail(LLICTI_EINVAL, "%s: in_stride %zu is smaller than the %d header bytes of a %dx%d image", who, in_stride, hdr, Ws[b], Hs[b]);
+    }
+    return 0;
+}
+// a transcode of images that differ in size (ragged: or that llicti_set_tuning("force_ragged") places as if they did) has no reference-format side
+static int check_transcode_sizes(const char *who, int B, const int *Hs, const int *Ws, int MEs, int MEd, bool ragged)
+{
+    bool mixed = ragged;
+    for (int b = 1; b < B; ++b) mixed = mixed || Hs[b] != Hs[0] || Ws[b] != Ws[0];
+    if (mixed && ((MEs & 0xFF) == 0 || (MEd & 0xFF) == 0))
+        return fail(LLICTI_EINVAL, "%s: a batch of mixed sizes needs rANS containers on both sides (the reference-format container codes equal sizes per call)", who);
+    return 0;
+}
+// Everything llicti_transcode_images refuses on sizes and modes alone -> (MEs, Mss) of the source side, (MEd, Msd) of the target side
+static int admit_transcode(int nlev, bool ragged, int B, const int *Hs, const int *Ws, const int *src_modes, int n_src, const int *dst_modes, int n_dst,
+                           int *MEs, std::vector<int> &Mss, int *MEd, std::vector<int> &Msd)
+{
+    if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
+    if (int rc = resolve_modes("transcode_images (source)", src_modes, n_src, B, MEs, Mss)) return rc;
+    if (int rc = check_model(nlev, "transcode_images (source)", *MEs, Mss)) return rc;
+    if (int rc = check_source_modes("transcode_images", "source container", *MEs)) return rc;
+    if (int rc = resolve_modes("transcode_images (target)", dst_modes, n_dst, B, MEd, Msd)) return rc;
+    if (int rc = check_model(nlev, "transcode_images (target)", *MEd, Msd)) return rc;
+    if (int rc = check_transcode_sizes("transcode_images", B, Hs, Ws, *MEs, *MEd, ragged)) return rc;
+    return check_header_grid("transcode_images", nlev, B, Hs, Ws);
+}
+
+// ------------------------------------------------------------------------------------------------ size queries
 // modes: one mode (n_modes = 1) or one per image (rANS containers of one lane kind, stream counts may differ)
 static size_t plan_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int nlev = LLICTI_NLEVELS)
 {
-    if (check_dims_v(B, Hs, Ws) || !modes || (n_modes != 1 && n_modes != B)) return 0;
-    int ME = mode_streams(modes[0]);
-    if (ME < 0) return 0;
+    int ME = 0;
     std::vector<int> Ms;
-    if (n_modes == B && B > 1) {
-        bool any_auto = false;
-        for (int b = 0; b < B; ++b) {
-            const int MEb = mode_streams(modes[b]);
-            if (MEb < 0 || ((MEb >> 8) & 3) != ((ME >> 8) & 3) || ((MEb & 0xFF) == 0) != ((ME & 0xFF) == 0)) return 0;      // (one lane kind per call; fixed and "auto" counts may mix)
-            Ms.push_back(MEb & 0x10FF);
-            any_auto = any_auto || (MEb & 0x1000);
-        }
-        if (any_auto) ME |= 0x1000;
-    }
+    if (check_dims_v(B, Hs, Ws) || resolve_modes("workspace_bytes", modes, n_modes, B, &ME, Ms)) return 0;
     Plan p, q;
-    build_plan(p, B, Hs, Ws, nullptr, ME, 256, 0, false, Ms.empty() ? nullptr : Ms.data(), nlev);
-    build_plan(q, B, Hs, Ws, nullptr, ME, 256, 0, true, Ms.empty() ? nullptr : Ms.data(), nlev);      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)
+    build_plan(p, PlanSpec{ B, Hs, Ws, ME, modes_ptr(Ms), nlev, false });
+    build_plan(q, PlanSpec{ B, Hs, Ws, ME, modes_ptr(Ms), nlev, true });      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)
     return std::max(p.total, q.total);
 }
 static size_t plan_workspace_bytes_v(int B, const int *Hs, const int *Ws, int mode) { return plan_workspace_bytes_vm(B, Hs, Ws, &mode, 1); }
@@ -581,14 +694,14 @@ static size_t plan_workspace_bytes(int B, int H, int W, int mode)
 static size_t plan_max_container_bytes(int H, int W, int nlev = LLICTI_NLEVELS)
 {
     if (check_dims(1, H, W)) return 0;
-    Plan p, q;
-    build_plan(p, 1, &H, &W, nullptr, 32, 256, 0, false, nullptr, nlev);     // covers the AC container and M <= 32 ...
-    build_plan(q, 1, &H, &W, nullptr, kRansMaxStreams, 256, 0, false, nullptr, nlev);     // ... and the many-stream latency modes (more per-stream slack)
-    Plan a, w, x;
-    build_plan(a, 1, &H, &W, nullptr, 0, 256, 0, false, nullptr, nlev);
-    build_plan(w, 1, &H, &W, nullptr, 14 | 0x100, 256, 0, false, nullptr, nlev);          // ... and wide ...
-    build_plan(x, 1, &H, &W, nullptr, 128 | 0x200, 256, 0, false, nullptr, nlev);         // ... and xwide streams (larger state blocks)
-    return std::max(std::max(std::max(p.max_container, q.max_container), std::max(w.max_container, x.max_container)), a.max_container);
+    // the reference format; M <= 32; the many-stream latency modes (more per-stream slack); wide and xwide streams (larger state blocks)
+    size_t most = 0;
+    for (int ME : { 0, 32, kRansMaxStreams, 14 | 0x100, 128 | 0x200 }) {
+        Plan p;
+        build_plan(p, PlanSpec{ 1, &H, &W, ME, nullptr, nlev });
+        most = std::max(most, p.max_container);
+    }
+    return most;
 }
 
 static int plan_header_dims(const uint8_t *h, int *H, int *W)
@@ -648,57 +761,19 @@ static bool transcode_plans_agree(const Plan &src, const Plan &dst)
     }
     return true;
 }
-// The container modes of one side of a whole-batch call -> ME and, where the images' modes differ, Ms (build_plan's arguments); false: a
-// combination the calls refuse (an unknown mode, mixed lane kinds, the reference format beside a rANS container).
-static bool plan_side_modes(const int *modes, int n_modes, int B, int *ME_out, std::vector<int> &Ms)
-{
-    Ms.clear();
-    if (!modes || (n_modes != 1 && n_modes != B)) return false;
-    int ME = mode_streams(modes[0]);
-    if (ME < 0) return false;
-    if (n_modes == B && B > 1) {
-        bool any_auto = false, differ = false;
-        for (int b = 0; b < B; ++b) {
-            const int MEb = mode_streams(modes[b]);
-            if (MEb < 0 || ((MEb >> 8) & 3) != ((ME >> 8) & 3) || ((MEb & 0xFF) == 0) != ((ME & 0xFF) == 0)) return false;
-            Ms.push_back(MEb & 0x10FF);
-            any_auto = any_auto || (MEb & 0x1000);
-            differ = differ || MEb != ME;
-        }
-        if (!differ) Ms.clear();
-        else if (any_auto) ME |= 0x1000;
-    }
-    *ME_out = ME;
-    return true;
-}
 // Bytes of workspace llicti_transcode_images needs; 0: a combination it refuses (bad sizes or modes, an "auto" mode as the source, mixed lane
 // kinds on a side, a mode the model does not take, the reference format on either side with images of different sizes).
 static size_t plan_transcode_workspace_bytes(int B, const int *Hs, const int *Ws, const int *src_modes, int n_src, const int *dst_modes, int n_dst,
                                              int nlev = LLICTI_NLEVELS)
 {
-    if (check_dims_v(B, Hs, Ws)) return 0;
     int MEs = 0, MEd = 0;
     std::vector<int> Mss, Msd;
-    if (!plan_side_modes(src_modes, n_src, B, &MEs, Mss) || !plan_side_modes(dst_modes, n_dst, B, &MEd, Msd)) return 0;
-    if (MEs & 0x1000) return 0;
-    for (int m : Mss) if (m & 0x1000) return 0;
-    bool ok = model_takes(nlev, MEs) && model_takes(nlev, MEd);
-    for (int m : Mss) ok = ok && model_takes(nlev, (MEs & 0x300) | m);
-    for (int m : Msd) ok = ok && model_takes(nlev, (MEd & 0x300) | m);
-    if (!ok) return 0;
-    bool mixed = false;
-    for (int b = 1; b < B; ++b) mixed = mixed || Hs[b] != Hs[0] || Ws[b] != Ws[0];
-    if (mixed && ((MEs & 0xFF) == 0 || (MEd & 0xFF) == 0)) return 0;
-    if (nlev < LLICTI_NLEVELS)
-        for (int b = 0; b < B; ++b) {
-            const Geom gl = make_geom(1, Hs[b], Ws[b], nlev - 1);
-            if (gl.h > 255 || gl.w > 255) return 0;
-        }
+    if (admit_transcode(nlev, false, B, Hs, Ws, src_modes, n_src, dst_modes, n_dst, &MEs, Mss, &MEd, Msd)) return 0;
     size_t total = 0;
     for (int ragged = 0; ragged < 2; ++ragged) {      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)
         Plan s, d;
-        build_plan(s, B, Hs, Ws, nullptr, MEs, 256, 0, ragged != 0, Mss.empty() ? nullptr : Mss.data(), nlev);
-        build_plan(d, B, Hs, Ws, nullptr, MEd, 256, 0, ragged != 0, Msd.empty() ? nullptr : Msd.data(), nlev);
+        build_plan(s, PlanSpec{ B, Hs, Ws, MEs, modes_ptr(Mss), nlev, ragged != 0 });
+        build_plan(d, PlanSpec{ B, Hs, Ws, MEd, modes_ptr(Msd), nlev, ragged != 0 });
         total = std::max(total, transcode_layout(s, d).total);
     }
     return total;

@@ -176,6 +176,12 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
+// what the context builds a batch's plan from (host_plan.hpp: PlanSpec)
+static PlanSpec ctx_spec(const llicti_ctx *c, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, const int *Ms)
+{
+    return PlanSpec{ B, Hs, Ws, ME, Ms, c->nlev, c->force_ragged != 0, rgb_off, c->n_cu, c->cnn_tile_rows };
+}
+
 extern "C" size_t llicti_workspace_bytes_v(int B, const int *Hs, const int *Ws, int mode) { return plan_workspace_bytes_v(B, Hs, Ws, mode); }
 extern "C" size_t llicti_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes) { return plan_workspace_bytes_vm(B, Hs, Ws, modes, B); }
 extern "C" size_t llicti_workspace_bytes(int B, int H, int W, int mode) { return plan_workspace_bytes(B, H, W, mode); }
@@ -196,6 +202,17 @@ extern "C" int llicti_header_mode(const uint8_t *h, int *mode)
     *mode = ((v >> 8) == 2 ? 0x500 : (v >> 8) == 1 ? 0x300 : 0x100) | (v & 0xFF);
     return LLICTI_OK;
 }
+
+// The 18 forms of the band CNN -- 3 bands x tile rows 16 / 4 / 8 x equal / mixed sizes, in the order of launch_band_params' `form` index -- each as
+// config A's kernel (88-wide heads) and config B's (60-wide heads): one signature, one grid, one tile list.
+typedef void (*BandParamsFn)(const float *, Geom, const float *, float *, int, int, int, const Geom *, const TileRef *);
+struct CnnForm { BandParamsFn fn[2]; int band, TH; };      // fn[0]: 88-wide, fn[1]: 60-wide
+#define LLICTI_CNN_ROW(TH_, RAG) \
+    { { band_params_kernel<0, TH_, RAG>, band_params_h60_kernel<0, TH_, RAG> }, 0, TH_ }, { { band_params_kernel<1, TH_, RAG>, band_params_h60_kernel<1, TH_, RAG> }, 1, TH_ }, \
+    { { band_params_kernel<2, TH_, RAG>, band_params_h60_kernel<2, TH_, RAG> }, 2, TH_ }
+static const CnnForm kCnnForms[18] = { LLICTI_CNN_ROW(kTileHMax, false), LLICTI_CNN_ROW(kTileHSmall, false), LLICTI_CNN_ROW(kTileHMid, false),
+                                       LLICTI_CNN_ROW(kTileHMax, true),  LLICTI_CNN_ROW(kTileHSmall, true),  LLICTI_CNN_ROW(kTileHMid, true) };
+#undef LLICTI_CNN_ROW
 
 extern "C" int llicti_create(llicti_ctx **out, int device)
 {
@@ -233,15 +250,10 @@ extern "C" int llicti_create(llicti_ctx **out, int device)
     for (int k = 0; k < 2; ++k) HIPCHK(hipEventCreateWithFlags(&c->ev_enc[k], hipEventDisableTiming));
     for (int i = 1; i < kMaxSub; ++i) HIPCHK(hipStreamCreateWithFlags(&c->sub[i], hipStreamNonBlocking));
     // the band CNN stages a whole head (up to 86 KB) in LDS
-#define LLICTI_CNN_ATTR(BAND, TH_) \
-    HIPCHK(hipFuncSetAttribute((const void *)band_params_kernel<BAND, TH_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_))); \
-    HIPCHK(hipFuncSetAttribute((const void *)band_params_kernel<BAND, TH_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_))); \
-    HIPCHK(hipFuncSetAttribute((const void *)band_params_h60_kernel<BAND, TH_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_, kHeadB))); \
-    HIPCHK(hipFuncSetAttribute((const void *)band_params_h60_kernel<BAND, TH_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(BAND, TH_, kHeadB)))
-    LLICTI_CNN_ATTR(0, kTileHMax); LLICTI_CNN_ATTR(1, kTileHMax); LLICTI_CNN_ATTR(2, kTileHMax);
-    LLICTI_CNN_ATTR(0, kTileHMid); LLICTI_CNN_ATTR(1, kTileHMid); LLICTI_CNN_ATTR(2, kTileHMid);
-    LLICTI_CNN_ATTR(0, kTileHSmall); LLICTI_CNN_ATTR(1, kTileHSmall); LLICTI_CNN_ATTR(2, kTileHSmall);
-#undef LLICTI_CNN_ATTR
+    for (const CnnForm &f : kCnnForms) {
+        HIPCHK(hipFuncSetAttribute((const void *)f.fn[0], hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(f.band, f.TH)));
+        HIPCHK(hipFuncSetAttribute((const void *)f.fn[1], hipFuncAttributeMaxDynamicSharedMemorySize, cnn_lds_bytes(f.band, f.TH, kHeadB)));
+    }
     *out = c;
     return LLICTI_OK;
 }
@@ -357,7 +369,7 @@ extern "C" int llicti_workspace_planes(llicti_ctx *c, int B, int H, int W, int m
     if (ME < 0) return fail(LLICTI_EINVAL, "workspace_planes: unknown mode 0x%x", mode);
     std::vector<int> Hs(B, H), Ws(B, W);
     Plan p;
-    build_plan(p, B, Hs.data(), Ws.data(), nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, nullptr, c->nlev);
+    build_plan(p, ctx_spec(c, B, Hs.data(), Ws.data(), nullptr, ME, nullptr));
     if (!p.uniform && B > 1) return fail(LLICTI_EINVAL, "workspace_planes: with the tuning switch force_ragged the images of a batch are not tightly packed");
     *off_planes = p.off_planes;
     *off_fplanes = p.off_fplanes;
@@ -386,6 +398,15 @@ extern "C" int llicti_set_profiling(llicti_ctx *c, int enable)
 }
 
 // ------------------------------------------------------------------------------------------------ launches
+// The grid of a lift launch over B images of at most `units` work items (pixels, or 4-pixel pieces): gx workgroups per image, so many that the
+// B * gx partial min/max entries fit the scratch
+static int lift_grid(long units, int B, int *gx)
+{
+    *gx = (int)std::max<long>(1, std::min<long>(std::min<long>((units + 255) / 256, std::max(8, 4096 / B)), kLiftMaxParts / B));
+    if ((long)B * *gx > kLiftMaxParts) return fail(LLICTI_EINVAL, "lift: batch of %d images exceeds the partials scratch", B);
+    return 0;
+}
+
 // part: scratch of kLiftMaxParts x 4 int32 (the workspace's for the whole-batch calls, the context's for llicti_lift_u8)
 static int launch_lift(const uint8_t *d_rgb, int B, long plane, bool vec_ok, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part, hipStream_t s,
                        int32_t *zero = nullptr, int n_zero = 0, const ImgGeo *iv = nullptr)
@@ -393,9 +414,8 @@ static int launch_lift(const uint8_t *d_rgb, int B, long plane, bool vec_ok, int
     // plane: H * W (with a table: of the batch's largest image -- it sizes the grid); vec_ok: every image's plane size and placement allow
     // 4-pixel accesses
     const bool vec = vec_ok && (plane % 4 == 0) && (((uintptr_t)d_rgb | (uintptr_t)planes | (uintptr_t)fplanes) % 16 == 0);
-    const long want = vec ? (plane / 4 + 255) / 256 : (plane + 255) / 256;
-    const int gx = (int)std::max<long>(1, std::min<long>(std::min<long>(want, std::max(8, 4096 / B)), kLiftMaxParts / B));
-    if ((long)B * gx > kLiftMaxParts) return fail(LLICTI_EINVAL, "lift: batch of %d images exceeds the partials scratch", B);
+    int gx;
+    if (int rc = lift_grid(vec ? plane / 4 : plane, B, &gx)) return rc;
     if (vec) lift_kernel<4><<<dim3(gx, B), 256, 0, s>>>(d_rgb, plane, planes, fplanes, part, zero, n_zero, iv);
     else lift_kernel<1><<<dim3(gx, B), 256, 0, s>>>(d_rgb, plane, planes, fplanes, part, zero, n_zero, iv);
     minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
@@ -407,9 +427,8 @@ static int launch_lift(const uint8_t *d_rgb, int B, long plane, bool vec_ok, int
 static int launch_lift_px(const uint8_t *d_pix, int B, long units, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part, hipStream_t s,
                           int32_t *zero, int n_zero, const ImgGeo *iv, const PixGeo *pv)
 {
-    const long want = (units + 255) / 256;
-    const int gx = (int)std::max<long>(1, std::min<long>(std::min<long>(want, std::max(8, 4096 / B)), kLiftMaxParts / B));
-    if ((long)B * gx > kLiftMaxParts) return fail(LLICTI_EINVAL, "lift: batch of %d images exceeds the partials scratch", B);
+    int gx;
+    if (int rc = lift_grid(units, B, &gx)) return rc;
     lift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(d_pix, planes, fplanes, part, zero, n_zero, iv, pv);
     minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
     HIPCHK(hipGetLastError());
@@ -422,43 +441,11 @@ static int launch_lift_f32(const float *d_x, int B, long plane, bool vec_ok, int
 {
     // vec_ok: every image's plane size and ELEMENT offset are multiples of 4 (build_plan, on the offsets as given)
     const bool vec = vec_ok && (((uintptr_t)d_x | (uintptr_t)planes | (uintptr_t)fplanes) % 16 == 0);
-    const long want = vec ? (plane / 4 + 255) / 256 : (plane + 255) / 256;
-    const int gx = (int)std::max<long>(1, std::min<long>(std::min<long>(want, std::max(8, 4096 / B)), kLiftMaxParts / B));
-    if ((long)B * gx > kLiftMaxParts) return fail(LLICTI_EINVAL, "lift: batch of %d images exceeds the partials scratch", B);
+    int gx;
+    if (int rc = lift_grid(vec ? plane / 4 : plane, B, &gx)) return rc;
     if (vec) lift_f32_kernel<4><<<dim3(gx, B), 256, 0, s>>>(d_x, planes, fplanes, part, zero, n_zero, iv);
     else lift_f32_kernel<1><<<dim3(gx, B), 256, 0, s>>>(d_x, planes, fplanes, part, zero, n_zero, iv);
     minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// The band CNN of config B (60-wide heads): the 18 forms of config A's, same grid and tile lists (launch_band_params decides them).
-static int launch_band_params_h60(llicti_ctx *c, const float *fplanes, const Geom &g, int band, float *params, hipStream_t s, const Geom *gv,
-                                  const TileRef *tiles, int form, int gx, int lds_bytes, int tiles_x, int tiles_y, int n_tiles)
-{
-    dim3 grid((unsigned)gx, 4);
-#define LLICTI_CNN_LAUNCH(BAND, TH_, RAG) band_params_h60_kernel<BAND, TH_, RAG><<<grid, 64 * TH_, lds_bytes, s>>>(fplanes, g, c->d_pack[BAND], params, tiles_x, tiles_y, n_tiles, gv, tiles)
-    switch (form) {
-    case 0: LLICTI_CNN_LAUNCH(0, kTileHMax, false); break;
-    case 1: LLICTI_CNN_LAUNCH(1, kTileHMax, false); break;
-    case 2: LLICTI_CNN_LAUNCH(2, kTileHMax, false); break;
-    case 3: LLICTI_CNN_LAUNCH(0, kTileHSmall, false); break;
-    case 4: LLICTI_CNN_LAUNCH(1, kTileHSmall, false); break;
-    case 5: LLICTI_CNN_LAUNCH(2, kTileHSmall, false); break;
-    case 6: LLICTI_CNN_LAUNCH(0, kTileHMid, false); break;
-    case 7: LLICTI_CNN_LAUNCH(1, kTileHMid, false); break;
-    case 8: LLICTI_CNN_LAUNCH(2, kTileHMid, false); break;
-    case 9: LLICTI_CNN_LAUNCH(0, kTileHMax, true); break;
-    case 10: LLICTI_CNN_LAUNCH(1, kTileHMax, true); break;
-    case 11: LLICTI_CNN_LAUNCH(2, kTileHMax, true); break;
-    case 12: LLICTI_CNN_LAUNCH(0, kTileHSmall, true); break;
-    case 13: LLICTI_CNN_LAUNCH(1, kTileHSmall, true); break;
-    case 14: LLICTI_CNN_LAUNCH(2, kTileHSmall, true); break;
-    case 15: LLICTI_CNN_LAUNCH(0, kTileHMid, true); break;
-    case 16: LLICTI_CNN_LAUNCH(1, kTileHMid, true); break;
-    default: LLICTI_CNN_LAUNCH(2, kTileHMid, true); break;
-    }
-#undef LLICTI_CNN_LAUNCH
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -481,33 +468,12 @@ static int launch_band_params(llicti_ctx *c, const float *fplanes, const Geom &g
     if (n_tiles_l > 0x7FFFFFFFL || n_tiles_l < 1) return fail(LLICTI_EINVAL, "band_params: bad tile count");
     const int n_tiles = (int)n_tiles_l;
     const int lds_bytes = cnn_lds_bytes(band, TH, c->head);
-    const int kCnnThreads = 64 * TH;
-    dim3 grid((unsigned)gx, 4);
-    ProfSpan span(c, PROF_CNN, s, g.lvl);
     const int form = band + (TH == kTileHSmall ? 3 : TH == kTileHMid ? 6 : 0) + (tiles ? 9 : 0);
-    if (c->head == kHeadB) return launch_band_params_h60(c, fplanes, g, band, params, s, gv, tiles, form, gx, lds_bytes, tiles_x, tiles_y, n_tiles);
-#define LLICTI_CNN_LAUNCH(BAND, TH_, RAG) band_params_kernel<BAND, TH_, RAG><<<grid, kCnnThreads, lds_bytes, s>>>(fplanes, g, c->d_pack[BAND], params, tiles_x, tiles_y, n_tiles, gv, tiles)
-    switch (form) {
-    case 0: LLICTI_CNN_LAUNCH(0, kTileHMax, false); break;
-    case 1: LLICTI_CNN_LAUNCH(1, kTileHMax, false); break;
-    case 2: LLICTI_CNN_LAUNCH(2, kTileHMax, false); break;
-    case 3: LLICTI_CNN_LAUNCH(0, kTileHSmall, false); break;
-    case 4: LLICTI_CNN_LAUNCH(1, kTileHSmall, false); break;
-    case 5: LLICTI_CNN_LAUNCH(2, kTileHSmall, false); break;
-    case 6: LLICTI_CNN_LAUNCH(0, kTileHMid, false); break;
-    case 7: LLICTI_CNN_LAUNCH(1, kTileHMid, false); break;
-    case 8: LLICTI_CNN_LAUNCH(2, kTileHMid, false); break;
-    case 9: LLICTI_CNN_LAUNCH(0, kTileHMax, true); break;
-    case 10: LLICTI_CNN_LAUNCH(1, kTileHMax, true); break;
-    case 11: LLICTI_CNN_LAUNCH(2, kTileHMax, true); break;
-    case 12: LLICTI_CNN_LAUNCH(0, kTileHSmall, true); break;
-    case 13: LLICTI_CNN_LAUNCH(1, kTileHSmall, true); break;
-    case 14: LLICTI_CNN_LAUNCH(2, kTileHSmall, true); break;
-    case 15: LLICTI_CNN_LAUNCH(0, kTileHMid, true); break;
-    case 16: LLICTI_CNN_LAUNCH(1, kTileHMid, true); break;
-    default: LLICTI_CNN_LAUNCH(2, kTileHMid, true); break;
-    }
-#undef LLICTI_CNN_LAUNCH
+    const CnnForm &f = kCnnForms[form];
+    // (a row of the table that is not this launch's would run a kernel against another band's weight pack: refused here, on the host)
+    if (f.band != band || f.TH != TH) return fail(LLICTI_EINVAL, "band_params: form %d of the table is band %d with %d tile rows, the launch band %d with %d", form, f.band, f.TH, band, TH);
+    ProfSpan span(c, PROF_CNN, s, g.lvl);
+    f.fn[c->head == kHeadB ? 1 : 0]<<<dim3((unsigned)gx, 4), 64 * TH, lds_bytes, s>>>(fplanes, g, c->d_pack[band], params, tiles_x, tiles_y, n_tiles, gv, tiles);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -703,20 +669,6 @@ static int acquire_block(llicti_ctx *c, size_t need, PlanBlock *out)
     return 0;
 }
 
-// the cache key of a full-size planar plan (build_plan writes the same words into Plan::key)
-static std::vector<long> plan_key(const llicti_ctx *c, int B, const int *Hs, const int *Ws, const size_t *rgb_off, int ME, const int *Ms)
-{
-    std::vector<long> key;
-    key.reserve(3 + 4 * (size_t)B);
-    key.push_back(ME); key.push_back(B); key.push_back(c->cnn_tile_rows * 2 + (c->force_ragged ? 1 : 0));
-    long pos = 0;
-    for (int b = 0; b < B; ++b) {
-        key.push_back(Hs[b]); key.push_back(Ws[b]); key.push_back(rgb_off ? (long)rgb_off[b] : pos); key.push_back((Ms && (ME & 0xFF)) ? Ms[b] : (ME & 0xFF));
-        pos += 3L * Hs[b] * Ws[b];
-    }
-    return key;
-}
-
 // The plan of a batch: cached by (mode, sizes, placement).  A miss builds the tables on the host, copies them into a pinned block and
 // enqueues ONE asynchronous upload on the call's stream -- no device synchronisation, no allocation once the pool is warm.
 // reduce >= 1 (llicti_decode_images_reduced): rgb_off places the REDUCED outputs; the plan itself is the batch's full-size one with tight
@@ -729,7 +681,8 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     if (pix) rgb_off = nullptr;
     const size_t *red_off = reduce > 0 ? rgb_off : nullptr;
     if (reduce > 0) rgb_off = nullptr;
-    std::vector<long> key = plan_key(c, B, Hs, Ws, rgb_off, ME, Ms);
+    const PlanSpec sp = ctx_spec(c, B, Hs, Ws, rgb_off, ME, Ms);
+    std::vector<long> key = plan_key(sp);
     if (reduce > 0) reduced_key_tail(key, B, Hs, Ws, reduce, red_off);
     if (pix) pixel_key_tail(key, *pix);
     auto it = c->plans.find(key);
@@ -745,10 +698,9 @@ static int get_plan(llicti_ctx *c, int B, const int *Hs, const int *Ws, const si
     std::unique_ptr<PlanDev> pd(new PlanDev());
     Plan &p = pd->p;
     ++c->n_plan_build;
-    build_plan(p, B, Hs, Ws, rgb_off, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms, c->nlev);
+    build_plan(p, sp);
     if (reduce > 0) plan_add_reduced(p, reduce, red_off);
     if (pix) plan_add_pixels(p, *pix);
-    if (p.key != key) return fail(LLICTI_EINVAL, "plan: key mismatch");
     if (p.rslot_off.size() != (size_t)p.nstreams || p.sref.size() != (size_t)p.nstreams)
         return fail(LLICTI_EINVAL, "plan: stream tables have %zu / %zu entries, expected %d", p.rslot_off.size(), p.sref.size(), p.nstreams);
     if (int rc = acquire_block(c, p.d_total, &pd->blk)) return rc;
@@ -845,43 +797,6 @@ struct PlanUse {
 // the pixel arguments of llicti_encode_images_px / llicti_decode_images_px as the caller gave them (host_plan.hpp: resolve_pixels)
 struct PixArgs { int fmt; const size_t *off, *pitch; };
 
-// modes: one container mode for the call (n_modes = 1) or one per image (n_modes = B: rANS containers of ONE lane kind whose stream counts may differ,
-// fixed and "auto" xwide counts mixed); -> ME of the call (the lane kind, with the first image's count, | 0x1000 if any image is "auto") and, for
-// per-image modes, Ms (count | 0x1000 for an "auto" image: build_plan)
-static int resolve_modes(const char *who, const int *modes, int n_modes, int B, int *ME_out, std::vector<int> &Ms)
-{
-    Ms.clear();
-    if (!modes || (n_modes != 1 && n_modes != B)) return fail(LLICTI_EINVAL, "%s: modes must hold one mode or one per image", who);
-    const int ME0 = mode_streams(modes[0]);
-    if (ME0 < 0) return fail(LLICTI_EINVAL, "%s: unknown mode 0x%x", who, modes[0]);
-    *ME_out = ME0;
-    if (n_modes == 1) return 0;
-    bool differ = false, any_auto = false;
-    for (int b = 0; b < B; ++b) {
-        const int ME = mode_streams(modes[b]);
-        if (ME < 0) return fail(LLICTI_EINVAL, "%s: unknown mode 0x%x of image %d", who, modes[b], b);
-        if (((ME >> 8) & 3) != ((ME0 >> 8) & 3) || ((ME & 0xFF) == 0) != ((ME0 & 0xFF) == 0))
-            return fail(LLICTI_EINVAL, "%s: the images of one call share a container kind (reference format, or rANS streams of one lane count); image %d differs", who, b);
-        Ms.push_back(ME & 0x10FF);
-        differ = differ || ME != ME0;
-        any_auto = any_auto || (ME & 0x1000);
-    }
-    if (!differ) Ms.clear();
-    else if (any_auto) *ME_out |= 0x1000;      // (the call runs the encoder's stream-count pick; images with Mlo = 0 keep their fixed count)
-    return 0;
-}
-
-// the container modes the context's model takes (host_plan.hpp: model_takes)
-static int check_model(const llicti_ctx *c, const char *who, int ME, const std::vector<int> &Ms)
-{
-    bool ok = model_takes(c->nlev, ME);
-    for (int m : Ms) ok = ok && model_takes(c->nlev, (ME & 0x300) | m);
-    if (!ok)
-        return fail(LLICTI_EINVAL, "%s: a %d-level model (config B) codes the reference-format container or xwide v4 streams, at most %d per image "
-                    "(\"auto\": a size-rule count of at most 13)", who, c->nlev, 9 * c->nlev);
-    return 0;
-}
-
 extern "C" int llicti_workspace_params_v(llicti_ctx *c, int B, const int *Hs, const int *Ws, const int *modes, int image, size_t *off_params, long *npos)
 {
     if (!c || !off_params || !npos || !modes) return fail(LLICTI_EINVAL, "workspace_params_v: null argument");
@@ -891,7 +806,7 @@ extern "C" int llicti_workspace_params_v(llicti_ctx *c, int B, const int *Hs, co
     std::vector<int> Ms;
     if (int rc = resolve_modes("workspace_params_v", modes, B, B, &ME, Ms)) return rc;
     Plan p;
-    build_plan(p, B, Hs, Ws, nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms.empty() ? nullptr : Ms.data(), c->nlev);
+    build_plan(p, ctx_spec(c, B, Hs, Ws, nullptr, ME, modes_ptr(Ms)));
     const Geom &g = p.geo[(size_t)0 * B + image];            // level 0: the last level both passes launch
     *off_params = p.off_params + (size_t)g.par_off * sizeof(float);
     *npos = (long)g.h * g.w;
@@ -952,20 +867,14 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
     int ME = 0;
     std::vector<int> Ms;
     if (int rc = resolve_modes("encode_images", modes, n_modes, B, &ME, Ms)) return rc;
-    if (int rc = check_model(c, "encode_images", ME, Ms)) return rc;
-    if (c->nlev < LLICTI_NLEVELS)
-        for (int b = 0; b < B; ++b) {
-            const Geom gl = make_geom(1, Hs[b], Ws[b], c->nlev - 1);
-            if (gl.h > 255 || gl.w > 255)
-                return fail(LLICTI_EINVAL, "encode_images: image %d is %dx%d; a %d-level model's header stores its level-%d grid (%dx%d) in one byte each "
-                            "(at most %d pixels per side)", b, Ws[b], Hs[b], c->nlev, c->nlev - 1, gl.w, gl.h, 255 << c->nlev);
-        }
+    if (int rc = check_model(c->nlev, "encode_images", ME, Ms)) return rc;
+    if (int rc = check_header_grid("encode_images", c->nlev, B, Hs, Ws)) return rc;
     const bool autoM = (ME & 0x1000) != 0;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
     PlanDev *pd = nullptr;
-    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd, 0, px ? &pix : nullptr)) return rc;
+    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, modes_ptr(Ms), s, &pd, 0, px ? &pix : nullptr)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     const int M = p.M;
@@ -1265,6 +1174,21 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
     return 0;
 }
 
+// Room for the per-image status words of a call on B images in the context's own copy (llicti_image_status); none are valid until the call has run
+static int reserve_img_status(llicti_ctx *c, int B)
+{
+    c->img_status_n = 0;
+    if (c->img_status_cap < B) {          // grows rarely (a larger batch than any before): blocking is fine here
+        ++c->n_device_sync; ++c->n_device_alloc;
+        HIPCHK(hipDeviceSynchronize());
+        if (c->d_img_status) { (void)hipFree(c->d_img_status); c->d_img_status = nullptr; c->img_status_cap = 0; }
+        const int cap = std::max(B, 64);
+        HIPCHK(hipMalloc(&c->d_img_status, (size_t)cap * sizeof(int32_t)));
+        c->img_status_cap = cap;
+    }
+    return 0;
+}
+
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
                         const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0,
                         const PixArgs *px = nullptr, const TensorArgs *tensor = nullptr)
@@ -1275,7 +1199,7 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
     int ME = 0;
     std::vector<int> Ms;
     if (int rc = resolve_modes("decode_images", modes, n_modes, B, &ME, Ms)) return rc;
-    if (int rc = check_model(c, "decode_images", ME, Ms)) return rc;
+    if (int rc = check_model(c->nlev, "decode_images", ME, Ms)) return rc;
     std::vector<PixGeo> pix;
     if (px) {
         std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes
@@ -1287,31 +1211,21 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
         if (int rc = resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, *tensor, tn.wins, tn.nm)) return rc;
         tn.dtype = tensor->dtype; tn.Ho = tensor->Ho; tn.Wo = tensor->Wo;
     }
-    if (ME & 0x1000) return fail(LLICTI_EINVAL, "decode_images: LLICTI_MODE_RANS_X_AUTO is an encoder's mode -- a container says how many streams it has (header: llicti_header_mode)");
+    if (int rc = check_source_modes("decode_images", "container", ME)) return rc;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
     PlanDev *pd = nullptr;
-    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, Ms.empty() ? nullptr : Ms.data(), s, &pd, reduce, px ? &pix : nullptr)) return rc;
+    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, modes_ptr(Ms), s, &pd, reduce, px ? &pix : nullptr)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     if (!p.uniform && p.M == 0) return fail(LLICTI_EINVAL, "decode_images: a batch of mixed sizes needs a rANS container (the reference-format container codes equal sizes per call)");
-    for (int b = 0; b < B; ++b)
-        if (in_stride < (size_t)p.img[b].hdr_bytes)
-            return fail(LLICTI_EINVAL, "decode_images: in_stride %zu is smaller than the %d header bytes of a %dx%d image", in_stride, p.img[b].hdr_bytes, Ws[b], Hs[b]);
+    if (int rc = check_in_stride("decode_images", p.nlev, B, Hs, Ws, in_stride)) return rc;
     if (workspace_bytes < p.total)
         return fail(LLICTI_ENOSPACE, "decode_images: workspace %zu < %zu", workspace_bytes, p.total);
     uint8_t *ws = (uint8_t *)d_workspace;
 
-    c->img_status_n = 0;
-    if (c->img_status_cap < B) {          // grows rarely (a larger batch than any before): blocking is fine here
-        ++c->n_device_sync; ++c->n_device_alloc;
-        HIPCHK(hipDeviceSynchronize());
-        if (c->d_img_status) { (void)hipFree(c->d_img_status); c->d_img_status = nullptr; c->img_status_cap = 0; }
-        const int cap = std::max(B, 64);
-        HIPCHK(hipMalloc(&c->d_img_status, (size_t)cap * sizeof(int32_t)));
-        c->img_status_cap = cap;
-    }
+    if (int rc = reserve_img_status(c, B)) return rc;
     CallScope call(c, s);
     if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce, nullptr, tensor ? &tn : nullptr)) return rc;
     c->img_status_n = B;
@@ -1403,10 +1317,11 @@ extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t i
 // a short workspace before it takes a plan (a new plan's tables are uploaded, and may allocate a block)
 static void plan_need(llicti_ctx *c, int B, const int *Hs, const int *Ws, int ME, const int *Ms, size_t *total, size_t *max_container)
 {
-    auto it = c->plans.find(plan_key(c, B, Hs, Ws, nullptr, ME, Ms));
+    const PlanSpec sp = ctx_spec(c, B, Hs, Ws, nullptr, ME, Ms);
+    auto it = c->plans.find(plan_key(sp));
     if (it != c->plans.end()) { *total = it->second->p.total; *max_container = it->second->p.max_container; return; }
     Plan p;
-    build_plan(p, B, Hs, Ws, nullptr, ME, c->n_cu, c->cnn_tile_rows, c->force_ragged != 0, Ms, c->nlev);
+    build_plan(p, sp);
     *total = p.total; *max_container = p.max_container;
 }
 
@@ -1421,29 +1336,10 @@ extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_
                                        void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len_out, void *stream)
 {
     if (!c || !d_in || !d_seg_len_in || !d_workspace || !d_out || !d_seg_len_out) return fail(LLICTI_EINVAL, "transcode_images: null pointer");
-    if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
     int MEs = 0, MEd = 0;
     std::vector<int> Mss, Msd;
-    if (int rc = resolve_modes("transcode_images (source)", src_modes, n_src, B, &MEs, Mss)) return rc;
-    if (int rc = check_model(c, "transcode_images (source)", MEs, Mss)) return rc;
-    bool src_auto = (MEs & 0x1000) != 0;
-    for (int m : Mss) src_auto = src_auto || (m & 0x1000);
-    if (src_auto) return fail(LLICTI_EINVAL, "transcode_images: LLICTI_MODE_RANS_X_AUTO is an encoder's mode -- a source container says how many streams it has (header: llicti_header_mode)");
-    if (int rc = resolve_modes("transcode_images (target)", dst_modes, n_dst, B, &MEd, Msd)) return rc;
-    if (int rc = check_model(c, "transcode_images (target)", MEd, Msd)) return rc;
-    bool mixed = c->force_ragged != 0;
-    for (int b = 1; b < B; ++b) mixed = mixed || Hs[b] != Hs[0] || Ws[b] != Ws[0];
-    if (mixed && ((MEs & 0xFF) == 0 || (MEd & 0xFF) == 0))
-        return fail(LLICTI_EINVAL, "transcode_images: a batch of mixed sizes needs rANS containers on both sides (the reference-format container codes equal sizes per call)");
-    for (int b = 0; b < B; ++b) {
-        const Geom gl = make_geom(1, Hs[b], Ws[b], c->nlev - 1);
-        if (c->nlev < LLICTI_NLEVELS && (gl.h > 255 || gl.w > 255))
-            return fail(LLICTI_EINVAL, "transcode_images: image %d is %dx%d; a %d-level model's header stores its level-%d grid (%dx%d) in one byte each "
-                        "(at most %d pixels per side)", b, Ws[b], Hs[b], c->nlev, c->nlev - 1, gl.w, gl.h, 255 << c->nlev);
-        const size_t hdr = 17 + 3 * (size_t)gl.h * gl.w;
-        if (in_stride < hdr)
-            return fail(LLICTI_EINVAL, "transcode_images: in_stride %zu is smaller than the %zu header bytes of a %dx%d image", in_stride, hdr, Ws[b], Hs[b]);
-    }
+    if (int rc = admit_transcode(c->nlev, c->force_ragged != 0, B, Hs, Ws, src_modes, n_src, dst_modes, n_dst, &MEs, Mss, &MEd, Msd)) return rc;
+    if (int rc = check_in_stride("transcode_images", c->nlev, B, Hs, Ws, in_stride)) return rc;
     {
         const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)B * in_stride, o0 = (uintptr_t)d_out, o1 = o0 + (size_t)B * out_stride;
         if (i0 < o1 && o0 < i1) return fail(LLICTI_EINVAL, "transcode_images: d_out overlaps d_in");
@@ -1451,7 +1347,7 @@ extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
-    const int *ms_src = Mss.empty() ? nullptr : Mss.data(), *ms_dst = Msd.empty() ? nullptr : Msd.data();
+    const int *ms_src = modes_ptr(Mss), *ms_dst = modes_ptr(Msd);
     {
         size_t tot_s = 0, tot_d = 0, mc_s = 0, mc_d = 0;
         plan_need(c, B, Hs, Ws, MEs, ms_src, &tot_s, &mc_s);
@@ -1472,15 +1368,7 @@ extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_
     uint8_t *ws = (uint8_t *)d_workspace;
     const TranscodeTarget tc{ pdd, ws + lay.off_dst };
 
-    c->img_status_n = 0;
-    if (c->img_status_cap < B) {          // grows rarely (a larger batch than any before): blocking is fine here
-        ++c->n_device_sync; ++c->n_device_alloc;
-        HIPCHK(hipDeviceSynchronize());
-        if (c->d_img_status) { (void)hipFree(c->d_img_status); c->d_img_status = nullptr; c->img_status_cap = 0; }
-        const int cap = std::max(B, 64);
-        HIPCHK(hipMalloc(&c->d_img_status, (size_t)cap * sizeof(int32_t)));
-        c->img_status_cap = cap;
-    }
+    if (int rc = reserve_img_status(c, B)) return rc;
     CallScope call(c, s);
     if (int rc = decode_stages(c, pds, d_in, in_stride, d_seg_len_in, ws, nullptr, s, 0, &tc)) return rc;
     const int16_t *planes = (const int16_t *)(ws + ps.off_planes);

@@ -1,0 +1,154 @@
+// host_queries.cpp -- what the size queries and the plan builder of llicti_amd/csrc/host_plan.hpp answer for a fixed list of batches, one line
+// per query, and what the admission rules of the whole-batch calls refuse.  Plain g++, beside tests/sanitize_host.cpp:
+//   - stdout is compared byte for byte with tests/golden/host_queries.txt (tests/test_host_cpu.py), which was recorded BEFORE the host layer's
+//     rules were given single homes: a change of the host layer that moves a workspace size, a container bound, a plan's `uniform` form or a
+//     cache key shows up as a differing line;
+//   - every admission function is then called with one faulty input per rule: LLICTI_EINVAL, and the message starts with the caller's prefix.
+// tests/sanitize_host.sh runs it under AddressSanitizer + UBSan too.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "../llicti_amd/csrc/host_plan.hpp"
+
+#define REQUIRE(c)                                                                      \
+    do {                                                                                \
+        if (!(c)) { fprintf(stderr, "FAILED %s (%s:%d): last error '%s'\n", #c, __FILE__, __LINE__, g_err.c_str()); exit(1); } \
+    } while (0)
+
+// ---- the two calls whose spelling belongs to host_plan.hpp: the resolver of one side's modes, and the plan builder
+static bool side_modes(const std::vector<int> &modes, int B, int *ME, std::vector<int> &Ms)
+{
+    return resolve_modes("host_queries", modes.data(), (int)modes.size(), B, ME, Ms) == 0;
+}
+static void plan_of(Plan &p, int B, const int *Hs, const int *Ws, int ME, const std::vector<int> &Ms, int nlev, bool ragged)
+{
+    build_plan(p, PlanSpec{ B, Hs, Ws, ME, modes_ptr(Ms), nlev, ragged });
+}
+// ----
+
+struct Sizes { const char *name; std::vector<int> Hs, Ws; };
+struct Modes { const char *name; std::vector<int> m; };
+
+static const int ac = LLICTI_MODE_AC, r8 = LLICTI_MODE_RANS(8), w14 = LLICTI_MODE_RANS_WIDE(14), x64 = LLICTI_MODE_RANS_X(64), xa3 = LLICTI_MODE_RANS_X_AUTO(3),
+                 x4 = LLICTI_MODE_RANS_X(4), x8 = LLICTI_MODE_RANS_X(8), x16 = LLICTI_MODE_RANS_X(16), x18 = LLICTI_MODE_RANS_X(18), x19 = LLICTI_MODE_RANS_X(19),
+                 xa10 = LLICTI_MODE_RANS_X_AUTO(10), bad = 0x777;
+
+static void query(const Sizes &s, const Modes &src, const std::vector<Modes> &targets, int nlev)
+{
+    const int B = (int)s.Hs.size();
+    const int *Hs = s.Hs.data(), *Ws = s.Ws.data();
+    printf("L%d %s %s: workspace %zu\n", nlev, s.name, src.name, plan_workspace_bytes_vm(B, Hs, Ws, src.m.data(), (int)src.m.size(), nlev));
+    int ME = 0;
+    std::vector<int> Ms;
+    if (check_dims_v(B, Hs, Ws) || !side_modes(src.m, B, &ME, Ms)) printf("L%d %s %s: no plan\n", nlev, s.name, src.name);
+    else
+        for (int ragged = 0; ragged < 2; ++ragged) {
+            Plan p;
+            plan_of(p, B, Hs, Ws, ME, Ms, nlev, ragged != 0);
+            printf("L%d %s %s ragged %d: total %zu max_container %zu uniform %d key", nlev, s.name, src.name, ragged, p.total, p.max_container, p.uniform ? 1 : 0);
+            for (long k : p.key) printf(" %ld", k);
+            printf("\n");
+        }
+    for (const Modes &t : targets)
+        printf("L%d %s %s -> %s: transcode workspace %zu\n", nlev, s.name, src.name, t.name,
+               plan_transcode_workspace_bytes(B, Hs, Ws, src.m.data(), (int)src.m.size(), t.m.data(), (int)t.m.size(), nlev));
+}
+
+static void queries()
+{
+    const Sizes one32{ "1x32x32", { 32 }, { 32 } }, one96{ "1x96x160", { 96 }, { 160 } }, three32{ "3x32x32", { 32, 32, 32 }, { 32, 32, 32 } },
+                three96{ "3x96x160", { 96, 96, 96 }, { 160, 160, 160 } }, mixed{ "96x160+67x93+32x33", { 96, 67, 32 }, { 160, 93, 33 } },
+                small{ "96x160+31x93+32x33", { 96, 31, 32 }, { 160, 93, 33 } };
+    const Modes m_ac{ "ac", { ac } }, m_r8{ "rans8", { r8 } }, m_w14{ "wide14", { w14 } }, m_x64{ "xwide64", { x64 } }, m_xa3{ "xauto3", { xa3 } }, m_x8{ "xwide8", { x8 } },
+                m_bad{ "unknown", { bad } };
+    // one mode per image (B = 3)
+    const Modes pi_equal{ "[x8 x8 x8]", { x8, x8, x8 } }, pi_count{ "[x4 x8 x16]", { x4, x8, x16 } }, pi_auto{ "[x4 xauto3 x8]", { x4, xa3, x8 } },
+                pi_all_auto{ "[xauto3 xauto3 xauto3]", { xa3, xa3, xa3 } }, pi_narrow{ "[r8 r8 r8]", { r8, r8, r8 } }, pi_ac{ "[ac ac ac]", { ac, ac, ac } },
+                pi_kinds{ "[x4 rans8 x4]", { x4, r8, x4 } }, pi_ac_x{ "[ac x4 ac]", { ac, x4, ac } }, pi_bad{ "[x4 unknown x4]", { x4, bad, x4 } },
+                pi_two{ "[x4 x8]", { x4, x8 } };
+    const std::vector<Modes> targets = { m_ac, m_x8, m_xa3 }, targets3 = { m_ac, m_x8, m_xa3, pi_auto, pi_kinds, pi_bad, pi_two };
+    for (const Sizes *s : { &one32, &one96, &three32, &three96, &mixed }) {
+        const bool three = s->Hs.size() == 3;
+        for (const Modes *m : { &m_ac, &m_r8, &m_w14, &m_x64, &m_xa3, &m_bad }) query(*s, *m, three ? targets3 : targets, LLICTI_NLEVELS);
+        if (three)
+            for (const Modes *m : { &pi_equal, &pi_count, &pi_auto, &pi_all_auto, &pi_narrow, &pi_ac, &pi_kinds, &pi_ac_x, &pi_bad, &pi_two })
+                query(*s, *m, targets3, LLICTI_NLEVELS);
+    }
+    query(small, m_x8, targets, LLICTI_NLEVELS);       // an image below 32 pixels: every query refuses
+    query(one96, pi_equal, targets, LLICTI_NLEVELS);   // three modes for one image
+    // config B (2 levels): the reference format and xwide streams, at most 18 per image; header grids of at most 255 per side
+    const Modes m_x18{ "xwide18", { x18 } }, m_x19{ "xwide19", { x19 } }, m_xa10{ "xauto10", { xa10 } }, pi_b{ "[x4 x18 xauto3]", { x4, x18, xa3 } },
+                pi_b19{ "[x4 x19 x8]", { x4, x19, x8 } };
+    const Sizes wide_b{ "1x1024x32", { 1024 }, { 32 } }, tall_b{ "1x32x1024", { 32 }, { 1024 } }, fits_b{ "1x1020x32", { 1020 }, { 32 } };
+    const std::vector<Modes> targets_b = { m_ac, m_x18, m_x19, m_xa3, m_xa10, m_r8 };
+    for (const Sizes *s : { &one32, &one96, &three96, &mixed, &wide_b, &tall_b, &fits_b })
+        for (const Modes *m : { &m_ac, &m_x18, &m_x19, &m_r8, &m_w14, &m_xa3, &m_xa10 }) query(*s, *m, targets_b, kLevelsB);
+    query(three96, pi_b, { m_ac, pi_b, pi_b19 }, kLevelsB);
+    query(mixed, pi_b19, { m_x18 }, kLevelsB);
+    for (int nlev : { LLICTI_NLEVELS, kLevelsB })
+        for (const auto &hw : { std::pair<int, int>{ 32, 32 }, { 96, 160 }, { 67, 93 }, { 32, 33 }, { 1024, 32 }, { 31, 64 }, { 64, 8161 } })
+            printf("L%d %dx%d: max container %zu\n", nlev, hw.first, hw.second, plan_max_container_bytes(hw.first, hw.second, nlev));
+}
+
+// One faulty input per admission rule: the code, and the caller's prefix in front of the reason.
+static bool refused(int rc, const char *who)
+{
+    const std::string want = std::string(who) + ": ";
+    return rc == LLICTI_EINVAL && g_err.compare(0, want.size(), want) == 0;
+}
+static void refusals()
+{
+    const int H3[3] = { 96, 96, 96 }, W3[3] = { 160, 160, 160 }, Hm[3] = { 96, 67, 32 }, Wm[3] = { 160, 93, 33 };
+    int ME = 0;
+    std::vector<int> Ms;
+    // the modes of one side
+    const int two[2] = { x4, x8 }, kinds[3] = { x4, r8, x4 }, ac_x[3] = { ac, x4, ac }, bad3[3] = { x4, bad, x4 }, counts[3] = { x4, x8, x16 }, mix[3] = { x4, xa3, x8 };
+    REQUIRE(refused(resolve_modes("encode_images", nullptr, 1, 3, &ME, Ms), "encode_images"));
+    REQUIRE(refused(resolve_modes("encode_images", two, 2, 3, &ME, Ms), "encode_images"));
+    REQUIRE(refused(resolve_modes("decode_images", &bad, 1, 3, &ME, Ms), "decode_images"));
+    REQUIRE(refused(resolve_modes("decode_images", bad3, 3, 3, &ME, Ms), "decode_images"));
+    REQUIRE(refused(resolve_modes("transcode_images (source)", kinds, 3, 3, &ME, Ms), "transcode_images (source)"));
+    REQUIRE(refused(resolve_modes("transcode_images (target)", ac_x, 3, 3, &ME, Ms), "transcode_images (target)"));
+    REQUIRE(resolve_modes("encode_images", counts, 3, 3, &ME, Ms) == 0 && ME == (4 | 0x200) && Ms == std::vector<int>({ 4, 8, 16 }));
+    REQUIRE(resolve_modes("encode_images", mix, 3, 3, &ME, Ms) == 0 && ME == (4 | 0x200 | 0x1000) && Ms == std::vector<int>({ 4, 3 | 0x1000, 8 }));
+    const int same[3] = { x8, x8, x8 };
+    REQUIRE(resolve_modes("encode_images", same, 3, 3, &ME, Ms) == 0 && ME == (8 | 0x200) && Ms.empty());
+    // the modes a model takes: config B refuses narrow and wide streams, more than 18 xwide streams, an "auto" rule above 13
+    REQUIRE(check_model(LLICTI_NLEVELS, "encode_images", 128 | 0x200, {}) == 0 && check_model(kLevelsB, "encode_images", 18 | 0x200, {}) == 0);
+    REQUIRE(refused(check_model(kLevelsB, "encode_images", 8, {}), "encode_images"));
+    REQUIRE(refused(check_model(kLevelsB, "decode_images", 14 | 0x100, {}), "decode_images"));
+    REQUIRE(refused(check_model(kLevelsB, "transcode_images (target)", 19 | 0x200, {}), "transcode_images (target)"));
+    REQUIRE(refused(check_model(kLevelsB, "transcode_images (source)", 4 | 0x200, { 4, 19, 8 }), "transcode_images (source)"));
+    REQUIRE(refused(check_model(kLevelsB, "encode_images", 14 | 0x200 | 0x1000, {}), "encode_images"));
+    // "auto" names no container
+    REQUIRE(check_source_modes("decode_images", "container", 8 | 0x200) == 0);
+    REQUIRE(refused(check_source_modes("decode_images", "container", 3 | 0x200 | 0x1000), "decode_images"));
+    REQUIRE(resolve_modes("transcode_images (source)", mix, 3, 3, &ME, Ms) == 0 && refused(check_source_modes("transcode_images", "source container", ME), "transcode_images"));
+    // config B's header: the last level's grid in one byte per side
+    const int Hb[2] = { 64, 1024 }, Wb[2] = { 48, 32 }, Hok[2] = { 64, 1020 };
+    REQUIRE(check_header_grid("encode_images", LLICTI_NLEVELS, 2, Hb, Wb) == 0 && check_header_grid("encode_images", kLevelsB, 2, Hok, Wb) == 0);
+    REQUIRE(refused(check_header_grid("encode_images", kLevelsB, 2, Hb, Wb), "encode_images"));
+    REQUIRE(refused(check_header_grid("transcode_images", kLevelsB, 2, Wb, Hb), "transcode_images"));
+    // a container slot holds at least its image's header: 17 + 3 h w of the last level's grid (96x160, 5 levels: 3 x 5; 2 levels: 24 x 40)
+    REQUIRE(header_bytes(96, 160, LLICTI_NLEVELS) == 17 + 3 * 3 * 5 && header_bytes(96, 160, kLevelsB) == 17 + 3 * 24 * 40);
+    REQUIRE(check_in_stride("decode_images", LLICTI_NLEVELS, 3, Hm, Wm, 62) == 0);
+    REQUIRE(refused(check_in_stride("decode_images", LLICTI_NLEVELS, 3, Hm, Wm, 61), "decode_images"));
+    REQUIRE(refused(check_in_stride("transcode_images", kLevelsB, 3, H3, W3, 2896), "transcode_images"));
+    // a transcode of mixed sizes (or of force_ragged's placement) needs rANS containers on both sides
+    REQUIRE(check_transcode_sizes("transcode_images", 3, Hm, Wm, 8 | 0x200, 4, false) == 0 && check_transcode_sizes("transcode_images", 3, H3, W3, 0, 0, false) == 0);
+    REQUIRE(refused(check_transcode_sizes("transcode_images", 3, Hm, Wm, 0, 8 | 0x200, false), "transcode_images"));
+    REQUIRE(refused(check_transcode_sizes("transcode_images", 3, Hm, Wm, 8 | 0x200, 0, false), "transcode_images"));
+    REQUIRE(refused(check_transcode_sizes("transcode_images", 3, H3, W3, 0, 8 | 0x200, true), "transcode_images"));
+    // a size query that refuses leaves the reason behind
+    g_err.clear();
+    REQUIRE(plan_workspace_bytes_vm(3, H3, W3, kinds, 3) == 0 && !g_err.empty());
+    g_err.clear();
+    REQUIRE(plan_transcode_workspace_bytes(3, H3, W3, &xa3, 1, &x8, 1) == 0 && !g_err.empty());
+}
+
+int main()
+{
+    queries();
+    refusals();
+    return 0;
+}

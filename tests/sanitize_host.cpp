@@ -154,7 +154,7 @@ int main()
                 for (int ragged = 0; ragged < 2; ++ragged) {
                     if (ragged && ME == 0 && B > 1) continue;
                     Plan p;
-                    build_plan(p, B, Hs.data(), Ws.data(), nullptr, ME, 256, 0, ragged != 0);
+                    build_plan(p, PlanSpec{ B, Hs.data(), Ws.data(), ME, nullptr, LLICTI_NLEVELS, ragged != 0 });
                     check_plan(p, B, Hs.data(), Ws.data(), ME);
                     REQUIRE(p.uniform == !ragged);
                 }
@@ -169,7 +169,7 @@ int main()
         const int mode = kModes[1 + rng() % (sizeof kModes / sizeof kModes[0] - 1)];
         const int tr[] = { 0, 16, 8, 4, -1 };
         Plan p;
-        build_plan(p, B, Hs.data(), Ws.data(), nullptr, mode_streams(mode), 1 + (int)(rng() % 320), tr[rng() % 5], false);
+        build_plan(p, PlanSpec{ B, Hs.data(), Ws.data(), mode_streams(mode), nullptr, LLICTI_NLEVELS, false, nullptr, 1 + (int)(rng() % 320), tr[rng() % 5] });
         check_plan(p, B, Hs.data(), Ws.data(), mode_streams(mode));
         REQUIRE(plan_workspace_bytes_v(B, Hs.data(), Ws.data(), mode) >= p.total);
         if (it % 2 == 0) {                                      // a stream count per image (llicti_encode_images_vm): any count the lane kind allows
@@ -180,7 +180,7 @@ int main()
                 modes[b] = (kind == 2 ? 0x500 : kind == 1 ? 0x300 : 0x100) | Ms[b];
             }
             Plan q;
-            build_plan(q, B, Hs.data(), Ws.data(), nullptr, ME, 256, 0, false, Ms.data());
+            build_plan(q, PlanSpec{ B, Hs.data(), Ws.data(), ME, Ms.data() });
             check_plan(q, B, Hs.data(), Ws.data(), ME, Ms.data());
             REQUIRE(plan_workspace_bytes_vm(B, Hs.data(), Ws.data(), modes.data(), B) >= q.total);
             if (B > 1) { modes[B - 1] = 0; REQUIRE(plan_workspace_bytes_vm(B, Hs.data(), Ws.data(), modes.data(), B) == 0); }      // the reference format among rANS modes: refused
@@ -190,7 +190,7 @@ int main()
             size_t pos = 64;
             for (int b = 0; b < B; ++b) { off[b] = pos; pos += 3 * (size_t)Hs[b] * Ws[b] + rng() % 100; }
             Plan q;
-            build_plan(q, B, Hs.data(), Ws.data(), off.data(), mode_streams(mode));
+            build_plan(q, PlanSpec{ B, Hs.data(), Ws.data(), mode_streams(mode), nullptr, LLICTI_NLEVELS, false, off.data() });
             check_plan(q, B, Hs.data(), Ws.data(), mode_streams(mode));
             REQUIRE(!q.uniform && q.rgb_bytes <= pos);
         }

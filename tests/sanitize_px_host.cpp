@@ -30,7 +30,7 @@ static Plan pixel_plan(int B, const int *Hs, const int *Ws, int ME, int nlev, bo
     std::vector<PixGeo> pix;
     REQUIRE(resolve_pixels("test", B, Hw.data(), Ww.data(), fmt, off, pitch, pix) == 0);
     Plan p;
-    build_plan(p, B, Hs, Ws, nullptr, ME, 256, 0, ragged, nullptr, nlev);
+    build_plan(p, PlanSpec{ B, Hs, Ws, ME, nullptr, nlev, ragged });
     *lookup = p.key;
     if (reduce > 0) { plan_add_reduced(p, reduce, nullptr); reduced_key_tail(*lookup, B, Hs, Ws, reduce, nullptr); }
     plan_add_pixels(p, pix);
@@ -41,11 +41,11 @@ static Plan pixel_plan(int B, const int *Hs, const int *Ws, int ME, int nlev, bo
 static void drive(int B, const int *Hs, const int *Ws, int ME, int nlev, bool ragged)
 {
     Plan full;
-    build_plan(full, B, Hs, Ws, nullptr, ME, 256, 0, ragged, nullptr, nlev);
+    build_plan(full, PlanSpec{ B, Hs, Ws, ME, nullptr, nlev, ragged });
     std::set<std::vector<long>> keys = { full.key };
     for (int r = 1; r <= nlev; ++r) {
         Plan red;
-        build_plan(red, B, Hs, Ws, nullptr, ME, 256, 0, ragged, nullptr, nlev);
+        build_plan(red, PlanSpec{ B, Hs, Ws, ME, nullptr, nlev, ragged });
         plan_add_reduced(red, r, nullptr);
         REQUIRE(keys.insert(red.key).second);
     }

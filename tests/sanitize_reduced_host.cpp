@@ -22,11 +22,11 @@ static long n_checks = 0;
 static void drive(int B, const int *Hs, const int *Ws, int ME, int nlev, bool ragged)
 {
     Plan full;
-    build_plan(full, B, Hs, Ws, nullptr, ME, 256, 0, ragged, nullptr, nlev);
+    build_plan(full, PlanSpec{ B, Hs, Ws, ME, nullptr, nlev, ragged });
     std::vector<size_t> loose(B);                     // an explicit full-size placement: a different full-size key
     { size_t pos = 64; for (int b = 0; b < B; ++b) { loose[b] = pos; pos += 3 * (size_t)Hs[b] * Ws[b] + 64; } }
     Plan full_loose;
-    build_plan(full_loose, B, Hs, Ws, loose.data(), ME, 256, 0, ragged, nullptr, nlev);
+    build_plan(full_loose, PlanSpec{ B, Hs, Ws, ME, nullptr, nlev, ragged, loose.data() });
     std::set<std::vector<long>> keys = { full.key, full_loose.key };
     REQUIRE(keys.size() == 2);
     for (int r = 1; r <= nlev; ++r) {
@@ -34,7 +34,7 @@ static void drive(int B, const int *Hs, const int *Ws, int ME, int nlev, bool ra
             std::vector<size_t> off(B);
             { size_t pos = 16; for (int b = 0; b < B; ++b) { off[b] = pos; pos += 3 * (size_t)reduced_dim(Hs[b], r) * reduced_dim(Ws[b], r) + 16; } }
             Plan p;
-            build_plan(p, B, Hs, Ws, nullptr, ME, 256, 0, ragged, nullptr, nlev);
+            build_plan(p, PlanSpec{ B, Hs, Ws, ME, nullptr, nlev, ragged });
             plan_add_reduced(p, r, placed ? off.data() : nullptr);
             // the same key as the one the cache looks up
             std::vector<long> key = full.key;

@@ -65,12 +65,12 @@ static void drive(int B, const int *Hs, const int *Ws, const std::vector<int> &s
     REQUIRE(need >= plan_workspace_bytes_vm(B, Hs, Ws, dst.data(), (int)dst.size(), nlev));
     int MEs = 0, MEd = 0;
     std::vector<int> Mss, Msd;
-    REQUIRE(plan_side_modes(src.data(), (int)src.size(), B, &MEs, Mss));
-    REQUIRE(plan_side_modes(dst.data(), (int)dst.size(), B, &MEd, Msd));
+    REQUIRE(resolve_modes("source", src.data(), (int)src.size(), B, &MEs, Mss) == 0);
+    REQUIRE(resolve_modes("target", dst.data(), (int)dst.size(), B, &MEd, Msd) == 0);
     for (int ragged = 0; ragged < 2; ++ragged) {
         Plan s, d;
-        build_plan(s, B, Hs, Ws, nullptr, MEs, 256, 0, ragged != 0, Mss.empty() ? nullptr : Mss.data(), nlev);
-        build_plan(d, B, Hs, Ws, nullptr, MEd, 256, 0, ragged != 0, Msd.empty() ? nullptr : Msd.data(), nlev);
+        build_plan(s, PlanSpec{ B, Hs, Ws, MEs, modes_ptr(Mss), nlev, ragged != 0 });
+        build_plan(d, PlanSpec{ B, Hs, Ws, MEd, modes_ptr(Msd), nlev, ragged != 0 });
         const TranscodeLayout lay = transcode_layout(s, d);
         REQUIRE(lay.total <= need);
         REQUIRE(lay.off_dst >= s.total && lay.off_dst % 256 == 0 && lay.total == lay.off_dst + d.total);      // [source | target], disjoint
@@ -100,8 +100,8 @@ static void drive(int B, const int *Hs, const int *Ws, const std::vector<int> &s
     // a plan pair that does NOT agree is told apart (another batch size)
     if (B > 1) {
         Plan s, d;
-        build_plan(s, B, Hs, Ws, nullptr, MEs, 256, 0, false, Mss.empty() ? nullptr : Mss.data(), nlev);
-        build_plan(d, B - 1, Hs, Ws, nullptr, MEd, 256, 0, false, nullptr, nlev);
+        build_plan(s, PlanSpec{ B, Hs, Ws, MEs, modes_ptr(Mss), nlev });
+        build_plan(d, PlanSpec{ B - 1, Hs, Ws, MEd, nullptr, nlev });
         REQUIRE(!transcode_plans_agree(s, d));
     }
 }

@@ -361,6 +361,26 @@ def test_host_plan_logic_driver(tmp_path):
     assert "clean" in out.stdout
 
 
+def test_host_queries_match_recorded_answers(tmp_path):
+    """tests/host_queries.cpp (plain g++ against host_plan.hpp, like the driver above) prints what the size queries -- workspace bytes, transcode
+    workspace bytes, the container bound -- and build_plan (total, max_container, uniform, the cache key) answer for a fixed list of batches:
+    B = 1 and 3, equal and mixed sizes, every container kind, per-image modes, both models, and the combinations that give 0.  The output was
+    recorded before the admission rules and the key builder got their single homes in host_plan.hpp and must stay equal byte for byte.  The
+    program then calls every admission function with one faulty input per rule (LLICTI_EINVAL, the caller's prefix in the message) and exits
+    non-zero if one is not refused."""
+    import subprocess
+    exe = tmp_path / "host_queries"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tests", "host_queries.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    with open(os.path.join(ROOT, "tests", "golden", "host_queries.txt"), "rb") as f:
+        want = f.read()
+    if out.stdout != want:
+        got_l, want_l = out.stdout.split(b"\n"), want.split(b"\n")
+        diff = [(i + 1, w, g) for i, (w, g) in enumerate(zip(want_l, got_l)) if w != g][:5]
+        assert False, (len(want_l), len(got_l), diff)
+
+
 def test_no_scratch_in_mfma_and_stage_kernels():
     """no kernel of the library may spill a vector register or use a private segment -- the band CNN (18 instantiations: band x
     tile rows x equal / mixed sizes) and the stage decoders least of all.  Round 5's `band_params_kernel<2,16,true>` (the heaviest kernel of the
