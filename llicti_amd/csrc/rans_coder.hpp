@@ -579,6 +579,7 @@ __global__ __launch_bounds__(64) void rans_init_kernel(const uint8_t *__restrict
         nbytes = n - 2 - GEO::kPayBytes;
         const int pad = (t16 >> 11) & 7;
         if ((t16 >> 14) || nbytes < 0 || (nbytes == 0 && pad)) { bad = true; T = 0; nbytes = max(nbytes, 0); }
+        else if (pad && (slot[4 + nbytes - 1] >> (8 - pad))) { bad = true; T = 0; }      // the unused bits on top of the region's last byte are zero
         cur = bad ? 0 : 8 * nbytes - pad;
     }
     const uint8_t *fs = slot + 4 + nbytes;

@@ -1211,6 +1211,7 @@ int orc_decode_image_rans(const uint8_t *in, const int32_t seg_len[49], const or
                 const int padb = (t16 >> 11) & 7;
                 nbytes = len - 2 - PAY_BITS / 8;
                 if ((t16 >> 14) || nbytes < 0 || (nbytes == 0 && padb)) { free(x); free(bitsp); free(cur); free(T); return -3; }
+                if (padb && (sp[2 + nbytes - 1] >> (8 - padb))) { free(x); free(bitsp); free(cur); free(T); return -3; }   /* the unused bits are zero */
                 T[m] = t16 & 0x7FF;
                 cur[m] = 8 * nbytes - padb;                           /* number of data bits */
             }

@@ -120,9 +120,14 @@ long orc_stream_pairs(const int16_t *planes, int H, int W, const int16_t minmax[
  * streams (1 .. 14) of L = 128 lanes.  Extended, v = 16 (byte 0 = 0xE8): XWIDE streams of L = 256 lanes in the v4 layout; their count is in bits
  * 10 .. 15 of the int16 pad field (bits 0 .. 9 are the five levels' pad flags; these six bits are zero in every other container): u = 1 .. 32 -> M = u
  * streams, one per segment; u = 33 / 34 -> 64 / 128 streams, two / four per segment behind the length table.
+ * Length table (M = 64 / 128, k = M / 32 streams per segment): segment g of the first 32 = k u32 LE lengths, then streams g k .. g k + k - 1 back to back;
+ * the lengths add up to the segment.  M <= 32: stream m is segment m, the segments behind the last stream are empty.
+ * Extended, v = 17 (byte 0 = 0xE9): the xwide v4 container of the product's SECOND model (config B: 2 levels, 4 + 18 segments, 4 pad-flag bits, pad bits
+ * 4 .. 9 zero), the count in bits 10 .. 15 as under 0xE8.  This oracle restates config A only and refuses the tag like a retired one.
  * COMPATIBILITY RULE: a format revision that changes the meaning of stream bytes takes a header value no earlier reader accepts.  v = 17 .. 31 were
- * the xwide tags of rounds 4-5 (v3 layout: u16 T field in front, seeded chains inside the payload, escape); v4 retires them -- this reader refuses
- * them with -4 / LLICTI_EFORMAT -- and a round-5 reader refuses a v4 container because its pad field contradicts the image size.
+ * the xwide tags of rounds 4-5 (v3 layout: u16 T field in front, seeded chains inside the payload, escape); v4 retires them -- a reader refuses
+ * v = 18 .. 31 with -4 / LLICTI_EFORMAT (v = 17 came back as config B's tag, above: its pad field carries a count, which no v3 xwide container's
+ * did) -- and a round-5 reader refuses a v4 container because its pad field contradicts the image size.
  * Same CDFs, same symbols; the 45 torchac streams are replaced by M independent L-way interleaved rANS streams per image
  * (seg_len[4 .. 4+M-1], the rest 0).  Stage st (decode order) has nc symbols in cropped raster order; symbol n sits in chunk
  * n/L, lane n%L; chunk c belongs to stream c % M and is that stream's step c / M of the stage.
@@ -130,6 +135,12 @@ long orc_stream_pairs(const int16_t *planes, int H, int W, const int16_t minmax[
  *              frequency f the encoder shifts out the n lowest bits of x, n minimal with (x >> n) < f << 16; then
  *              x = ((x / f) << 16) + x % f + c_low.  The decoder inverts: x = f * (x >> 16) + (x & 0xFFFF) - c_low, n = clz(x),
  *              x = x << n | n bits.  x / f >= 2^15: the loss per symbol is ~2^-16 of its length, like the range coder's.
+ *              A field of n bits lies at n consecutive positions of the LSB-first bit region and is the integer they spell, lowest position =
+ *              bit 0 (the n lowest bits of the encoder's x as they were).  The symbol is the largest s whose table entry c_low(s) <= the slot
+ *              x & 0xFFFF, and symbol 0 if there is none: entry 0 is the floor of the search whatever it holds (it need not be 0; no encoder
+ *              writes a slot below it, and a decoder that meets one takes symbol 0 and goes on).  The state is updated in 32-bit arithmetic.
+ *              Checks of every coder, main and tail: n = clz(x) <= 16 after each symbol (x / f >= 2^15: a smaller state was never written),
+ *              and no field reaches below its region.  A forged slot is caught by these or by the end-of-stream checks, if at all.
  *   order      per step the decoder first decodes the L lanes' symbols, then renormalises lane-ascending; it reads the bit
  *              region DOWNWARDS (the encoder, which runs the steps backwards and the lanes descending, wrote it upwards).
  *   tail       a lane's initial state carries payload instead of nothing: the stream's last T symbols of the LAST stage
@@ -140,8 +151,11 @@ long orc_stream_pairs(const int16_t *planes, int H, int W, const int16_t minmax[
  *              from bit 0 of the payload (1984 / 3968 bits), the final 32-bit state on top (leading one = the payload's highest set bit).  T is
  *              maximal with 32 + bits <= 31 L (T <= 2047).  The decoder finds the tail state by its leading one, reads downwards, and must end
  *              with the tail coder's start state and no bit left (and the main region read to its last bit) -- the format's integrity check.
+ *              A stream without tail symbols (T = 0: no symbol in the last stage) carries a tail coder that pushed nothing: payload = its state
+ *              2^31 and no bit, i.e. lane 1's lowest payload bit and nothing else.
  *              Stream: u16 LE (T | pad << 11, bits 14 and 15 zero) | bit region, LSB first, ceil(bits / 8) bytes, pad = unused zero bits on top
- *              of its last byte | L x 31-bit final states (low 31 bits of x_l at bit 31 l; 248 / 496 bytes).
+ *              of its last byte (a reader checks that they are zero: one byte sequence per image) | L x 31-bit final states (low 31 bits of
+ *              x_l at bit 31 l; 248 / 496 bytes).
  *   tail, xwide v4 (round 6):
  *     arena    the tail coder's output is NOT cut to the payload: tail symbols are taken -- counting from the stream's end, j = 0 the last -- until,
  *              at a multiple of 32, the output has reached the payload's 7936 bits (or the stream's share of the last stage, or 8160 symbols, ends).
@@ -163,7 +177,10 @@ long orc_stream_pairs(const int16_t *planes, int H, int W, const int16_t minmax[
  *              seeds).  Arena: bits [0, 32) the final state (flat: it may be below 2^31 if the tail is a handful of symbols), the fields from
  *              bit 32 up in the decoder's reading order, then ONE end-marker bit -- the arena's highest set bit (a spill ends with it).  The
  *              decoder takes min(clz(x), bits left below the marker) bits after each symbol: once the bits are used up it is in the encoder's
- *              silent start and the state stays small.  Checks: clz <= 16 wherever bits were left, every bit read, the final state = sym(0) < A.
+ *              silent start and the state stays small.  Checks: clz <= 16 wherever the chain takes clz bits (clz above what is left is the silent
+ *              start, not an error), every bit read, the final state = sym(0) < A.
+ *              A stream without tail symbols (T = 0) is the one-chain form with nothing pushed: flag set, state 0, the end marker at arena bit 32
+ *              (so an empty stream's 992 state bytes are not all zero: lane 1 carries bit 1).  The flag of a stream without symbols is "one chain".
  *     stream   bit region, LSB first | L x 31-bit final states (992 bytes).  Bit region, bottom up: the spill | the main coder's bits | 8 bits
  *              ceil(T / 32) | 1 bit "one chain" | 1 end-marker bit | zeros to the byte boundary: the decoder finds the marker as the highest set
  *              bit of the region's last byte (which is never zero), takes the 9 bits below it and reads the main bits down from there.
@@ -172,8 +189,10 @@ long orc_stream_pairs(const int16_t *planes, int H, int W, const int16_t minmax[
  * ~6.5, xwide v4 2.3-2.8 (noise) / 4.1 (natural-like, model-drawn) / 5.1 (a 1.5-bit source) of which 1.8 are the 256 lanes' 0.057 bit each (v3:
  * 3.5-4.1 / 5.1-6.6 / 9.8); an empty stream costs 250 / 498 / 994 bytes.
  * M: streams per image, | 0x100 for wide streams, | 0x200 for xwide streams; | 0x1200: xwide streams whose count the ENCODER picks from the image
- * (orc_auto_streams: M is what the image's size gives; expensive last-stage symbols -> M + ceil(M / 3), a last stage too cheap to fill M
- * payloads -> ceil(M / 2)) and writes into the header -- the container is an ordinary xwide v4 container of that count.  Returns total bytes or <0. */
+ * and writes into the header -- the container is an ordinary xwide v4 container of that count.  The rule (orc_auto_streams), with M what the image's
+ * size gives, n the symbols of the last stage and S = the sum over them of 16 - floor(log2 freq):  S >= 11 n -> M' = min(32, M + ceil(M / 3));
+ * else S < 4 n -> M' = ceil(2 M / 3); else M' = M.  Then, if 2 S - n < 2 * 8704 M' (the last stage cannot fill M' payloads of 7,936 bits with a tenth
+ * to spare): M if M' > M and 2 S - n >= 2 * 8704 M, else ceil(M / 2).  n = 0 -> M.  Returns total bytes or <0. */
 int orc_auto_streams(int Mlo, const uint32_t *clow, const uint32_t *chigh, long n);
 long orc_encode_image_rans(const uint8_t *rgb, int H, int W, const orc_weights *wts, int M,
                            uint8_t *out, long cap, int32_t seg_len[49]);

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Randomised HIP-vs-oracle parity hunt (GPU box): random shapes, image kinds, weight perturbations, containers.
 Test infrastructure (it calls the CPU oracle), hence under tests/; not collected by pytest (minutes of GPU time).
-usage: tests/fuzz_parity.py [N_CASES] [SEED] [SUMMARY.json] [xwide] [corrupt]   -- stops at the first mismatch with a reproducer line ("xwide": only the
-256-lane containers, whose tail -- two seeded chains, radix-A seeds -- has the most cases: narrow value ranges, streams shorter than the seeds);
+usage: tests/fuzz_parity.py [N_CASES] [SEED] [SUMMARY.json] [xwide] [corrupt] [ref]   -- stops at the first mismatch with a reproducer line ("xwide": only the
+256-lane containers, whose tail -- two seeded chains, radix-A seeds -- has the most cases: narrow value ranges, streams shorter than the seeds;
+"ref", off by default: every rANS container, clean and corrupted, is also decoded by tests/ref_rans.py, the second reading of the format -- pure Python,
+about a second per 10 kpixel);
 the summary (cases, per-container / per-kind counts, wall time) is what profiles/<round>/fuzz_summary.json holds."""
 import collections, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +19,21 @@ N = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 XWIDE_ONLY = len(sys.argv) > 4 and "xwide" in sys.argv[4:]
 CORRUPT_ALL = len(sys.argv) > 4 and "corrupt" in sys.argv[4:]      # every rANS case also decodes a corrupted copy (default: a third of them)
+REF = len(sys.argv) > 4 and "ref" in sys.argv[4:]                  # the second reading of the rANS formats decodes every rANS container too
+if REF:
+    import ref_rans
+
+
+def ref_decode(ch_b, sh_b, W_o, canonical):
+    """tests/ref_rans.py on one container (CDF rows from the oracle's numerics) -> (uint8 [3, H, W] or None if it refuses, info or the refusal)"""
+    segs = ref_rans.segments(container_to_bytestream_list(ch_b, sh_b))
+    try:
+        planes, info = ref_rans.decode_image(segs, ref_rans.OraclePlanes(segs, W_o), canonical=canonical)
+    except ref_rans.Refused as e:
+        return None, e
+    return orc.unlift(planes), info
+
+
 gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 base = {w: dict(np.load(os.path.join(gold, f"weights_{w}.npz"))) for w in ("rand1337", "trainedlike")}
 t0 = time.time()
@@ -105,6 +122,13 @@ for case in range(N):
     for b in range(B):
         ref = orc.encode_image(imgs[b], W_o) if M == 0 else orc.encode_image_rans(imgs[b], W_o, Mb[b], wide, auto=auto)
         assert container_to_bytestream_list(ch[b], sh[b]) == ref, "BYTES " + tag + f" image {b}"
+        if REF and M != 0:
+            # every check of the format text and every encoder choice re-derived (T, the field, one chain or two; "auto": the count)
+            got2, info = ref_decode(ch[b], sh[b], W_o, canonical=True)
+            assert got2 is not None, "REF REFUSES " + tag + f" image {b}: {info}"
+            assert np.array_equal(got2, imgs[b]), "REF PIXELS " + tag + f" image {b}"
+            assert info["header"]["M"] == (ref_rans.auto_pick(Mb[b], info["last_freqs"]) if auto else Mb[b]), "REF COUNT " + tag + f" image {b}"
+            counts["ref_decoded"] += 1
     if M != 0 and (CORRUPT_ALL or rng.integers(0, 3) == 0):
         # round 5, corrupted containers: bytes of ONE image's streams flipped -> the HIP decoder and the oracle agree on whether the image is malformed
         # (status LLICTI_EFORMAT <=> the oracle's decoder refuses it) and, where neither notices (a flip the integrity checks cannot see), on every pixel;
@@ -136,6 +160,11 @@ for case in range(N):
         except RuntimeError:
             want = None
         assert (st[bsel] != 0) == (want is None), "CORRUPT VERDICT " + tag + f" image {bsel}: hip status {st[bsel]}, oracle {'refuses' if want is None else 'accepts'}"
+        if REF:
+            got2, why = ref_decode(bad[bsel].cpu().numpy(), sh[bsel], W_o, canonical=False)
+            assert (got2 is None) == (want is None), "REF CORRUPT VERDICT " + tag + f" image {bsel}: ref_rans {'refuses: ' + str(why) if got2 is None else 'accepts'}"
+            assert got2 is None or np.array_equal(got2, want), "REF CORRUPT PIXELS " + tag + f" image {bsel}"
+            counts["ref_corrupted"] += 1
         if want is not None:
             assert np.array_equal(got[bsel], want), "CORRUPT PIXELS " + tag + f" image {bsel}"
             counts["corrupt_undetected_same_pixels"] += 1

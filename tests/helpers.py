@@ -85,3 +85,80 @@ def tile_edge_classes(H, W, levels=(0, 1, 2)):
 def all_tile_edge_classes():
     return {(TH, rc, cc, ph, pw) for TH in TILE_ROWS for rc in ("fast", "border") for cc in ("fast_edge", "border_edge", "interior")
             for ph in (0, 1) for pw in (0, 1)}
+
+
+# Frozen config B rANS containers (tests/golden/rans_b_vectors.npz, written by the HIP encoder: tests/golden/make_rans_b_vectors.py):
+# key -> (make_image kind, H, W, seed, config B weight set, xwide streams).  One odd shape, one even.
+B_CORRUPT_BASE = "b_noise_33x40_x3"           # ... whose stream 0 is also flipped bit by bit, with the HIP decoders' verdicts recorded
+B_VECTORS = {"b_noise_33x40_x3": ("noise", 33, 40, 9, "rand1337", 3), "b_smooth_64x96_x2": ("smooth", 64, 96, 9, "trainedlike", 2)}
+
+
+def two_valued_image(H, W, seed=5):
+    """R = B = 100, G in {100, 101}: the Cg channel has exactly two values (A = 2, n = 31 raw symbols per seed)."""
+    r = np.random.default_rng(seed)
+    img = np.full((3, H, W), 100, np.uint8)
+    img[1] += r.integers(0, 2, (H, W)).astype(np.uint8)
+    return img
+
+
+def bw_image(H, W, seed=7):
+    """every sample 0 or 255: the full chroma range (A = 511) from two pixel values"""
+    return (np.random.default_rng(seed).integers(0, 2, (3, H, W)) * 255).astype(np.uint8)
+
+
+def flat_image(H, W):
+    return np.full((3, H, W), 201, np.uint8)
+
+
+# The images of the rANS format tests (tests/test_ref_rans.py, tests/test_hip_ref_rans.py): name -> maker.
+RANS_TEST_IMAGES = {
+    "smooth67": lambda: make_image("smooth", 67, 93, 3), "noise67": lambda: make_image("noise", 67, 93, 3),
+    "smooth33": lambda: make_image("smooth", 33, 64, 4), "noise33": lambda: make_image("noise", 33, 64, 4),
+    "smooth32": lambda: make_image("smooth", 32, 32, 2), "smooth32b": lambda: make_image("smooth", 32, 32, 1), "noise32": lambda: make_image("noise", 32, 32, 1),
+    "smooth64": lambda: make_image("smooth", 64, 96, 6), "noise64": lambda: make_image("noise", 64, 96, 6),
+    "flat33": lambda: flat_image(33, 64), "flat192": lambda: flat_image(192, 192), "two64": lambda: two_valued_image(64, 96), "two67": lambda: two_valued_image(67, 93),
+    "bw33": lambda: bw_image(33, 64), "bw32": lambda: bw_image(32, 32),
+    "b_noise33x40": lambda: make_image("noise", 33, 40, 9),                # (the image of B_VECTORS' corruption base)
+}
+
+
+def corruptions(stream, L, layout, seed, n_state=32, n_main=32):
+    """The fixed, seeded set of single-bit flips of one stream: (name, bit index in the stream's bytes).  Every bit of the bit region's last two
+    bytes, its lowest 64 bits (a v4 stream's spill lies there), n_state seeded positions in the states and n_main in the main bits."""
+    nstate = 31 * L // 8
+    r0 = 16 if layout == "v3" else 0
+    r1 = 8 * (len(stream) - nstate)
+    rng = np.random.default_rng(seed)
+    out = [("top", b) for b in range(max(r0, r1 - 16), r1)]
+    out += [("low", b) for b in range(r0, min(r1, r0 + 64))]
+    out += [("state", int(b)) for b in r1 + rng.choice(8 * nstate, n_state, replace=False)]
+    if r1 - 16 > r0 + 64:
+        out += [("main", int(b)) for b in r0 + 64 + rng.choice(r1 - 16 - r0 - 64, min(n_main, r1 - 16 - r0 - 64), replace=False)]
+    return out
+
+
+def corrupted(bl, stream_index, bit):
+    bad = [list(r) for r in bl]
+    b = bytearray(bad[1][stream_index])
+    b[bit >> 3] ^= 1 << (bit & 7)
+    bad[1][stream_index] = bytes(b)
+    return bad
+
+
+def padded_to_88(packed):
+    """pack_state_dict() of a 60-wide model -> the same model as an 88-wide one: channels 60..87 of every head have zero weights and biases."""
+    out = {}
+    for b, d in packed.items():
+        hw, K0 = int(d["head"]), int(d["K0"])
+        assert hw == 60
+        w0, b0 = np.zeros((4 * 88, K0), np.float32), np.zeros(4 * 88, np.float32)
+        w1, b1 = np.zeros((4 * 88, 88), np.float32), np.zeros(4 * 88, np.float32)
+        w2 = np.zeros((60, 88), np.float32)
+        for g in range(4):
+            w0[g * 88:g * 88 + hw] = d["w0"][g * hw:(g + 1) * hw]
+            b0[g * 88:g * 88 + hw] = d["b0"][g * hw:(g + 1) * hw]
+            w1[g * 88:g * 88 + hw, :hw] = d["w1"][g * hw:(g + 1) * hw]
+            b1[g * 88:g * 88 + hw] = d["b1"][g * hw:(g + 1) * hw]
+        w2[:, :hw] = d["w2"]
+        out[b] = {"K0": K0, "head": 88, "w0": w0, "b0": b0, "w1": w1, "b1": b1, "w2": w2, "b2": np.ascontiguousarray(d["b2"], dtype=np.float32)}
+    return out
