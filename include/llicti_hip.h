@@ -21,6 +21,13 @@
  *     streams (llicti_decode_images with the AC container fans out over two internal streams and joins back on `stream`;
  *     llicti_encode_images with the tuning switch "enc_side_levels" runs its coarse levels on one internal stream and joins back before
  *     the entropy coder)
+ *   - a caller that takes a context from one stream to another orders the two itself (an event or hipStreamWaitEvent, so that the next call
+ *     starts behind the previous one: calls of one context never overlap), as it orders its own buffers -- inputs, outputs and the workspace
+ *     belong to a call until its stream has passed it.  The library orders everything of its own: a call waits on `stream` for a cached
+ *     plan's tables that were uploaded or last used on another stream, forks its internal streams behind `stream` and joins them back onto it
+ *     before it returns, hands a pooled table block to a new plan only once the block's last user has finished, and llicti_check_status /
+ *     llicti_image_status wait for, read and clear on `stream` alone -- no kernel-level, whole-batch or status call uses the null stream unless it
+ *     is given it (tests/test_hip_streams.py)
  *   - every call makes the context's device current for its own duration and restores the caller's current device
  *   - calls that BLOCK the host: llicti_create / llicti_destroy / llicti_set_band_weights (device-wide synchronise:
  *     work in flight may still read the old weights), llicti_check_status and llicti_last_timing (they return

@@ -1393,10 +1393,13 @@ extern "C" int llicti_check_status(llicti_ctx *c, void *stream)
 {
     if (!c) return fail(LLICTI_EINVAL, "null ctx");
     DeviceGuard guard(c);
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    // read and cleared ON `stream`: a synchronous hipMemcpy / hipMemset runs on the null stream and waits for whatever the caller has in flight
+    // there (a caller that keeps the codec on a side stream next to a busy default stream; tests/test_hip_streams.py)
+    hipStream_t s = (hipStream_t)stream;
     int32_t st = 0;
-    HIPCHK(hipMemcpy(&st, c->d_status, 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(c->d_status, 0, 4));
+    HIPCHK(hipMemcpyAsync(&st, c->d_status, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemsetAsync(c->d_status, 0, 4, s));
+    HIPCHK(hipStreamSynchronize(s));
     if (st == LLICTI_EFORMAT) return fail(LLICTI_EFORMAT, "malformed container (header does not match the requested shape, or a stream is too long)");
     if (st == LLICTI_ENOSPACE) return fail(LLICTI_ENOSPACE, "output buffer too small for the encoded streams");
     if (st != 0) return fail(st, "device-side status %d", st);
@@ -1457,8 +1460,8 @@ extern "C" int llicti_image_status(llicti_ctx *c, int32_t *h_status, int n, void
     if (!c || !h_status || n < 1) return fail(LLICTI_EINVAL, "image_status: bad argument");
     DeviceGuard guard(c);
     if (!c->d_img_status || n > c->img_status_n) return fail(LLICTI_EINVAL, "image_status: the last decode held %d images ", c->img_status_n);
+    HIPCHK(hipMemcpyAsync(h_status, c->d_img_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));      // (on `stream` alone, as llicti_check_status)
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipMemcpy(h_status, c->d_img_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LLICTI_OK;
 }
 

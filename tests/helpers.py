@@ -162,3 +162,38 @@ def padded_to_88(packed):
         w2[:, :hw] = d["w2"]
         out[b] = {"K0": K0, "head": 88, "w0": w0, "b0": b0, "w1": w1, "b1": b1, "w2": w2, "b2": np.ascontiguousarray(d["b2"], dtype=np.float32)}
     return out
+
+
+class StreamGate:
+    """Holds a HIP stream busy so that ordering bugs become deterministic (tests/test_hip_streams.py, DESIGN.md "the gate"): hold(stream, ms)
+    enqueues a one-thread spin kernel of about `ms` milliseconds (torch.cuda._sleep; its cycles per millisecond are measured once, with events,
+    when the gate is made) and records two timing events around it.  Whatever is enqueued on the stream afterwards starts when the spin ends;
+    whatever is NOT ordered behind the stream runs while it spins.  The gate feeds the library nothing and needs no hook in it.  A test asserts
+    `end.query() is False` once it has enqueued everything: a gate that ran out before that proves nothing and must fail the test."""
+
+    def __init__(self, torch, device="cuda:0", probe_cycles=4_000_000):
+        self.torch, self.device = torch, torch.device(device)
+        s = torch.cuda.Stream(device=self.device)
+        best = None
+        for _ in range(3):                      # (the first launch pays for loading the kernel)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(s):
+                e0.record()
+                torch.cuda._sleep(probe_cycles)
+                e1.record()
+            e1.synchronize()
+            ms = e0.elapsed_time(e1)
+            best = ms if best is None else min(best, ms)
+        assert best > 0
+        self.cycles_per_ms = probe_cycles / best
+
+    def hold(self, stream, ms):
+        """-> (begin, end): timing events on `stream` around a spin of about `ms` milliseconds; begin.elapsed_time(end) is its measured length
+        once `end` has fired."""
+        torch = self.torch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record()
+            torch.cuda._sleep(int(ms * self.cycles_per_ms))
+            e1.record()
+        return e0, e1
