@@ -102,6 +102,20 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v)
 // fmaf per element (tools/hipchecks/check_mfma4x4.hip)
 #define MFMA1(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
 
+// LDS reads of the tile loop: base register + the instruction's 16-bit offset field, nothing else.  Left to itself
+// the compiler pairs two reads of one base into a ds_read2_b32, whose offsets are 8 bits: unless the pair lies within 1 KB of the base it first
+// adds a literal to the base -- a vector instruction (4 cycles of the issue port the MFMAs need) to save an LDS instruction (a port with room to
+// spare).  lds_at() makes the base opaque in front of the read -- no instruction, the same register -- so that no two reads share a base the
+// compiler can see, and every read is a ds_read_b32 with its offset in the instruction.  (An LDS-address-space pointer: one register.)  The 16-byte
+// bias reads need none of this: a ds_read_b128 is never paired, they take their base as it is.
+typedef const __attribute__((address_space(3))) float lds_cf;
+typedef const __attribute__((address_space(3))) f32x4 lds_cf4;
+__device__ __forceinline__ float lds_at(lds_cf *&p, int off)
+{
+    asm volatile("" : "+v"(p));
+    return p[off];
+}
+
 // priority to switch to when the wave's issued-MFMA count passes a quarter mark of the tile inside (before, after]; -1: none
 constexpr int prio_step(int before, int after, int total)
 {
@@ -231,8 +245,8 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
             for (int k = 0; k < kMyPieces; ++k) {
                 const int u = wave_u + k * (kCnnThreads / 64);                           // wave-uniform: the rest of the address is scalar work
                 if (u < kPieces) {
-                    const int pl = u / kPP, v = u - kPP * pl, q4 = v / 3, t = v - 3 * q4;
-                    const int src = pl / 3, ci = pl - 3 * src;
+                    const int pl = (unsigned)u / kPP, v = u - kPP * pl, q4 = (unsigned)v / 3, t = v - 3 * q4;     // (unsigned: see the note at the ballot in the border path)
+                    const int src = (unsigned)pl / 3, ci = pl - 3 * src;
                     const uint32_t uoff = (uint32_t)(ci * (int)g.plane + (((8 * q4 + src_oi(src)) * g.W + src_oj(src)) << g.lvl)) * 4;     // < 3 planes: 32 bits (check_dims: H, W <= 8160)
                     uint32_t lo;
                     if constexpr (RAGGED) lo = lane_off(t);
@@ -278,16 +292,20 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
         const unsigned rlim = odd_col ? 0u : (unsigned)max(g.h - 2, 0);
         const char *origin = reinterpret_cast<const char *>(base) + (((long)(2 * i0) * g.W + 2 * j0) << g.lvl) * 4;      // (outside the plane where i0 or j0 is -2: an address only with a piece's offsets)
         // which of the wave's pieces are plain: lane k looks at piece k (its first halo row is 4 q4 + t = v + v / 3 for v = 3 q4 + t), one ballot per tile
-        const int uk = wave_u + lb * kWaves, vk = uk % kPP;
+        // (The divisions of stage() are unsigned -- u, v, pl, uk are all >= 0 -- because a signed division by a constant carries two sign-fix
+        // instructions.  Not for speed: tests/test_cnn_border_isa_cpu.py holds this path to its recorded instruction count with no margin, and any
+        // change elsewhere in the kernel made the allocator re-materialise a division's magic constant here instead of keeping it across the
+        // tile loop, one instruction over the record in one instantiation.  The unsigned forms are four vector instructions per border tile below it.)
+        const int uk = wave_u + lb * kWaves, vk = (unsigned)uk % kPP;
         const bool mine = lb < kMyPieces && uk < kPieces;
-        const unsigned plain = (unsigned)__ballot(mine && (unsigned)(i0 + vk + vk / 3) < rlim);
+        const unsigned plain = (unsigned)__ballot(mine && (unsigned)(i0 + vk + (unsigned)vk / 3) < rlim);
         unsigned rest = (unsigned)__ballot(mine) & ~plain;
 #pragma unroll
         for (int k = 0; k < kMyPieces; ++k) {
             if (plain >> k & 1) {
                 const int u = wave_u + k * kWaves;                                      // wave-uniform: the interior path's scalars
-                const int pl = u / kPP, v = u - kPP * pl, q4 = v / 3;
-                const int src = pl / 3, ci = pl - 3 * src;
+                const int pl = (unsigned)u / kPP, v = u - kPP * pl, q4 = (unsigned)v / 3;
+                const int src = (unsigned)pl / 3, ci = pl - 3 * src;
                 const uint32_t uoff = (uint32_t)(ci * (int)g.plane + (((8 * q4 + src_oi(src)) * g.W + src_oj(src)) << g.lvl)) * 4;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(origin + uoff + lt[(k * kWaves) % 3]),
                                                  (__attribute__((address_space(3))) void *)(dst + u * 64), 4, 0, 0);
@@ -296,8 +314,8 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
         while (rest) {
             const int u = wave_u + __builtin_ctz(rest) * kWaves;
             rest &= rest - 1;
-            const int pl = u / kPP, v = u - kPP * pl, q4 = v / 3, t = v - 3 * q4;       // wave-uniform
-            const int src = pl / 3, ci = pl - 3 * src;
+            const int pl = (unsigned)u / kPP, v = u - kPP * pl, q4 = (unsigned)v / 3, t = v - 3 * q4;       // wave-uniform
+            const int src = (unsigned)pl / 3, ci = pl - 3 * src;
             const int thr = 48 - 16 * t;
             const bool up = lb >= thr;
             const int cidx = min(up ? lb - thr : lb + 16 * t, kInCols - 1);
@@ -383,12 +401,14 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 #if CNN_PREFETCH_L0
         {
             float a_c[kMT0], b_c[kNT];
+            // the B fragments' two bases (a k-step's four k are four columns, S = 1, or four rows); every k-step's U is an offset below 64 KB
+            lds_cf *bq = (lds_cf *)(lds_cur + pix0 + q), *bqr = (lds_cf *)(lds_cur + pix0 + q_row);
 #if CNN_REM4X4
             // channels 80..87 of the head: block b = lane >> 2 = (cg, pg): channels 80 + 4 cg + i (A, lane & 3 = i) x pixels
             // 4 pg + j of the wave's 32-pixel row (B, lane & 3 = j); accumulator register i of lane (b, j) = channel
             // 80 + 4 cg + i at pixel 4 pg + j.  One k per instruction, in k order: the same fmaf chain as the 16x16x4 tiles.
             const int rsub = lane & 3, rcg = lane >> 5, rpix = 4 * ((lane >> 2) & 7) + rsub;
-            const float *rb_base = lds_cur + ((wave * kNT) >> 1) * kInPitch + rpix;
+            lds_cf *rb_base = (lds_cf *)(lds_cur + ((wave * kNT) >> 1) * kInPitch + rpix);
             const float *ra_base = lds + PO::w0r + (4 * rcg + rsub) * 4;
             f32x4 dR = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
             if constexpr (kRem && !(CNN_EXP_NO_RELU_BIAS & 2)) dR = *reinterpret_cast<const f32x4 *>(lds + PO::bias0r + 4 * rcg);
@@ -397,16 +417,15 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 #endif
             {
                 constexpr int U = kKTab<BAND, TH>.s[0].U, S = kKTab<BAND, TH>.s[0].S;
-                const float *bp = lds_cur + U + pix0 + (S == 1 ? q : q_row);
 #pragma unroll
-                for (int n = 0; n < kNT; ++n) b_c[n] = bp[(n >> 1) * kInPitch + 16 * (n & 1)];
+                for (int n = 0; n < kNT; ++n) b_c[n] = lds_at(S == 1 ? bq : bqr, U + (n >> 1) * kInPitch + 16 * (n & 1));
 #pragma unroll
                 for (int T = 0; T < kMT0; ++T) a_c[T] = lds[PO::w0 + (T * NK0 + 0) * 64 + lane];
 #if CNN_REM4X4
                 if constexpr (kRem) {
                     ar_c = *reinterpret_cast<const f32x4 *>(ra_base);
 #pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) br_c[kk] = rb_base[U + (S == 1 ? kk : kk * kInPitch)];
+                    for (int kk = 0; kk < 4; ++kk) br_c[kk] = lds_at(rb_base, U + (S == 1 ? kk : kk * kInPitch));
                 }
 #endif
             }
@@ -421,16 +440,15 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 #endif
                 if constexpr (t + 1 < NK0) {       // next k-step's fragments are in flight while this one's MFMAs run
                     constexpr int U = kKTab<BAND, TH>.s[t + 1].U, S = kKTab<BAND, TH>.s[t + 1].S;
-                    const float *bp = lds_cur + U + pix0 + (S == 1 ? q : q_row);
 #pragma unroll
-                    for (int n = 0; n < kNT; ++n) b_n[n] = CNN_EXP_L0_B_ONCE ? b_c[n] : bp[(n >> 1) * kInPitch + 16 * (n & 1)];
+                    for (int n = 0; n < kNT; ++n) b_n[n] = CNN_EXP_L0_B_ONCE ? b_c[n] : lds_at(S == 1 ? bq : bqr, U + (n >> 1) * kInPitch + 16 * (n & 1));
 #pragma unroll
                     for (int T = 0; T < kMT0; ++T) a_n[T] = CNN_EXP_NO_WFRAG ? a_c[T] : lds[PO::w0 + (T * NK0 + t + 1) * 64 + lane];
 #if CNN_REM4X4
                     if constexpr (kRem) {
                         ar_n = CNN_EXP_NO_WFRAG ? ar_c : *reinterpret_cast<const f32x4 *>(ra_base + (t + 1) * 32);
 #pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) br_n[kk] = CNN_EXP_REM_B_ONCE ? br_c[kk] : rb_base[U + (S == 1 ? kk : kk * kInPitch)];
+                        for (int kk = 0; kk < 4; ++kk) br_n[kk] = CNN_EXP_REM_B_ONCE ? br_c[kk] : lds_at(rb_base, U + (S == 1 ? kk : kk * kInPitch));
                     }
 #endif
                 }
@@ -521,9 +539,17 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 
         // ---- layers 1 and 2, interleaved per 16-channel tile: the accumulator registers of one layer ARE
         //      the B fragments of the next (k-step tt of the consumer = tile tt>>2, register tt&3)
+        // Their half of the pack (bias1, w1, bias2, w2) is read through bases of its own, made once per tile here: band 2's pack is 86 KB, and
+        // from the lane's offset into the whole pack everything behind bias1 lies beyond a DS instruction's 16-bit offset -- the 16-row form, at
+        // its 128-register cap, re-derived base + 0x1xxxx in front of every such read (54 vector adds per tile).  From bias1 on every offset is
+        // below 40 KB.  Opaque per tile: left visible, the bases are loop invariants kept in registers across layer 0, which has none to spare.
+        lds_cf *l12 = (lds_cf *)(lds + PO::bias1 + lane);           // weight fragments: lane-linear rows of 64
+        lds_cf *l12q = (lds_cf *)(lds + PO::bias1 + q * 4);         // biases: four floats per lane group
+        asm volatile("" : "+v"(l12), "+v"(l12q));
+        constexpr int oW1 = PO::w1 - PO::bias1, oB2 = PO::bias2 - PO::bias1, oW2 = PO::w2 - PO::bias1;
         f32x4 a2[kNT];
         {
-            const f32x4 bv = (CNN_EXP_NO_RELU_BIAS & 2) ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : *reinterpret_cast<const f32x4 *>(lds + PO::bias2 + q * 4);
+            const f32x4 bv = (CNN_EXP_NO_RELU_BIAS & 2) ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : *reinterpret_cast<lds_cf4 *>(l12q + oB2);
 #pragma unroll
             for (int n = 0; n < kNT; ++n) a2[n] = bv;
         }
@@ -535,7 +561,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
         constexpr int D1 = CNN_PREFETCH_L1;
         float ring1[D1];
 #pragma unroll
-        for (int i = 0; i < D1; ++i) ring1[i] = lds[PO::w1 + i * 64 + lane];
+        for (int i = 0; i < D1; ++i) ring1[i] = l12[oW1 + i * 64];
 #endif
         static_for<kMT>([&](auto Tc) {
             constexpr int T = decltype(Tc)::value;
@@ -546,7 +572,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
             if constexpr (T == 2 * kMT / 3 && CNN_STAGE_SITES > 2) stage_next(3);
             f32x4 a1[kNT];
             {
-                const f32x4 bv = (CNN_EXP_NO_RELU_BIAS & 2) ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : *reinterpret_cast<const f32x4 *>(lds + PO::bias1 + (T * 4 + q) * 4);
+                const f32x4 bv = (CNN_EXP_NO_RELU_BIAS & 2) ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : *reinterpret_cast<lds_cf4 *>(l12q + T * 16);
 #pragma unroll
                 for (int n = 0; n < kNT; ++n) a1[n] = bv;
             }
@@ -554,7 +580,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
             float a2w[4] = { 0.0f, 0.0f, 0.0f, 0.0f };      // this tile's layer-2 fragments: requested now, used 22 k-steps later
             static_for<4>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
-                if constexpr (4 * T + r < kKS1) a2w[r] = CNN_EXP_NO_WFRAG ? ring1[r % D1] : lds[PO::w2 + (4 * T + r) * 64 + lane];
+                if constexpr (4 * T + r < kKS1) a2w[r] = CNN_EXP_NO_WFRAG ? ring1[r % D1] : l12[oW2 + (4 * T + r) * 64];
             });
 #endif
             static_for<kKS1>([&](auto ttc) {
@@ -562,9 +588,9 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 #if CNN_PREFETCH_L1 > 0
                 constexpr int i = T * kKS1 + tt;
                 const float a = ring1[i % D1];
-                if constexpr (i + D1 < kMT * kKS1 && !CNN_EXP_NO_WFRAG) ring1[i % D1] = lds[PO::w1 + (i + D1) * 64 + lane];
+                if constexpr (i + D1 < kMT * kKS1 && !CNN_EXP_NO_WFRAG) ring1[i % D1] = l12[oW1 + (i + D1) * 64];
 #else
-                const float a = lds[PO::w1 + (T * kKS1 + tt) * 64 + lane];
+                const float a = l12[oW1 + (T * kKS1 + tt) * 64];
 #endif
 #pragma unroll
                 for (int n = 0; n < kNT; ++n) a1[n] = MFMA4(a, a0[tt >> 2][n][tt & 3], a1[n]);
@@ -580,7 +606,7 @@ __device__ __forceinline__ void band_params_body(const float *__restrict__ fplan
 #if CNN_PREFETCH_L1 > 0
                     const float a = a2w[r];
 #else
-                    const float a = lds[PO::w2 + (4 * T + r) * 64 + lane];
+                    const float a = l12[oW2 + (4 * T + r) * 64];
 #endif
 #pragma unroll
                     for (int n = 0; n < kNT; ++n) a2[n] = MFMA4(a, a1[n][r], a2[n]);
