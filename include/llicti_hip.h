@@ -205,7 +205,14 @@ int llicti_ac_decode_u16cdf(llicti_ctx *ctx, const uint16_t *d_cdf, int Lp, int 
                                                   container does not depend on the batch, the device or anything coded before.  The container is an ordinary
                                                   LLICTI_MODE_RANS_X(count) container -- its header says which (llicti_header_mode) -- and is decoded as such. */
 
-/* Bytes of device workspace the calls below need for B images of H x W in `mode` (_v: of Hs[b] x Ws[b]). */
+/* The bound on a stream's bits.  The rANS coders keep a stream's bit position in a signed 32-bit word, so a stream takes fewer than 2^28 bytes:
+ * every whole-batch encode, decode and transcode (llicti_encode_images*, llicti_decode_images*, llicti_transcode_images) returns LLICTI_EINVAL for
+ * a call in which one stream's worst case -- 2 bytes per symbol of its share of the image, chunks dealt round-robin, plus fixed terms -- is 2^28
+ * bytes or more; the message names the image, its size, its stream count and the smallest count that fits; the size queries return 0.  An
+ * LLICTI_MODE_RANS_X_AUTO(M) image is held to ceil(M / 2) streams, the fewest its encoder may pick.  Only ONE stream on an image of about 45 M
+ * pixels or more meets it (8160 pixels wide: from 5,489 rows; xwide: 5,488): 8160x8160 takes any mode with two streams or more, and LLICTI_MODE_AC. */
+
+/* Bytes of device workspace the calls below need for B images of H x W in `mode` (_v: of Hs[b] x Ws[b]).  0: a call the library refuses. */
 size_t llicti_workspace_bytes(int B, int H, int W, int mode);
 size_t llicti_workspace_bytes_v(int B, const int *Hs, const int *Ws, int mode);
 size_t llicti_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const int *modes);      /* one mode per image, see llicti_encode_images_vm */

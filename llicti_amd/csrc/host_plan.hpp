@@ -156,6 +156,25 @@ static TileForm choose_tile_form(int n_cu, int tile_rows, int band, COUNT &&coun
 static int rans_byte0(int M, int Q, int nlev = LLICTI_NLEVELS);
 static int rans_pad_hi(int M, int Q);
 
+// Bytes of the slot one rANS stream of an H x W image gets when the image has M streams of 64 Q lanes.  The worst case of one stream: every
+// symbol emits 16 bits; chunks of 64 Q symbols are dealt round-robin, so a stream gets at most ceil(nchunks / M) chunks of every stage; + T, the
+// 31-bit states, slack, zero pad (xwide v4: + the tail's spill and the header field).  build_plan sizes the slots with it, check_stream_bits bounds it.
+static long rans_slot_bytes(int nlev, int H, int W, int M, int Q)
+{
+    const long L = 64 * Q;
+    long syms = 0;
+    for (int lvl = 0; lvl < nlev; ++lvl) {
+        const Geom g = make_geom(1, H, W, lvl);
+        for (int band = 0; band < 3; ++band) {
+            int hc, wc;
+            coded_dims(g, band, &hc, &wc);
+            const long nchunks = ((long)hc * wc + L - 1) / L;
+            syms += 3 * ((nchunks + M - 1) / M * L);      // (the three colours of a band code the same positions)
+        }
+    }
+    return (long)align_up((size_t)(2 * syms + 4 + 8 + Q * RansGeo<1>::kPayBytes + 16 + 64 + (Q == 4 ? kRansSpillMax / 8 + 8 : 0)), 64);
+}
+
 // What a plan is built from, and nothing else: two calls with equal specs get equal plans.
 struct PlanSpec {
     int B = 0;
@@ -304,22 +323,15 @@ static void build_plan(Plan &p, const PlanSpec &sp)
     p.sref.clear();
     p.nstreams = 0;
     if (M > 0) {
-        // worst case of one stream: every symbol emits 16 bits; chunks are dealt round-robin, so a
-        // stream gets at most ceil(nchunks / M) chunks of every stage (one capacity for all: the largest any image's streams need)
-        const int L = 64 * Q;
+        // one slot capacity for all streams: the largest any image's need (rans_slot_bytes)
         const int pay_bytes = Q * RansGeo<1>::kPayBytes;
         p.rslot_cap = 0;
         for (int b = 0; b < B; ++b) {
             const int Mb = p.img[b].M;
             const int Mfew = p.img[b].Mlo ? rans_auto_min(p.img[b].Mlo) : Mb;      // the fewest streams the image may end up with: the longest ones
-            long syms = 0, all_syms = 0;
-            for (int st = 0; st < LLICTI_NSTREAMS; ++st) {
-                const long n = p.desc[(size_t)st * B + b].n;
-                const long nchunks = (n + L - 1) / L;
-                syms += (nchunks + Mfew - 1) / Mfew * L;
-                all_syms += (n + 63) / 64 * 64;
-            }
-            p.rslot_cap = std::max(p.rslot_cap, (int)align_up((size_t)(2 * syms + 4 + 8 + pay_bytes + 16 + 64 + (Q == 4 ? kRansSpillMax / 8 + 8 : 0)), 64));   // + T, the 31-bit states, slack, zero pad (xwide v4: + the tail's spill and the header field)
+            long all_syms = 0;
+            for (int st = 0; st < LLICTI_NSTREAMS; ++st) all_syms += ((long)p.desc[(size_t)st * B + b].n + 63) / 64 * 64;
+            p.rslot_cap = std::max(p.rslot_cap, (int)rans_slot_bytes(nlev, p.img[b].H, p.img[b].W, Mfew, Q));      // (below 2^28: check_stream_bits)
             // container bound: the streams together hold every symbol once (<= 16 bits each, whole chunks), plus per stream T | pad, the
             // 64 final states, a table entry (M > 32) and the byte the bit region rounds up to
             p.max_container = std::max(p.max_container, align_up((size_t)p.img[b].hdr_bytes + (size_t)(2 * all_syms) + (size_t)Mb * (2 + pay_bytes + 4 + 4 + (Q == 4 ? kRansSpillMax / 8 : 0)) + 64, 16));
@@ -639,6 +651,27 @@ static int check_header_grid(const char *who, int nlev, int B, const int *Hs, co
     }
     return 0;
 }
+// The rANS coders keep a stream's bit position in a signed 32-bit word (the encoder's cursor, rans_init_kernel's top and cur, the stage decoders'
+// rpos): a stream's slot -- its worst case, rans_slot_bytes -- stays below 2^28 bytes = 2^31 bits.  An "auto" image is bounded at the fewest
+// streams its encoder may pick.  Only one-stream calls on images of about 45 M pixels reach it (8,160 wide: from 5,488 rows); two streams hold 8160x8160.
+constexpr long kRansSlotMax = 1L << 28;
+static int check_stream_bits(const char *who, int nlev, int B, const int *Hs, const int *Ws, int ME, const std::vector<int> &Ms)
+{
+    if ((ME & 0xFF) == 0) return 0;
+    const int Q = 1 << ((ME >> 8) & 3);
+    for (int b = 0; b < B; ++b) {
+        const int m = Ms.empty() ? (ME & 0x10FF) : Ms[b];
+        const int M = m & 0xFF, Mfew = (m & 0x1000) ? rans_auto_min(M) : M;
+        const long need = rans_slot_bytes(nlev, Hs[b], Ws[b], Mfew, Q);
+        if (need < kRansSlotMax) continue;
+        int fit = Mfew + 1;
+        while (rans_slot_bytes(nlev, Hs[b], Ws[b], fit, Q) >= kRansSlotMax) ++fit;
+        return fail(LLICTI_EINVAL, "%s: image %d is %dx%d; in %d stream%s%s one stream may take %ld bytes, and a stream's bit position is a signed 32-bit word "
+                    "(fewer than 2^28 = %ld bytes per stream): the smallest count that fits is %d", who, b, Ws[b], Hs[b], Mfew, Mfew == 1 ? "" : "s",
+                    (m & 0x1000) ? " (the fewest an \"auto\" encode may pick)" : "", need, kRansSlotMax, fit);
+    }
+    return 0;
+}
 // every container slot of a decode holds at least its image's header
 static int check_in_stride(const char *who, int nlev, int B, const int *Hs, const int *Ws, size_t in_stride)
 {
@@ -666,8 +699,10 @@ static int admit_transcode(int nlev, bool ragged, int B, const int *Hs, const in
     if (int rc = resolve_modes("transcode_images (source)", src_modes, n_src, B, MEs, Mss)) return rc;
     if (int rc = check_model(nlev, "transcode_images (source)", *MEs, Mss)) return rc;
     if (int rc = check_source_modes("transcode_images", "source container", *MEs)) return rc;
+    if (int rc = check_stream_bits("transcode_images (source)", nlev, B, Hs, Ws, *MEs, Mss)) return rc;
     if (int rc = resolve_modes("transcode_images (target)", dst_modes, n_dst, B, MEd, Msd)) return rc;
     if (int rc = check_model(nlev, "transcode_images (target)", *MEd, Msd)) return rc;
+    if (int rc = check_stream_bits("transcode_images (target)", nlev, B, Hs, Ws, *MEd, Msd)) return rc;
     if (int rc = check_transcode_sizes("transcode_images", B, Hs, Ws, *MEs, *MEd, ragged)) return rc;
     return check_header_grid("transcode_images", nlev, B, Hs, Ws);
 }
@@ -678,7 +713,7 @@ static size_t plan_workspace_bytes_vm(int B, const int *Hs, const int *Ws, const
 {
     int ME = 0;
     std::vector<int> Ms;
-    if (check_dims_v(B, Hs, Ws) || resolve_modes("workspace_bytes", modes, n_modes, B, &ME, Ms)) return 0;
+    if (check_dims_v(B, Hs, Ws) || resolve_modes("workspace_bytes", modes, n_modes, B, &ME, Ms) || check_stream_bits("workspace_bytes", nlev, B, Hs, Ws, ME, Ms)) return 0;
     Plan p, q;
     build_plan(p, PlanSpec{ B, Hs, Ws, ME, modes_ptr(Ms), nlev, false });
     build_plan(q, PlanSpec{ B, Hs, Ws, ME, modes_ptr(Ms), nlev, true });      // (llicti_set_tuning("force_ragged"): image blocks at 64-element boundaries)

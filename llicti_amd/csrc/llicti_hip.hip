@@ -868,6 +868,7 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
     std::vector<int> Ms;
     if (int rc = resolve_modes("encode_images", modes, n_modes, B, &ME, Ms)) return rc;
     if (int rc = check_model(c->nlev, "encode_images", ME, Ms)) return rc;
+    if (int rc = check_stream_bits("encode_images", c->nlev, B, Hs, Ws, ME, Ms)) return rc;
     if (int rc = check_header_grid("encode_images", c->nlev, B, Hs, Ws)) return rc;
     const bool autoM = (ME & 0x1000) != 0;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
@@ -1200,6 +1201,7 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
     std::vector<int> Ms;
     if (int rc = resolve_modes("decode_images", modes, n_modes, B, &ME, Ms)) return rc;
     if (int rc = check_model(c->nlev, "decode_images", ME, Ms)) return rc;
+    if (int rc = check_stream_bits("decode_images", c->nlev, B, Hs, Ws, ME, Ms)) return rc;
     std::vector<PixGeo> pix;
     if (px) {
         std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes

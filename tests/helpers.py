@@ -197,3 +197,28 @@ class StreamGate:
             torch.cuda._sleep(int(ms * self.cycles_per_ms))
             e1.record()
         return e0, e1
+
+
+def crop_windows(img, y0, x0, ch=None, cw=None, margin=2, levels=5):
+    """A crop of a large image that the CPU oracle can afford, and where the crop's band grids equal the image's (tests/test_large_cpu.py holds the
+    rule on the oracle; tests/test_hip_large.py uses it on images the oracle cannot run whole).  The band CNN is local -- a 5x5 window of its band
+    grid -- so the crop img[:, y0:y0 + ch, x0:x0 + cw], with y0 and x0 multiples of 32 (every level's grid then starts on a grid position of the
+    image's) and each side either ending at the image's edge (ch / cw None: the true border and its odd-edge pad are inside the crop) or a
+    multiple of 32 long, has bit-equal band_params from `margin` positions inwards of every side the crop CUT; a side that is the image's own needs none.
+    -> (crop, [per level: (rows of the image's grid, columns of it, rows of the crop's grid, columns of it)], slices)."""
+    H, W = img.shape[-2:]
+    ch = H - y0 if ch is None else ch
+    cw = W - x0 if cw is None else cw
+    assert y0 % 32 == 0 and x0 % 32 == 0 and 0 < ch <= H - y0 and 0 < cw <= W - x0
+    assert (y0 + ch == H or ch % 32 == 0) and (x0 + cw == W or cw % 32 == 0)
+    crop = img[..., y0:y0 + ch, x0:x0 + cw]
+    wins = []
+    for lvl in range(levels):
+        st = 2 << lvl                                            # pixels per position of the level's band grids
+        gh, gw = -(-(-(-ch // (st // 2))) // 2), -(-(-(-cw // (st // 2))) // 2)      # (ceil(ceil(n / 2^lvl) / 2): the grid of the crop)
+        oy, ox = y0 // st, x0 // st
+        t, l = (margin if y0 else 0), (margin if x0 else 0)
+        b, r = (margin if y0 + ch < H else 0), (margin if x0 + cw < W else 0)
+        assert gh - t - b > 0 and gw - l - r > 0, "the crop is too small for this margin at level %d" % lvl
+        wins.append((slice(oy + t, oy + gh - b), slice(ox + l, ox + gw - r), slice(t, gh - b), slice(l, gw - r)))
+    return crop, wins

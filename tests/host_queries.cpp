@@ -3,6 +3,7 @@
 //   - stdout is compared byte for byte with tests/golden/host_queries.txt (tests/test_host_cpu.py), which was recorded BEFORE the host layer's
 //     rules were given single homes: a change of the host layer that moves a workspace size, a container bound, a plan's `uniform` form or a
 //     cache key shows up as a differing line;
+//   - the bound on a stream's bits (check_stream_bits) is walked to its exact boundary in every lane kind; the heights found are recorded lines too;
 //   - every admission function is then called with one faulty input per rule: LLICTI_EINVAL, and the message starts with the caller's prefix.
 // tests/sanitize_host.sh runs it under AddressSanitizer + UBSan too.
 #include <stdio.h>
@@ -90,6 +91,61 @@ static void queries()
             printf("L%d %dx%d: max container %zu\n", nlev, hw.first, hw.second, plan_max_container_bytes(hw.first, hw.second, nlev));
 }
 
+// The bound on a stream's bits (check_stream_bits): a slot of 2^28 bytes or more is refused.  The boundary is FOUND with the rule and then held
+// against the plan builder's own slot size and against the 32-bit bit position the rule protects; the heights go to stdout, into the recorded answers.
+static bool admits(int H, int W, int mode, int nlev = LLICTI_NLEVELS)
+{
+    const int ME = mode_streams(mode);
+    return check_dims(1, H, W) == 0 && check_stream_bits("encode_images", nlev, 1, &H, &W, ME, {}) == 0;
+}
+static long slot_of(int H, int W, int mode)
+{
+    Plan p;
+    build_plan(p, PlanSpec{ 1, &H, &W, mode_streams(mode), nullptr, LLICTI_NLEVELS, false });
+    return p.rslot_cap;
+}
+static void stream_bits()
+{
+    const int W = 8160;
+    const struct { const char *name; int base; } kinds[3] = { { "rans", 0x100 }, { "wide", 0x300 }, { "xwide", 0x500 } };
+    for (const auto &k : kinds) {
+        const int one = k.base | 1, two = k.base | 2;
+        // the largest image: refused in one stream, admitted in two -- by the rule, the size queries and both sides of a transcode
+        REQUIRE(!admits(8160, 8160, one) && admits(8160, 8160, two));
+        const int H8 = 8160;
+        g_err.clear();
+        REQUIRE(plan_workspace_bytes(1, 8160, 8160, one) == 0 && g_err.find("image 0 is 8160x8160") != std::string::npos);
+        REQUIRE(g_err.find("in 1 stream ") != std::string::npos && g_err.find("the smallest count that fits is 2") != std::string::npos);
+        REQUIRE(plan_workspace_bytes(1, 8160, 8160, two) > 0 && plan_workspace_bytes_v(1, &H8, &H8, one) == 0 && plan_workspace_bytes_vm(1, &H8, &H8, &one, 1) == 0);
+        REQUIRE(plan_transcode_workspace_bytes(1, &H8, &H8, &one, 1, &two, 1) == 0 && plan_transcode_workspace_bytes(1, &H8, &H8, &two, 1, &one, 1) == 0);
+        REQUIRE(plan_transcode_workspace_bytes(1, &H8, &H8, &two, 1, &two, 1) > 0 && plan_transcode_workspace_bytes(1, &H8, &H8, &ac, 1, &two, 1) > 0);
+        // the exact boundary at W = 8160: the largest H one stream still takes
+        int H = 32;
+        while (H < 8160 && admits(H + 1, W, one)) ++H;
+        REQUIRE(H < 8160 && admits(H, W, one) && !admits(H + 1, W, one));
+        for (int h = H + 1; h <= 8160; h += 97) REQUIRE(!admits(h, W, one));                      // (monotone: nothing above it slips through)
+        const long fits = slot_of(H, W, one), over = slot_of(H + 1, W, one);
+        REQUIRE(fits < (1L << 28) && over >= (1L << 28));                                          // the plan's own slot, on either side of 2^28 bytes
+        REQUIRE(8 * fits <= 0x7FFFFFFFL && 8 * over > 0x7FFFFFFFL);                                // ... which is where the bit position leaves a signed int
+        REQUIRE(plan_workspace_bytes(1, H, W, one) > 0 && plan_workspace_bytes(1, H + 1, W, one) == 0 && plan_workspace_bytes(1, H + 1, W, two) > 0);
+        printf("stream bits %s: 8160x8160 refused in 1 stream, admitted in 2; W=8160, 1 stream: H=%d admitted (slot %ld), H=%d refused (slot %ld)\n", k.name, H, fits, H + 1, over);
+    }
+    // an "auto" image is bounded at the fewest streams its encoder may pick: size rule 2 -> 1 .. 3 streams
+    REQUIRE(!admits(8160, 8160, LLICTI_MODE_RANS_X_AUTO(2)) && !admits(8160, 8160, LLICTI_MODE_RANS_X_AUTO(1)) && admits(8160, 8160, LLICTI_MODE_RANS_X_AUTO(3)));
+    // one image of a batch is enough, and the message names it; per-image modes are read per image
+    const int Hs[3] = { 96, 8160, 64 }, Ws[3] = { 160, 8160, 64 };
+    const int x1 = LLICTI_MODE_RANS_X(1), per_ok[3] = { x1, x4, x1 }, per_bad[3] = { x4, x1, x4 };
+    int ME = 0;
+    std::vector<int> Ms;
+    g_err.clear();
+    REQUIRE(plan_workspace_bytes_v(3, Hs, Ws, x1) == 0 && g_err.find("image 1 is 8160x8160") != std::string::npos);
+    REQUIRE(plan_workspace_bytes_vm(3, Hs, Ws, per_ok, 3) > 0 && plan_workspace_bytes_vm(3, Hs, Ws, per_bad, 3) == 0);
+    REQUIRE(resolve_modes("decode_images", per_bad, 3, 3, &ME, Ms) == 0 && check_stream_bits("decode_images", LLICTI_NLEVELS, 3, Hs, Ws, ME, Ms) == LLICTI_EINVAL);
+    REQUIRE(g_err.compare(0, 15, "decode_images: ") == 0);
+    // the reference format has no rANS stream; config B's two levels hold 3/4 of the symbols: the same rule, its own boundary (its header admits at most 1020 pixels a side anyway)
+    REQUIRE(admits(8160, 8160, ac) && admits(1020, 1020, x1, kLevelsB));
+}
+
 // One faulty input per admission rule: the code, and the caller's prefix in front of the reason.
 static bool refused(int rc, const char *who)
 {
@@ -149,6 +205,7 @@ static void refusals()
 int main()
 {
     queries();
+    stream_bits();
     refusals();
     return 0;
 }

@@ -158,7 +158,9 @@ int main()
                     check_plan(p, B, Hs.data(), Ws.data(), ME);
                     REQUIRE(p.uniform == !ragged);
                 }
-                REQUIRE(plan_workspace_bytes(B, sh[0], sh[1], mode) > 0);
+                // (8160x8160 in ONE stream: a stream's bits would pass a signed 32-bit cursor -- check_stream_bits refuses, the size query answers 0)
+                const bool one_stream_8160 = sh[0] == 8160 && sh[1] == 8160 && (ME & 0xFF) == 1;
+                REQUIRE((plan_workspace_bytes(B, sh[0], sh[1], mode) > 0) == !one_stream_8160);
             }
     for (auto &sh : shapes) REQUIRE(plan_max_container_bytes(sh[0], sh[1]) >= 17);
     // mixed-size plans: random batches, every tile-form tuning, odd compute-unit counts
@@ -193,6 +195,58 @@ int main()
             build_plan(q, PlanSpec{ B, Hs.data(), Ws.data(), mode_streams(mode), nullptr, LLICTI_NLEVELS, false, off.data() });
             check_plan(q, B, Hs.data(), Ws.data(), mode_streams(mode));
             REQUIRE(!q.uniform && q.rgb_bytes <= pos);
+        }
+    }
+    // the LARGE plans of tests/test_hip_large.py: offsets past 2^32 bytes and elements inside one workspace, and the largest image the format takes.
+    // UBSan is what would notice a signed overflow of an `int` or `long` product in the plan builder; every byte quantity the kernels keep in 32
+    // bits is bounded here at these sizes.
+    {
+        auto large = [&](int B, const std::vector<int> &Hc, const std::vector<int> &Wc, const std::vector<int> &modes_c) {
+            std::vector<int> Hs(B), Ws(B), modes(B);
+            for (int b = 0; b < B; ++b) { Hs[b] = Hc[b % Hc.size()]; Ws[b] = Wc[b % Wc.size()]; modes[b] = modes_c[b % modes_c.size()]; }
+            int ME = 0;
+            std::vector<int> Ms;
+            REQUIRE(check_dims_v(B, Hs.data(), Ws.data()) == 0 && resolve_modes("large", modes.data(), B, B, &ME, Ms) == 0);
+            REQUIRE(check_stream_bits("large", LLICTI_NLEVELS, B, Hs.data(), Ws.data(), ME, Ms) == 0);
+            const size_t ws = plan_workspace_bytes_vm(B, Hs.data(), Ws.data(), modes.data(), B);
+            for (int ragged = 0; ragged < 2; ++ragged) {
+                if (ragged && ME == 0 && B > 1) continue;
+                Plan p;
+                build_plan(p, PlanSpec{ B, Hs.data(), Ws.data(), ME, modes_ptr(Ms), LLICTI_NLEVELS, ragged != 0 });
+                ++n_plans;
+                REQUIRE(p.total <= ws && p.B == B);
+                // 32-bit quantities of the coders: a slot's bytes x 8 and a stream's symbols fit a signed int; AC slots likewise
+                REQUIRE(p.rslot_cap >= 0 && (long)p.rslot_cap < kRansSlotMax && 8L * p.rslot_cap <= 0x7FFFFFFFL);
+                for (const StreamDesc &d : p.desc) REQUIRE(d.n >= 0 && d.n <= 4080 * 4080 && d.cap >= 0 && 8L * (d.cap + 16) <= 0x7FFFFFFFL && d.pair_off >= 0);
+                for (int b = 0; b < B; ++b) REQUIRE(p.img[b].pix_off >= 0 && p.img[b].rgb_off >= 0 && p.img[b].plane == (long)Hs[b] * Ws[b]);
+                REQUIRE(p.max_container < (1u << 31));                              // segment lengths are int32
+                for (int lvl = 0; lvl < LLICTI_NLEVELS; ++lvl) {
+                    const Geom &g = p.geo[(size_t)lvl * B + (B - 1)];
+                    REQUIRE(g.par_off >= 0 && (size_t)g.par_off + (size_t)g.h * g.w * 64 == p.lev_floats[lvl]);
+                    REQUIRE((size_t)g.h * g.w * 64 * sizeof(float) <= (17ull << 28));      // ONE image's outputs of a level: below 2^32 + 2^28 bytes, what band_cnn.hpp's 32-bit offsets are argued over
+                }
+                if (!p.uniform) for (int k = 0; k < LLICTI_NLEVELS * 3; ++k) REQUIRE(p.run[k].off + (size_t)p.run[k].n_tiles <= p.tiles.size());
+                if (B <= 64) check_plan(p, B, Hs.data(), Ws.data(), ME & 0x3FF, (Ms.empty() || (ME & 0x1000)) ? nullptr : Ms.data());
+            }
+            return ws;
+        };
+        const int x2 = 0x500 | 2, x128 = 0x500 | 128, xa4 = 0x10500 | 4, xa3 = 0x10500 | 3;
+        // (c) 3,712 images of 256x384: the timed container of that size ("auto", size rule 4), four narrow streams, the reference format; mixed sizes
+        REQUIRE(large(3712, { 256 }, { 384 }, { xa4 }) > (4ull << 30));
+        REQUIRE(large(3712, { 256 }, { 384 }, { 0x100 | 4 }) > (4ull << 30));
+        REQUIRE(large(3712, { 256 }, { 384 }, { 0 }) > (4ull << 30));
+        REQUIRE(large(3712, { 256, 250, 192 }, { 384, 391, 512 }, { xa4, xa3, xa4 }) > (4ull << 30));
+        // (b) the batch whose CNN outputs pass 2^32 elements, as a whole-batch plan
+        REQUIRE(large(928, { 512 }, { 768 }, { 0x500 | 16 }) > (4ull << 30));
+        // (d) the largest image and its odd neighbour: the fewest streams the rule admits, and what container "auto" gives that size
+        for (int mode : { x2, x128 }) {
+            REQUIRE(large(1, { 8160 }, { 8160 }, { mode }) > (4ull << 30));
+            REQUIRE(large(1, { 8159 }, { 8157 }, { mode }) > (4ull << 30));
+        }
+        // ... and one stream is refused in every lane kind, by the size query too
+        for (int mode : { 0x100 | 1, 0x300 | 1, 0x500 | 1, 0x10500 | 1, 0x10500 | 2 }) {
+            const int H = 8160, W = 8160, ME = mode_streams(mode);
+            REQUIRE(check_stream_bits("large", LLICTI_NLEVELS, 1, &H, &W, ME, {}) == LLICTI_EINVAL && plan_workspace_bytes(1, H, W, mode) == 0);
         }
     }
     // bad arguments: rejected, never indexed with
