@@ -320,7 +320,7 @@ int llicti_decode_images_px(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stri
  *             is aligned to 4 elements, element by element otherwise
  *   y0, x0    host arrays of B window origins in the coordinates of the decoded image -- the REDUCED one for reduce >= 1 (llicti_reduced_dims:
  *             Hr x Wr); NULL = 0.  Image b's window must lie inside it: 0 <= y0[b], y0[b] + Ho <= Hr, 0 <= x0[b], x0[b] + Wo <= Wr
- *             (llicti_tensor_window_ok).  No padding, no resampling
+ *             (llicti_tensor_window_ok).  No padding, no resampling (llicti_decode_images_tensor_resized resamples)
  *   flip      host array of B flags, NULL = none: a set flag mirrors the window, output column j is window column Wo - 1 - j
  *   mean, std host arrays of 3 floats (R, G, B); both NULL = no normalisation
  * ARITHMETIC, to the operation (torchvision's ToTensor + Normalize on the CPU, bit for bit): x = (float)v / 255.0f, one IEEE fp32 division; with
@@ -344,6 +344,49 @@ int llicti_decode_images_tensor(llicti_ctx *ctx, const uint8_t *d_in, size_t in_
                                 void *d_workspace, size_t workspace_bytes,
                                 void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
                                 const float *mean, const float *std, void *stream);
+/* RESIZED CROPS: llicti_decode_images_tensor with a resampling step in the decode's last kernel -- image b's source BOX (origin y0, x0, extent
+ * hs x ws, in the coordinates of the decoded image: the REDUCED one for reduce >= 1, source pixel (y, x) being plane pixel (y << reduce, x << reduce))
+ * is resampled to Ho x Wo, flipped, normalised and written as out[b][3][Ho][Wo]: torchvision's RandomResizedCrop + flip + ToTensor + Normalize
+ * on a batch of MIXED sizes in one call.  Containers, modes, reduce, workspace, d_out, dtype, flip, mean, std, status words and the integrity rule
+ * are llicti_decode_images_tensor's; the plan is the one llicti_decode_images_reduced builds for the same sizes, modes and reduce with tight
+ * placement.  Boxes, flips, output size and the filter flag are KERNEL ARGUMENTS of the last kernel (two packed words per image, 128 images per
+ * launch), no part of the plan or its key: a loader that draws new boxes for every batch neither allocates device memory, synchronises nor
+ * builds a plan.  A reduced decode is a DECIMATION (every 2^reduce-th pixel, no low-pass): it aliases; the filter below works on what is decoded.
+ *   y0, x0    host arrays of B box origins, NULL = 0
+ *   hs, ws    host arrays of B box extents, NULL = the whole decoded image from the origin (Hr - y0[b], Wr - x0[b]; llicti_reduced_dims)
+ *   Ho, Wo    1 .. 8160
+ *   antialias 1: the triangle filter is widened by the scale when the box shrinks (PIL, torch antialias=True); then hs <= 4 Ho and ws <= 4 Wo
+ *             (at most 9 taps per axis) -- a larger scale is LLICTI_EINVAL: raise reduce.  0: two taps per axis at every scale (plain bilinear)
+ * ARITHMETIC, to the operation: every value fp32, every operation rounded once, no contraction.  Per axis, n the box extent, m the output
+ * extent, i an output index:
+ *   scale   = (float)n / (float)m
+ *   support = (antialias && scale > 1) ? scale : 1
+ *   inv     = 1 / support
+ *   center  = scale * ((float)i + 0.5f)
+ *   lo      = max(0, (int)((center - support) + 0.5f))            (the conversion truncates)
+ *   hi      = min(n, (int)((center + support) + 0.5f))
+ *   t_k     = max(0, 1 - |(((float)k - center) + 0.5f) * inv|)    k = lo .. hi - 1
+ *   total   = t_lo + t_lo+1 + ...                                 (left to right, from +0)
+ *   w_k     = t_k / total
+ * A channel of output pixel (i, j): p = the 8-bit value after the inverse YCoCg-R, as float; for every row tap a, h_a = sum over the column
+ * taps b of w^x_b * p[a][b] (left to right from +0, product then sum); v = sum over a of w^y_a * h_a (the same way); x = v / 255.0f; then
+ * (x - mean[c]) / std[c] and the rounding to dtype as llicti_decode_images_tensor.  A flipped image is the unflipped result mirrored: output
+ * column j holds the value of column Wo - 1 - j.  This is F.interpolate(mode="bilinear", align_corners=False, antialias=...) up to fp32
+ * rounding (tests/test_resize_cpu.py bounds it); at n == m the weights are 1 and 0, so a box of Ho x Wo gives the BYTES of
+ * llicti_decode_images_tensor for the same window.
+ * LLICTI_EINVAL before anything is launched, naming the image: a box with hs or ws < 1, a box that leaves the decoded image, Ho or Wo outside
+ * 1 .. 8160, antialias not 0 or 1, antialias = 1 with hs > 4 Ho or ws > 4 Wo, and everything llicti_decode_images_tensor refuses.
+ * Host helpers (no device needed): llicti_resize_window_ok -- 1 if the call takes that box of an H x W image at `reduce` for that output size and
+ * flag, else 0; llicti_resize_axis -- the taps of output index i (0 .. m - 1) of an axis: returns their count, writes the first source index to
+ * *lo and the weights of taps lo, lo + 1, ... to w[0 .. cap - 1] (zeros behind the last tap; a count above cap is cut, the weights stay those
+ * of the full sum); 0 for n or m < 1 or i outside 0 .. m - 1.  It is compiled from the function the kernel calls. */
+int llicti_resize_window_ok(int H, int W, int reduce, int y0, int x0, int hs, int ws, int Ho, int Wo, int antialias);
+int llicti_resize_axis(int n, int m, int antialias, int i, int *lo, float *w, int cap);
+int llicti_decode_images_tensor_resized(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                        int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                        void *d_workspace, size_t workspace_bytes,
+                                        void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
+                                        const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream);
 /* llicti_encode_images_vm on planar float32: image b's [3][Hs[b]][Ws[b]] block at ELEMENT offset x_off[b] of d_x (NULL = the blocks back to back
  * in call order).  A sample x becomes the pixel value v = (int)rintf(x * 255.0f) -- one rounded fp32 product, rounded half to even
  * (torch.round) --, clamped to 0 .. 255, a NaN gives 0; containers and segment lengths are byte for byte those of the uint8 call on v, under

@@ -76,6 +76,9 @@ _SIGS = {
     "llicti_tensor_elem_bytes": (_i, [_i]),
     "llicti_tensor_window_ok": (_i, [_i] * 7),
     "llicti_decode_images_tensor": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "llicti_resize_window_ok": (_i, [_i] * 10),
+    "llicti_resize_axis": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_float), _i]),
+    "llicti_decode_images_tensor_resized": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "llicti_encode_images_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_transcode_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i]),

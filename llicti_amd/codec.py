@@ -276,6 +276,55 @@ def tensor_window_ok(H, W, reduce, y0, x0, Ho, Wo) -> bool:
     return bool(_lib.lib().llicti_tensor_window_ok(int(H), int(W), int(reduce), int(y0), int(x0), int(Ho), int(Wo)))
 
 
+RESIZE_BOX_SLICE = 128         # images per launch of the resized decode's last kernel (kResizeBoxMax: a larger batch takes several launches)
+RESIZE_TAP_MAX = 9             # taps per axis that kernel is compiled for (kResizeTapMax)
+
+
+def resize_window_ok(H, W, reduce, y0, x0, hs, ws, Ho, Wo, antialias=True) -> bool:
+    """Whether decode_tensor_resized takes the hs x ws box at (y0, x0) of an H x W image decoded at `reduce` for an Ho x Wo output
+    (llicti_resize_window_ok, works without a device): inside the decoded image, Ho, Wo in 1 .. 8160, and with the filter on a scale of at
+    most 4 per axis."""
+    return bool(_lib.lib().llicti_resize_window_ok(int(H), int(W), int(reduce), int(y0), int(x0), int(hs), int(ws), int(Ho), int(Wo), int(antialias)))
+
+
+def resize_axis(n, m, antialias, i, cap=RESIZE_TAP_MAX):
+    """The taps of output index i when n source pixels are resampled to m (llicti_resize_axis: the function the kernel calls, compiled for the
+    host) -> (count, first source index, float32 weights [cap], zeros behind the last tap)."""
+    lo = C.c_int(0)
+    w = np.zeros(int(cap), dtype=np.float32)
+    cnt = int(_lib.lib().llicti_resize_axis(int(n), int(m), int(bool(antialias)), int(i), C.byref(lo), w.ctypes.data_as(C.POINTER(C.c_float)), int(cap)))
+    return cnt, int(lo.value), w
+
+
+def resized_crop_plan(sizes, boxes_full, size, nlevels=5):
+    """The `reduce` a batch of resized crops can be decoded at, and its boxes on that grid.  sizes: (H, W) per image; boxes_full: (y0, x0, h, w)
+    per image in FULL-resolution pixels (torchvision's RandomResizedCrop.get_params order); size = (Ho, Wo) -> (reduce, boxes_reduced) for
+    decode_tensor_resized.  reduce is ONE value per call, as the decoder requires: the largest r in 0 .. nlevels at which EVERY image's box
+    still has at least Ho rows and Wo columns of decoded pixels (0 if none has: the boxes are then magnified).  A box maps to the pixels of the
+    decimated grid that lie inside it: y0r = ceil(y0 / 2^r), y1r = floor((y0 + h - 1) / 2^r) + 1, and the same for the columns.
+    A REDUCED DECODE IS A DECIMATION -- every 2^r-th pixel of the image, taken without a low-pass filter -- so it ALIASES: fine detail of the
+    source folds into the crop, where a full decode followed by an antialiased resize would have averaged it out.  What is gained is that the r
+    finest levels are never decoded (level 0 alone is three quarters of the CNN work).  Pure Python, no device."""
+    Ho, Wo = int(size[0]), int(size[1])
+    sizes, boxes_full = list(sizes), list(boxes_full)
+    assert len(sizes) == len(boxes_full) and Ho >= 1 and Wo >= 1
+
+    def mapped(box, r):
+        y0, x0, h, w = (int(v) for v in box)
+        s = 1 << r
+        y0r, x0r = -(-y0 // s), -(-x0 // s)
+        return y0r, x0r, (y0 + h - 1) // s + 1 - y0r, (x0 + w - 1) // s + 1 - x0r
+
+    for (H, W), (y0, x0, h, w) in zip(sizes, boxes_full):
+        if not (0 <= y0 and 0 <= x0 and h >= 1 and w >= 1 and y0 + h <= H and x0 + w <= W):
+            raise ValueError(f"box (y0 {y0}, x0 {x0}, {h} x {w}) leaves its {H} x {W} image")
+    reduce = 0
+    for r in range(1, int(nlevels) + 1):
+        if all(m[2] >= Ho and m[3] >= Wo for m in (mapped(b, r) for b in boxes_full)):
+            reduce = r
+    return reduce, [mapped(b, reduce) for b in boxes_full]
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -694,6 +743,44 @@ class HipCodec:
         _lib.check(self.L.llicti_decode_images_tensor(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
                                                       _ptr(modes), len(modes), int(reduce), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
                                                       _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
+        return out
+
+    def decode_tensor_resized(self, containers, seg_len, Hs, Ws, mode, size, boxes, dtype=torch.float32, flip=None, mean=None, std=None, antialias=True,
+                              reduce=0, out=None):
+        """decode_tensor with a resampling step (llicti_decode_images_tensor_resized): image b's source box boxes[b] = (y0, x0, hs, ws) -- in the
+        coordinates of the decoded image, the reduced one for reduce >= 1; boxes None: every whole image -- is resampled to size = (Ho, Wo) by
+        the decode's last kernel, flipped, normalised and written into ONE device tensor [B, 3, Ho, Wo] of `dtype`, async: torchvision's
+        RandomResizedCrop + flip + ToTensor + Normalize on a batch of mixed sizes.  The filter is F.interpolate's bilinear one
+        (align_corners=False); antialias=True widens it by the scale when a box shrinks, up to a scale of 4 per axis -- beyond that raise
+        `reduce` (resized_crop_plan picks it).  A box of Ho x Wo gives decode_tensor's bytes.  Boxes, flips, size and flag are per-call data:
+        calls that differ only in them share decode_reduced's cached plan and neither allocate nor synchronise."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.shape[0] == B
+        Ho, Wo = int(size[0]), int(size[1])
+        dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
+        tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
+        ws = self.workspace_v(Hs, Ws, mode)
+        if out is None:
+            out = torch.empty((B, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= B * 3 * Ho * Wo
+        y0 = x0 = bh = bw = None
+        if boxes is not None:
+            bx = np.ascontiguousarray(boxes, dtype=np.int32)
+            assert bx.shape == (B, 4)
+            y0, x0, bh, bw = (np.ascontiguousarray(bx[:, k]) for k in range(4))
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        assert fl is None or fl.shape == (B,)
+        mn = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
+        sd = None if std is None else np.ascontiguousarray(std, dtype=np.float32)
+        assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
+        one, per = self._modes_arg(mode, B)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        aa = int(antialias) if isinstance(antialias, (bool, int, np.integer)) else -1
+        _lib.check(self.L.llicti_decode_images_tensor_resized(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                                                              _ptr(modes), len(modes), int(reduce), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
+                                                              _ptr(y0), _ptr(x0), _ptr(bh), _ptr(bw), _ptr(fl), _ptr(mn), _ptr(sd), aa,
+                                                              _stream_ptr(self.device)))
         return out
 
     def encode_f32(self, x_flat, Hs, Ws, mode, x_off=None, out=None, seg_len=None):

@@ -521,6 +521,43 @@ static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, 
     return 0;
 }
 
+// Resized crops (llicti_decode_images_tensor_resized): the output description as the caller gave it -- hs, ws NULL: the whole decoded image from
+// the origin -- ...
+struct ResizeArgs { int dtype, Ho, Wo; const int *y0, *x0, *hs, *ws; const uint8_t *flip; const float *mean, *std; int antialias; };
+// ... and validated like resolve_tensor's: two packed words per image (ResizeBoxes) and the normalisation constants, kernel arguments all.
+static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ResizeArgs &t, std::vector<uint32_t> &boxes, TensorNorm &nm)
+{
+    if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
+    if (t.Ho < 1 || t.Wo < 1 || t.Ho > 8160 || t.Wo > 8160) return fail(LLICTI_EINVAL, "%s: output size %dx%d (need 1 <= Ho, Wo <= 8160)", who, t.Wo, t.Ho);
+    if (t.antialias != 0 && t.antialias != 1) return fail(LLICTI_EINVAL, "%s: antialias = %d (0: two taps per axis, 1: the triangle filter widened by the scale)", who, t.antialias);
+    if (reduce < 0 || reduce > LLICTI_NLEVELS) return fail(LLICTI_EINVAL, "%s: reduce = %d", who, reduce);
+    if ((t.mean == nullptr) != (t.std == nullptr)) return fail(LLICTI_EINVAL, "%s: mean and std go together (both, or both NULL)", who);
+    memset(&nm, 0, sizeof nm);
+    if (t.mean) {
+        for (int k = 0; k < 3; ++k) {
+            if (!(t.std[k] > 0.0f) || !std::isfinite(t.std[k])) return fail(LLICTI_EINVAL, "%s: std[%d] = %g (need a finite value above zero)", who, k, (double)t.std[k]);
+            nm.mean[k] = t.mean[k]; nm.std[k] = t.std[k];
+        }
+        nm.on = 1;
+    }
+    boxes.assign(2 * (size_t)B, 0u);
+    for (int b = 0; b < B; ++b) {
+        const int Hr = reduced_dim(Hs[b], reduce), Wr = reduced_dim(Ws[b], reduce);
+        const int y0 = t.y0 ? t.y0[b] : 0, x0 = t.x0 ? t.x0[b] : 0;
+        // (a NULL extent with an origin outside the image: the box is empty or negative, refused below)
+        const int hs = t.hs ? t.hs[b] : (int)std::max<long>((long)Hr - y0, -1), ws = t.ws ? t.ws[b] : (int)std::max<long>((long)Wr - x0, -1);
+        if (hs < 1 || ws < 1) return fail(LLICTI_EINVAL, "%s: the box of image %d is %dx%d (need hs, ws >= 1)", who, b, ws, hs);
+        if (!resize_window_ok(Hs[b], Ws[b], reduce, y0, x0, hs, ws, t.Ho, t.Wo, 0))
+            return fail(LLICTI_EINVAL, "%s: the %dx%d box at (y %d, x %d) leaves image %d (%dx%d at reduce %d)", who, ws, hs, y0, x0, b, Wr, Hr, reduce);
+        if (!resize_window_ok(Hs[b], Ws[b], reduce, y0, x0, hs, ws, t.Ho, t.Wo, t.antialias))
+            return fail(LLICTI_EINVAL, "%s: the %dx%d box of image %d shrinks to %dx%d by more than 4 on an axis; the filter (antialias = 1) takes scales up to 4: "
+                        "raise reduce (every step halves the box), or pass antialias = 0", who, ws, hs, b, t.Wo, t.Ho);
+        boxes[2 * (size_t)b] = tensor_win_pack(y0, x0, t.flip && t.flip[b]);
+        boxes[2 * (size_t)b + 1] = resize_ext_pack(hs, ws);
+    }
+    return 0;
+}
+
 // mode: 0 = AC container (torchac-compatible, the reference's format); 0x100 | M = rANS container (v3) with M
 // streams per image, M in 1 .. 32 (one per container segment) or {64, 128} (latency modes: 2 / 4 streams per segment)
 static int mode_streams(int mode)      // -> M, | 0x100 for wide streams (LLICTI_MODE_RANS_WIDE), | 0x200 for xwide streams (LLICTI_MODE_RANS_X); 0: AC container; -1: unknown

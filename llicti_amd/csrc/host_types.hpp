@@ -89,6 +89,49 @@ LLICTI_HD bool tensor_window_ok(int H, int W, int r, int y0, int x0, int Ho, int
     if (H < 1 || W < 1 || r < 0 || r > LLICTI_NLEVELS || Ho < 1 || Wo < 1 || y0 < 0 || x0 < 0) return false;
     return (long)y0 + Ho <= reduced_dim(H, r) && (long)x0 + Wo <= reduced_dim(W, r);
 }
+// Resized crops (llicti_decode_images_tensor_resized): image b's source BOX -- origin, extent, flip, in the coordinates of the decoded image --
+// is resampled to Ho x Wo by unlift_resize_tensor_kernel.  Per call data like the windows above: two packed words per image (origins and
+// extents are at most 8160 < 2^13), kResizeBoxMax images per launch.
+constexpr int kResizeBoxMax = 128;
+constexpr int kResizeTapMax = 9;                                     // taps of one output index along an axis, at a scale of at most 4 with the filter on
+struct ResizeBoxes { uint32_t w[2 * kResizeBoxMax]; };               // [2 b]: y0 | x0 << 13 | flip << 26 (tensor_win_pack); [2 b + 1]: hs | ws << 13
+LLICTI_HD uint32_t resize_ext_pack(int hs, int ws) { return (uint32_t)hs | ((uint32_t)ws << 13); }
+// an hs x ws box at (y0, x0) of an H x W image decoded at reduce r lies inside it, and the resampling to Ho x Wo is one the kernel does: output
+// sizes 1 .. 8160, the filter flag 0 or 1, and with the filter on a scale of at most 4 per axis (hs <= 4 Ho, ws <= 4 Wo: kResizeTapMax taps)
+LLICTI_HD bool resize_window_ok(int H, int W, int r, int y0, int x0, int hs, int ws, int Ho, int Wo, int antialias)
+{
+    if (H < 1 || W < 1 || r < 0 || r > LLICTI_NLEVELS || hs < 1 || ws < 1 || y0 < 0 || x0 < 0) return false;
+    if (Ho < 1 || Wo < 1 || Ho > 8160 || Wo > 8160 || (antialias != 0 && antialias != 1)) return false;
+    if ((long)y0 + hs > reduced_dim(H, r) || (long)x0 + ws > reduced_dim(W, r)) return false;
+    return !antialias || ((long)hs <= 4L * Ho && (long)ws <= 4L * Wo);
+}
+// The triangle filter of one axis (PIL's and torch's bilinear, align_corners = False): a box extent of n source pixels resampled to m, output
+// index i -> the tap count; *lo: the first source index; w[0 .. cap - 1]: the weights of taps lo, lo + 1, ..., zeros behind the last tap.  The
+// rule, every operation fp32 and rounded once (include/llicti_hip.h states it; no contraction: the build's -ffp-contract=off):
+//   scale = n / m; support = (antialias && scale > 1) ? scale : 1; center = scale (i + 0.5); lo = max(0, (int)(center - support + 0.5));
+//   hi = min(n, (int)(center + support + 0.5)); t_k = max(0, 1 - |(k - center + 0.5) / support|); w_k = t_k / (t_lo + ... + t_hi-1).
+// ONE function for the kernel (w in LDS) and llicti_resize_axis (the host): the weights a test reads here are the kernel's.
+LLICTI_HD float resize_tap(int k, float center, float inv)
+{
+    const float d = (((float)k - center) + 0.5f) * inv;
+    const float t = 1.0f - (d < 0.0f ? -d : d);
+    return t > 0.0f ? t : 0.0f;
+}
+LLICTI_HD int resize_axis(int n, int m, int antialias, int i, int *lo_out, float *w, int cap)
+{
+    const float scale = (float)n / (float)m;
+    const float support = (antialias && scale > 1.0f) ? scale : 1.0f;
+    const float inv = 1.0f / support;
+    const float center = scale * ((float)i + 0.5f);
+    int lo = (int)((center - support) + 0.5f), hi = (int)((center + support) + 0.5f);
+    if (lo < 0) lo = 0;
+    if (hi > n) hi = n;
+    float total = 0.0f;
+    for (int k = lo; k < hi; ++k) total = total + resize_tap(k, center, inv);
+    for (int k = 0; k < cap; ++k) w[k] = (lo + k < hi) ? resize_tap(lo + k, center, inv) / total : 0.0f;
+    *lo_out = lo;
+    return hi - lo;
+}
 static Geom make_geom(int B, int H, int W, int lvl)
 {
     Geom g;

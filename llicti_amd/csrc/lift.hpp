@@ -515,3 +515,103 @@ __global__ __launch_bounds__(256) void unlift_tensor_kernel(const int16_t *__res
         }
     }
 }
+
+// The last kernel of llicti_decode_images_tensor_resized, in the place of unlift_tensor_kernel: image b's source box (two words of `boxes`, the
+// call's kernel arguments: origin, flip, extent -- decoded coordinates, plane pixel (y << r, x << r)) resampled to out[b][3][Ho][Wo] by the
+// triangle filter of resize_axis, to the operation of include/llicti_hip.h: per row tap a the sum over the column taps of w^x_b * p, left to
+// right from +0, then the sum over the row taps of w^y_a * h_a, then / 255, normalise and round as unlift_tensor_kernel does.
+// A workgroup owns a 16 x 64 tile of one image's output and computes the weights of its 64 columns and 16 rows ONCE into LDS (zeros behind the
+// last tap: x + 0 * p == x, so the tap loops run to the tile's largest count, a wave-uniform bound, and no thread keeps a weight array); a
+// flipped image's tile takes the weights of the mirrored columns.  A lane then owns 4 consecutive output pixels of one row: one 4-element store
+// per channel when Wo % 4 == 0 and `out` is aligned to 4 elements, element by element otherwise.  Source indices are clamped into the box
+// (only zero-weight taps ever are).  Latches the call's status words exactly as the other unlift kernels do.
+constexpr int kResizeTileH = 16, kResizeTileW = 64;
+template <typename T>
+__global__ __launch_bounds__(256) void unlift_resize_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
+                                                                   int tiles_x, int antialias, const ResizeBoxes boxes, const TensorNorm nm,
+                                                                   const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                                   int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv)
+{
+    __shared__ float wx[kResizeTileW][kResizeTapMax], wy[kResizeTileH][kResizeTapMax];
+    __shared__ int xlo[kResizeTileW], ylo[kResizeTileH], ntap[2];
+    const int b = b0 + blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (b == 0 && status[0] != 0) *latched = status[0];
+        if (img_latched) img_latched[b] = status[status_head + b];
+    }
+    const uint32_t w0 = boxes.w[2 * blockIdx.y], w1 = boxes.w[2 * blockIdx.y + 1];
+    const int y0 = (int)(w0 & 0x1FFFu), x0 = (int)((w0 >> 13) & 0x1FFFu);
+    const bool flip = ((w0 >> 26) & 1u) != 0;
+    const int hs = (int)(w1 & 0x1FFFu), ws = (int)((w1 >> 13) & 0x1FFFu);
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    const int i0 = ty * kResizeTileH, j0 = tx * kResizeTileW;
+    const int tid = (int)threadIdx.x;
+    if (tid < 2) ntap[tid] = 1;
+    __syncthreads();
+    if (tid < kResizeTileW) {
+        const int j = min(j0 + tid, Wo - 1);                       // (columns behind the row's end: any valid one, never stored)
+        const int n = resize_axis(ws, Wo, antialias, flip ? Wo - 1 - j : j, &xlo[tid], wx[tid], kResizeTapMax);
+        atomicMax(&ntap[0], min(n, kResizeTapMax));
+    } else if (tid < kResizeTileW + kResizeTileH) {
+        const int k = tid - kResizeTileW;
+        const int n = resize_axis(hs, Ho, antialias, min(i0 + k, Ho - 1), &ylo[k], wy[k], kResizeTapMax);
+        atomicMax(&ntap[1], min(n, kResizeTapMax));
+    }
+    __syncthreads();
+    const int li = tid >> 4, lj = (tid & 15) * 4;
+    const int i = i0 + li, j = j0 + lj;
+    if (i >= Ho || j >= Wo) return;
+    const int nx = ntap[0], ny = ntap[1];
+    const int n = min(4, Wo - j);
+    const int W = iv[b].W;
+    const long plane = iv[b].plane, oplane = (long)Ho * Wo;
+    const int16_t *src = planes + iv[b].pix_off;
+    const int yl = ylo[li];
+    float v[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k][0] = v[k][1] = v[k][2] = 0.0f;
+    for (int a = 0; a < ny; ++a) {
+        const float wa = wy[li][a];
+        const int16_t *row = src + (long)((y0 + min(yl + a, hs - 1)) << r) * W;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < n) {
+                const int xl = xlo[lj + k];
+                float h[3] = { 0.0f, 0.0f, 0.0f };
+                for (int t = 0; t < nx; ++t) {
+                    const float wb = wx[lj + k][t];
+                    const int16_t *s = row + ((long)(x0 + min(xl + t, ws - 1)) << r);
+                    const int Y = s[0] + 127, Co = s[plane], Cg = s[2 * plane];
+                    const int u = Y - (Cg >> 1);
+                    const int G = Cg + u;
+                    const int Bl = u - (Co >> 1);
+                    const int R = Bl + Co;
+                    h[0] = __fadd_rn(h[0], __fmul_rn(wb, (float)(int)(uint8_t)R));
+                    h[1] = __fadd_rn(h[1], __fmul_rn(wb, (float)(int)(uint8_t)G));
+                    h[2] = __fadd_rn(h[2], __fmul_rn(wb, (float)(int)(uint8_t)Bl));
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[k][c] = __fadd_rn(v[k][c], __fmul_rn(wa, h[c]));
+            }
+        }
+    }
+    TensorQuad<T> q[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float f = __fdiv_rn(v[k][c], 255.0f);
+            if (nm.on) f = __fdiv_rn(__fsub_rn(f, nm.mean[c]), nm.std[c]);
+            q[c].e[k] = tensor_elem<T>(f);
+        }
+    T *o = out + (long)b * 3 * oplane + (long)i * Wo + j;
+    const bool out_vec = (Wo & 3) == 0 && ((uintptr_t)out & (4 * sizeof(T) - 1)) == 0;
+    if (out_vec) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<TensorQuad<T> *>(o + c * oplane) = q[c];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) { o[k] = q[0].e[k]; o[oplane + k] = q[1].e[k]; o[2 * oplane + k] = q[2].e[k]; }
+    }
+}

@@ -6,6 +6,7 @@
 //   lift_kernel / unlift_kernel       integer YCoCg-R lift, min/max, float planes          (HBM bound)
 //   lift_px_kernel / unlift_px_kernel the same on the caller's interleaved, pitched pixels (RGB8 / BGR8 / RGBA8 / BGRA8) (HBM bound)
 //   lift_f32_kernel / unlift_tensor_kernel  planar float32 in, the dense float / half / bfloat16 batch tensor (crop, flip, normalise) out (HBM bound)
+//   unlift_resize_tensor_kernel       the same tensor from a per-image source box RESAMPLED to the output size (triangle filter; a gather)
 //   band_params_kernel<BAND>          interpolator CNN: 3 chained fp32-MFMA GEMMs per pixel tile,
 //                                     weights of one 88-channel head resident in LDS        (MFMA bound)
 //   cdf_pairs_kernel                  encoder: the two table entries per symbol (10 erfc)   (VALU)
@@ -991,13 +992,16 @@ extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, 
 
 // llicti_decode_images_tensor: the validated output description of the call (host_plan.hpp: resolve_tensor) -- kernel arguments of its last kernel
 struct TensorOut { int dtype, Ho, Wo; std::vector<uint32_t> wins; TensorNorm nm; };
+// llicti_decode_images_tensor_resized: the same for a resampled output (resolve_resize) -- two box words per image, the filter flag
+struct ResizeOut { int dtype, Ho, Wo, antialias; std::vector<uint32_t> boxes; TensorNorm nm; };
 
 // llicti_transcode_images: the target plan of the call and its part of the workspace.  decode_stages then launches cdf_pairs_kernel behind every
 // (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
 struct TranscodeTarget { PlanDev *pd; uint8_t *ws; };
 
 static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
-                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce, const TranscodeTarget *tc = nullptr, const TensorOut *tn = nullptr)
+                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce, const TranscodeTarget *tc = nullptr, const TensorOut *tn = nullptr,
+                         const ResizeOut *rz = nullptr)
 {
     const Plan &p = pd->p;
     const int B = p.B, M = p.M, Q = p.Q;
@@ -1145,6 +1149,27 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
         HIPCHK(hipGetLastError());
         return 0;
     }
+    if (rz) {
+        // resized crops (llicti_decode_images_tensor_resized): boxes, flips, output size and filter flag are this call's kernel arguments,
+        // kResizeBoxMax images per launch; a workgroup per 16 x 64 tile of an image's output; the status words as above
+        const int tiles_x = (rz->Wo + kResizeTileW - 1) / kResizeTileW, tiles_y = (rz->Ho + kResizeTileH - 1) / kResizeTileH;
+        ProfSpan span(c, PROF_MISC, s);
+        for (int b0 = 0; b0 < B; b0 += kResizeBoxMax) {
+            const int nb = std::min(kResizeBoxMax, B - b0);
+            ResizeBoxes bx;
+            memset(&bx, 0, sizeof bx);
+            memcpy(bx.w, rz->boxes.data() + 2 * (size_t)b0, 2 * (size_t)nb * sizeof(uint32_t));
+#define LLICTI_RESIZE_LAUNCH(T) unlift_resize_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(planes, (T *)d_rgb, reduce, rz->Ho, rz->Wo, b0, tiles_x, \
+                                                                                                          rz->antialias, bx, rz->nm, status, kStatusHead, \
+                                                                                                          c->d_status, c->d_img_status, d_img)
+            if (rz->dtype == LLICTI_T_F32) LLICTI_RESIZE_LAUNCH(float);
+            else if (rz->dtype == LLICTI_T_F16) LLICTI_RESIZE_LAUNCH(_Float16);
+            else LLICTI_RESIZE_LAUNCH(bf16_bits);
+#undef LLICTI_RESIZE_LAUNCH
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     if (!p.pix.empty()) {
         // interleaved output (llicti_decode_images_px), full size or reduced: one kernel, the window table behind the others
         const int gxp = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
@@ -1192,7 +1217,7 @@ static int reserve_img_status(llicti_ctx *c, int B)
 
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
                         const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0,
-                        const PixArgs *px = nullptr, const TensorArgs *tensor = nullptr)
+                        const PixArgs *px = nullptr, const TensorArgs *tensor = nullptr, const ResizeArgs *resize = nullptr)
 {
     if (!c || !d_in || !d_seg_len || !d_workspace || !d_rgb) return fail(LLICTI_EINVAL, "decode_images: null pointer");
     if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
@@ -1213,6 +1238,11 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
         if (int rc = resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, *tensor, tn.wins, tn.nm)) return rc;
         tn.dtype = tensor->dtype; tn.Ho = tensor->Ho; tn.Wo = tensor->Wo;
     }
+    ResizeOut rz;
+    if (resize) {
+        if (int rc = resolve_resize("decode_images_tensor_resized", B, Hs, Ws, reduce, *resize, rz.boxes, rz.nm)) return rc;
+        rz.dtype = resize->dtype; rz.Ho = resize->Ho; rz.Wo = resize->Wo; rz.antialias = resize->antialias;
+    }
     if (int rc = check_source_modes("decode_images", "container", ME)) return rc;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
@@ -1229,7 +1259,7 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
 
     if (int rc = reserve_img_status(c, B)) return rc;
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce, nullptr, tensor ? &tn : nullptr)) return rc;
+    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce, nullptr, tensor ? &tn : nullptr, resize ? &rz : nullptr)) return rc;
     c->img_status_n = B;
     return LLICTI_OK;
 }
@@ -1296,6 +1326,29 @@ extern "C" int llicti_decode_images_tensor(llicti_ctx *c, const uint8_t *d_in, s
 {
     const TensorArgs tensor{ dtype, Ho, Wo, y0, x0, flip, mean, std };
     return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, (uint8_t *)d_out, nullptr, stream, reduce, nullptr, &tensor);
+}
+
+extern "C" int llicti_resize_window_ok(int H, int W, int reduce, int y0, int x0, int hs, int ws, int Ho, int Wo, int antialias)
+{
+    return resize_window_ok(H, W, reduce, y0, x0, hs, ws, Ho, Wo, antialias) ? 1 : 0;
+}
+// (the host's compile of resize_axis: the function unlift_resize_tensor_kernel calls)
+extern "C" int llicti_resize_axis(int n, int m, int antialias, int i, int *lo, float *w, int cap)
+{
+    if (n < 1 || m < 1 || i < 0 || i >= m || !lo || cap < 0 || (cap > 0 && !w)) return 0;
+    return resize_axis(n, m, antialias ? 1 : 0, i, lo, w, cap);
+}
+
+// (the plan: llicti_decode_images_tensor's -- boxes, flips, output size and filter flag are kernel arguments)
+extern "C" int llicti_decode_images_tensor_resized(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                                   int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                                   void *d_workspace, size_t workspace_bytes,
+                                                   void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
+                                                   const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream)
+{
+    const ResizeArgs resize{ dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, (uint8_t *)d_out, nullptr, stream, reduce, nullptr, nullptr,
+                        &resize);
 }
 
 extern "C" int llicti_encode_images_f32(llicti_ctx *c, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,

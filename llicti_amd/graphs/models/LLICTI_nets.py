@@ -472,10 +472,15 @@ class LLICTI(nn.Module):
         (that flat buffer, Hs, Ws) instead.
         tensor = dict(size=(Ho, Wo), dtype=, origin=, flip=, mean=, std=) (only size is required): the result is ONE device tensor [B,3,Ho,Wo] of
         dtype (float32 by default), every image's window cropped, flipped and normalised by the decode's last kernel (HipCodec.decode_tensor) --
-        the images' sizes may differ.  Not together with pixels= or flat=."""
+        the images' sizes may differ.  Not together with pixels= or flat=.
+        tensor = dict(size=(Ho, Wo), boxes=[(y0, x0, hs, ws), ...], antialias=, dtype=, flip=, mean=, std=): with `boxes` every image's source box
+        (decoded coordinates: the reduced ones for reduce >= 1; codec.resized_crop_plan maps full-resolution boxes and picks reduce) is RESAMPLED
+        to size by that kernel (HipCodec.decode_tensor_resized) -- a random resized crop per image; `origin` does not go with it."""
         if tensor is not None and (pixels is not None or flat):
             raise ValueError("tensor=... gives one dense float tensor: it goes with neither pixels= nor flat=")
         codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
+        if tensor is not None and "boxes" in tensor:
+            return codec.decode_tensor_resized(cont_d, seg_d, Hs, Ws, mode, reduce=reduce, **tensor)      # (an `origin` beside boxes: a TypeError)
         if tensor is not None:
             return codec.decode_tensor(cont_d, seg_d, Hs, Ws, mode, reduce=reduce, **tensor)
         if pixels is not None:
