@@ -387,6 +387,34 @@ int llicti_decode_images_tensor_resized(llicti_ctx *ctx, const uint8_t *d_in, si
                                         void *d_workspace, size_t workspace_bytes,
                                         void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
                                         const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream);
+/* VIEWS: several resized crops per image from ONE decode.  The batch is decoded once -- exactly the launches of llicti_decode_images_reduced for the
+ * same sizes, modes and reduce, with its plan and its key -- and the last kernel then runs once per view: view v of group g is what
+ * llicti_decode_images_tensor_resized writes for image image[v] with that box, flip, size, dtype and flag, to the bit (the ARITHMETIC paragraph
+ * above is the one specification).  A GROUP is a set of views of one output size, dtype and flag, written to ONE dense [n][3][Ho][Wo] tensor;
+ * two crop sizes are two groups of one call (multi-crop: 2 x 224 and 6 x 96 views per image).  The view launches of group 0, then group 1, ...
+ * follow the decode on the same stream.  A group with image == NULL and n == B gives llicti_decode_images_tensor_resized's bytes.
+ * The image index, box and flip of a view are KERNEL ARGUMENTS of the view launches (three packed words per view, 128 views per launch), no
+ * part of the plan or its key: no device allocation, no upload and no synchronisation per call.  Status words are latched for every one of the
+ * B images, those no view names included: llicti_check_status and llicti_image_status report what the resized call reports for the same
+ * containers; the integrity rule is llicti_decode_images_reduced's.  mean, std: one pair for the call, as above.
+ * Nothing is written outside a group's [d_out, d_out + n * 3 * Ho * Wo * elem).  The outputs of different groups MUST NOT OVERLAP, and none may
+ * overlap the workspace; this is NOT checked.
+ * LLICTI_EINVAL before anything is launched, naming the group and the view: G outside 1 .. LLICTI_VIEW_GROUPS_MAX, null groups or d_out, n outside
+ * 1 .. 1,048,576, an image index outside 0 .. B - 1, image == NULL with n != B, and per view, against the view's own image, everything
+ * llicti_decode_images_tensor_resized refuses. */
+#define LLICTI_VIEW_GROUPS_MAX 16
+typedef struct llicti_view_group {
+    void *d_out;                  /* ONE dense [n][3][Ho][Wo] tensor of dtype */
+    int dtype, Ho, Wo, antialias;
+    int n;                        /* views of this group, 1 .. 1,048,576 */
+    const int *image;             /* n image indices in 0 .. B-1: any order, repeats allowed, images may be absent.  NULL: view v is image v, then n == B */
+    const int *y0, *x0, *hs, *ws; /* n each; NULL defaults as in llicti_decode_images_tensor_resized, taken against the view's image */
+    const uint8_t *flip;          /* n flags, NULL = none */
+} llicti_view_group;
+int llicti_decode_images_tensor_views(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                      int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                      void *d_workspace, size_t workspace_bytes,
+                                      const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream);
 /* llicti_encode_images_vm on planar float32: image b's [3][Hs[b]][Ws[b]] block at ELEMENT offset x_off[b] of d_x (NULL = the blocks back to back
  * in call order).  A sample x becomes the pixel value v = (int)rintf(x * 255.0f) -- one rounded fp32 product, rounded half to even
  * (torch.round) --, clamped to 0 .. 255, a NaN gives 0; containers and segment lengths are byte for byte those of the uint8 call on v, under

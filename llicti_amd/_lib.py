@@ -41,6 +41,15 @@ def build(force: bool = False) -> str:
 
 _lib = None
 _vp, _i, _l, _sz = C.c_void_p, C.c_int, C.c_long, C.c_size_t
+VIEW_GROUPS_MAX = 16           # LLICTI_VIEW_GROUPS_MAX
+
+
+class ViewGroup(C.Structure):
+    """llicti_view_group of include/llicti_hip.h: the views of one output size, dtype and flag, written to one dense [n][3][Ho][Wo] tensor"""
+    _fields_ = [("d_out", C.c_void_p), ("dtype", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int), ("antialias", C.c_int), ("n", C.c_int),
+                ("image", C.c_void_p), ("y0", C.c_void_p), ("x0", C.c_void_p), ("hs", C.c_void_p), ("ws", C.c_void_p), ("flip", C.c_void_p)]
+
+
 _SIGS = {
     "llicti_last_error": (C.c_char_p, []),
     "llicti_version": (C.c_char_p, []),
@@ -79,6 +88,7 @@ _SIGS = {
     "llicti_resize_window_ok": (_i, [_i] * 10),
     "llicti_resize_axis": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_float), _i]),
     "llicti_decode_images_tensor_resized": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "llicti_decode_images_tensor_views": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(ViewGroup), _i, _vp, _vp, _vp]),
     "llicti_encode_images_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_transcode_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i]),

@@ -296,6 +296,20 @@ def resize_axis(n, m, antialias, i, cap=RESIZE_TAP_MAX):
     return cnt, int(lo.value), w
 
 
+def _box_on_grid(box, r):
+    """A full-resolution box (y0, x0, h, w) as the pixels of the grid decimated by 2^r that lie inside it (resized_crop_plan states the rule)"""
+    y0, x0, h, w = (int(v) for v in box)
+    s = 1 << r
+    y0r, x0r = -(-y0 // s), -(-x0 // s)
+    return y0r, x0r, (y0 + h - 1) // s + 1 - y0r, (x0 + w - 1) // s + 1 - x0r
+
+
+def _box_must_fit(H, W, box):
+    y0, x0, h, w = box
+    if not (0 <= y0 and 0 <= x0 and h >= 1 and w >= 1 and y0 + h <= H and x0 + w <= W):
+        raise ValueError(f"box (y0 {y0}, x0 {x0}, {h} x {w}) leaves its {H} x {W} image")
+
+
 def resized_crop_plan(sizes, boxes_full, size, nlevels=5):
     """The `reduce` a batch of resized crops can be decoded at, and its boxes on that grid.  sizes: (H, W) per image; boxes_full: (y0, x0, h, w)
     per image in FULL-resolution pixels (torchvision's RandomResizedCrop.get_params order); size = (Ho, Wo) -> (reduce, boxes_reduced) for
@@ -308,21 +322,43 @@ def resized_crop_plan(sizes, boxes_full, size, nlevels=5):
     Ho, Wo = int(size[0]), int(size[1])
     sizes, boxes_full = list(sizes), list(boxes_full)
     assert len(sizes) == len(boxes_full) and Ho >= 1 and Wo >= 1
-
-    def mapped(box, r):
-        y0, x0, h, w = (int(v) for v in box)
-        s = 1 << r
-        y0r, x0r = -(-y0 // s), -(-x0 // s)
-        return y0r, x0r, (y0 + h - 1) // s + 1 - y0r, (x0 + w - 1) // s + 1 - x0r
-
-    for (H, W), (y0, x0, h, w) in zip(sizes, boxes_full):
-        if not (0 <= y0 and 0 <= x0 and h >= 1 and w >= 1 and y0 + h <= H and x0 + w <= W):
-            raise ValueError(f"box (y0 {y0}, x0 {x0}, {h} x {w}) leaves its {H} x {W} image")
+    for (H, W), box in zip(sizes, boxes_full):
+        _box_must_fit(H, W, box)
     reduce = 0
     for r in range(1, int(nlevels) + 1):
-        if all(m[2] >= Ho and m[3] >= Wo for m in (mapped(b, r) for b in boxes_full)):
+        if all(m[2] >= Ho and m[3] >= Wo for m in (_box_on_grid(b, r) for b in boxes_full)):
             reduce = r
-    return reduce, [mapped(b, reduce) for b in boxes_full]
+    return reduce, [_box_on_grid(b, reduce) for b in boxes_full]
+
+
+VIEW_SLICE = 128               # views per launch of the views call's last kernel (kViewMax: a longer group takes several launches)
+
+
+def multi_crop_plan(sizes, groups_full, nlevels=5):
+    """resized_crop_plan for views (decode_tensor_views): several crops per image, of several output sizes, from ONE decode.  sizes: (H, W) per
+    image; groups_full: a list of (size, image_indices, boxes_full) -- size = (Ho, Wo) of the group, image_indices[v] the image view v is cut
+    from (None: view v is image v), boxes_full[v] = (y0, x0, h, w) in FULL-resolution pixels of that image -> (reduce, [boxes_reduced per
+    group]).  reduce is ONE value per call: the largest r in 0 .. nlevels at which EVERY view of EVERY group still has at least Ho x Wo decoded
+    pixels of its group's size in its box (0 if none has) -- the small crops of a multi-crop set decide it.  The box mapping is
+    resized_crop_plan's, and so is what it says about a reduced decode: a DECIMATION, which aliases.  For one group with image_indices None it
+    returns what resized_crop_plan returns.  Pure Python, no device."""
+    sizes = list(sizes)
+    groups = []
+    for size, image, boxes in groups_full:
+        Ho, Wo = int(size[0]), int(size[1])
+        boxes = list(boxes)
+        image = list(range(len(sizes))) if image is None else [int(b) for b in image]
+        assert len(image) == len(boxes) and Ho >= 1 and Wo >= 1
+        for b, box in zip(image, boxes):
+            if not 0 <= b < len(sizes):
+                raise ValueError(f"a view names image {b}: the batch has images 0 .. {len(sizes) - 1}")
+            _box_must_fit(sizes[b][0], sizes[b][1], box)
+        groups.append((Ho, Wo, boxes))
+    reduce = 0
+    for r in range(1, int(nlevels) + 1):
+        if all(m[2] >= Ho and m[3] >= Wo for Ho, Wo, boxes in groups for m in (_box_on_grid(b, r) for b in boxes)):
+            reduce = r
+    return reduce, [[_box_on_grid(b, reduce) for b in boxes] for _, _, boxes in groups]
 
 
 def _ptr(t):
@@ -782,6 +818,60 @@ class HipCodec:
                                                               _ptr(y0), _ptr(x0), _ptr(bh), _ptr(bw), _ptr(fl), _ptr(mn), _ptr(sd), aa,
                                                               _stream_ptr(self.device)))
         return out
+
+    def decode_tensor_views(self, containers, seg_len, Hs, Ws, mode, groups, mean=None, std=None, reduce=0):
+        """Several resized crops per image from ONE decode (llicti_decode_images_tensor_views).  groups: a list of dict(size=(Ho, Wo),
+        image=[...] | None, boxes=[(y0, x0, hs, ws), ...] | None, flip=None, dtype=torch.float32, antialias=True, out=None): view v of a
+        group is what decode_tensor_resized writes for image image[v] (any order, repeats allowed, images may be absent; None: view v is
+        image v) with box boxes[v] (decoded coordinates, the reduced ones for reduce >= 1; None: the whole image), to the bit.  -> a list
+        of one device tensor [n, 3, Ho, Wo] per group, async.  Outputs of different groups must not overlap.  The batch is decoded once;
+        every view costs one more pass of the last kernel.  Image indices, boxes and flips are per-call data: calls that differ only in
+        them share decode_reduced's cached plan and neither allocate nor synchronise.  multi_crop_plan picks reduce."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.shape[0] == B
+        groups = list(groups)
+        ws = self.workspace_v(Hs, Ws, mode)
+        arr = (_lib.ViewGroup * max(len(groups), 1))()
+        outs, keep = [], []
+        for g, spec in enumerate(groups):
+            spec = dict(spec)
+            Ho, Wo = (int(v) for v in spec.pop("size"))
+            image, boxes, flip, out = spec.pop("image", None), spec.pop("boxes", None), spec.pop("flip", None), spec.pop("out", None)
+            dtype, antialias = spec.pop("dtype", torch.float32), spec.pop("antialias", True)
+            if spec:
+                raise TypeError(f"group {g}: unknown keys {sorted(spec)}")
+            dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
+            tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
+            img = None if image is None else np.ascontiguousarray(image, dtype=np.int32)
+            assert img is None or img.ndim == 1
+            n = B if img is None else len(img)
+            if out is None:
+                out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
+            assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= n * 3 * Ho * Wo
+            cols = [None] * 4
+            if boxes is not None:
+                bx = np.ascontiguousarray(boxes, dtype=np.int32)
+                assert bx.shape == (n, 4)
+                cols = [np.ascontiguousarray(bx[:, k]) for k in range(4)]
+            fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+            assert fl is None or fl.shape == (n,)
+            aa = int(antialias) if isinstance(antialias, (bool, int, np.integer)) else -1
+            keep.append((img, cols, fl))                  # (the host arrays live until the call returns)
+            vg = arr[g]
+            vg.d_out, vg.dtype, vg.Ho, vg.Wo, vg.antialias, vg.n = out.data_ptr(), int(dt), Ho, Wo, aa, n
+            vg.image, vg.flip = _ptr(img), _ptr(fl)
+            vg.y0, vg.x0, vg.hs, vg.ws = (_ptr(c) for c in cols)
+            outs.append(out)
+        mn = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
+        sd = None if std is None else np.ascontiguousarray(std, dtype=np.float32)
+        assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
+        one, per = self._modes_arg(mode, B)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        _lib.check(self.L.llicti_decode_images_tensor_views(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                                                            _ptr(modes), len(modes), int(reduce), _ptr(ws), ws.numel(), arr, len(groups),
+                                                            _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
+        return outs
 
     def encode_f32(self, x_flat, Hs, Ws, mode, x_off=None, out=None, seg_len=None):
         """encode_v on planar float32: x_flat is a flat float32 device tensor holding image b's [3][Hs[b]][Ws[b]] block at ELEMENT x_off[b] (None:

@@ -525,7 +525,8 @@ static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, 
 // the origin -- ...
 struct ResizeArgs { int dtype, Ho, Wo; const int *y0, *x0, *hs, *ws; const uint8_t *flip; const float *mean, *std; int antialias; };
 // ... and validated like resolve_tensor's: two packed words per image (ResizeBoxes) and the normalisation constants, kernel arguments all.
-static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ResizeArgs &t, std::vector<uint32_t> &boxes, TensorNorm &nm)
+// (what does not depend on the image: dtype, output size, flag, reduce, mean and std)
+static int resolve_resize_head(const char *who, int reduce, const ResizeArgs &t, TensorNorm &nm)
 {
     if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
     if (t.Ho < 1 || t.Wo < 1 || t.Ho > 8160 || t.Wo > 8160) return fail(LLICTI_EINVAL, "%s: output size %dx%d (need 1 <= Ho, Wo <= 8160)", who, t.Wo, t.Ho);
@@ -540,20 +541,67 @@ static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, 
         }
         nm.on = 1;
     }
+    return 0;
+}
+// (one box, entry k of the call's arrays, against its H x W image: `whose` is how a message names it; -> the two packed words)
+static int resolve_resize_box(const char *who, const char *whose, int H, int W, int reduce, const ResizeArgs &t, int k, uint32_t *words)
+{
+    const int Hr = reduced_dim(H, reduce), Wr = reduced_dim(W, reduce);
+    const int y0 = t.y0 ? t.y0[k] : 0, x0 = t.x0 ? t.x0[k] : 0;
+    // (a NULL extent with an origin outside the image: the box is empty or negative, refused below)
+    const int hs = t.hs ? t.hs[k] : (int)std::max<long>((long)Hr - y0, -1), ws = t.ws ? t.ws[k] : (int)std::max<long>((long)Wr - x0, -1);
+    if (hs < 1 || ws < 1) return fail(LLICTI_EINVAL, "%s: the box of %s is %dx%d (need hs, ws >= 1)", who, whose, ws, hs);
+    if (!resize_window_ok(H, W, reduce, y0, x0, hs, ws, t.Ho, t.Wo, 0))
+        return fail(LLICTI_EINVAL, "%s: the %dx%d box at (y %d, x %d) leaves %s (%dx%d at reduce %d)", who, ws, hs, y0, x0, whose, Wr, Hr, reduce);
+    if (!resize_window_ok(H, W, reduce, y0, x0, hs, ws, t.Ho, t.Wo, t.antialias))
+        return fail(LLICTI_EINVAL, "%s: the %dx%d box of %s shrinks to %dx%d by more than 4 on an axis; the filter (antialias = 1) takes scales up to 4: "
+                    "raise reduce (every step halves the box), or pass antialias = 0", who, ws, hs, whose, t.Wo, t.Ho);
+    words[0] = tensor_win_pack(y0, x0, t.flip && t.flip[k]);
+    words[1] = resize_ext_pack(hs, ws);
+    return 0;
+}
+static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ResizeArgs &t, std::vector<uint32_t> &boxes, TensorNorm &nm)
+{
+    if (int rc = resolve_resize_head(who, reduce, t, nm)) return rc;
     boxes.assign(2 * (size_t)B, 0u);
     for (int b = 0; b < B; ++b) {
-        const int Hr = reduced_dim(Hs[b], reduce), Wr = reduced_dim(Ws[b], reduce);
-        const int y0 = t.y0 ? t.y0[b] : 0, x0 = t.x0 ? t.x0[b] : 0;
-        // (a NULL extent with an origin outside the image: the box is empty or negative, refused below)
-        const int hs = t.hs ? t.hs[b] : (int)std::max<long>((long)Hr - y0, -1), ws = t.ws ? t.ws[b] : (int)std::max<long>((long)Wr - x0, -1);
-        if (hs < 1 || ws < 1) return fail(LLICTI_EINVAL, "%s: the box of image %d is %dx%d (need hs, ws >= 1)", who, b, ws, hs);
-        if (!resize_window_ok(Hs[b], Ws[b], reduce, y0, x0, hs, ws, t.Ho, t.Wo, 0))
-            return fail(LLICTI_EINVAL, "%s: the %dx%d box at (y %d, x %d) leaves image %d (%dx%d at reduce %d)", who, ws, hs, y0, x0, b, Wr, Hr, reduce);
-        if (!resize_window_ok(Hs[b], Ws[b], reduce, y0, x0, hs, ws, t.Ho, t.Wo, t.antialias))
-            return fail(LLICTI_EINVAL, "%s: the %dx%d box of image %d shrinks to %dx%d by more than 4 on an axis; the filter (antialias = 1) takes scales up to 4: "
-                        "raise reduce (every step halves the box), or pass antialias = 0", who, ws, hs, b, t.Wo, t.Ho);
-        boxes[2 * (size_t)b] = tensor_win_pack(y0, x0, t.flip && t.flip[b]);
-        boxes[2 * (size_t)b + 1] = resize_ext_pack(hs, ws);
+        char whose[32];
+        snprintf(whose, sizeof whose, "image %d", b);
+        if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], reduce, t, b, &boxes[2 * (size_t)b])) return rc;
+    }
+    return 0;
+}
+
+// Views (llicti_decode_images_tensor_views): the call's groups as the caller gave them ...
+struct ViewArgs { const llicti_view_group *groups; int G; const float *mean, *std; };
+// ... and one validated group: three packed words per view (ViewSlice), kernel arguments of the group's launches like the boxes above
+struct ViewGroupOut { void *d_out; int dtype, Ho, Wo, antialias, n; std::vector<uint32_t> words; };
+// Every view is held to resolve_resize's rules against the image it names (resolve_resize_head, resolve_resize_box: the same functions, the
+// same words); a refusal names the group and the view.
+static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ViewArgs &a, std::vector<ViewGroupOut> &out, TensorNorm &nm)
+{
+    if (a.G < 1 || a.G > LLICTI_VIEW_GROUPS_MAX) return fail(LLICTI_EINVAL, "%s: %d groups (need 1 .. %d)", who, a.G, LLICTI_VIEW_GROUPS_MAX);
+    if (!a.groups) return fail(LLICTI_EINVAL, "%s: null groups", who);
+    out.assign((size_t)a.G, ViewGroupOut());
+    for (int g = 0; g < a.G; ++g) {
+        const llicti_view_group &vg = a.groups[g];
+        char whose[80];
+        snprintf(whose, sizeof whose, "%s: group %d", who, g);
+        if (!vg.d_out) return fail(LLICTI_EINVAL, "%s: null d_out", whose);
+        if (vg.n < 1 || vg.n > kViewCountMax) return fail(LLICTI_EINVAL, "%s: n = %d views (need 1 .. %d)", whose, vg.n, kViewCountMax);
+        if (!vg.image && vg.n != B) return fail(LLICTI_EINVAL, "%s: image = NULL means view v is image v: n = %d, the batch has %d images", whose, vg.n, B);
+        const ResizeArgs t{ vg.dtype, vg.Ho, vg.Wo, vg.y0, vg.x0, vg.hs, vg.ws, vg.flip, a.mean, a.std, vg.antialias };
+        if (int rc = resolve_resize_head(whose, reduce, t, nm)) return rc;
+        ViewGroupOut &o = out[(size_t)g];
+        o.d_out = vg.d_out; o.dtype = vg.dtype; o.Ho = vg.Ho; o.Wo = vg.Wo; o.antialias = vg.antialias; o.n = vg.n;
+        o.words.assign(3 * (size_t)vg.n, 0u);
+        for (int v = 0; v < vg.n; ++v) {
+            const int b = vg.image ? vg.image[v] : v;
+            if (b < 0 || b >= B) return fail(LLICTI_EINVAL, "%s: view %d of group %d names image %d (the batch has images 0 .. %d)", who, v, g, b, B - 1);
+            snprintf(whose, sizeof whose, "view %d of group %d (image %d)", v, g, b);
+            if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], reduce, t, v, &o.words[3 * (size_t)v])) return rc;
+            o.words[3 * (size_t)v + 2] = (uint32_t)b;
+        }
     }
     return 0;
 }

@@ -96,6 +96,11 @@ constexpr int kResizeBoxMax = 128;
 constexpr int kResizeTapMax = 9;                                     // taps of one output index along an axis, at a scale of at most 4 with the filter on
 struct ResizeBoxes { uint32_t w[2 * kResizeBoxMax]; };               // [2 b]: y0 | x0 << 13 | flip << 26 (tensor_win_pack); [2 b + 1]: hs | ws << 13
 LLICTI_HD uint32_t resize_ext_pack(int hs, int ws) { return (uint32_t)hs | ((uint32_t)ws << 13); }
+// Views (llicti_decode_images_tensor_views): a view is such a box of the image it NAMES -- three words per view, kViewMax views per launch of
+// unlift_views_tensor_kernel (a longer group takes several launches).  The image index has a word of its own: a batch has no upper bound.
+constexpr int kViewMax = 128;
+constexpr int kViewCountMax = 1 << 20;                               // views of one group
+struct ViewSlice { uint32_t w[3 * kViewMax]; };                      // [3 v]: tensor_win_pack; [3 v + 1]: resize_ext_pack; [3 v + 2]: the image's index
 // an hs x ws box at (y0, x0) of an H x W image decoded at reduce r lies inside it, and the resampling to Ho x Wo is one the kernel does: output
 // sizes 1 .. 8160, the filter flag 0 or 1, and with the filter on a scale of at most 4 per axis (hs <= 4 Ho, ws <= 4 Wo: kResizeTapMax taps)
 LLICTI_HD bool resize_window_ok(int H, int W, int r, int y0, int x0, int hs, int ws, int Ho, int Wo, int antialias)

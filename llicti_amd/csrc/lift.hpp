@@ -526,20 +526,14 @@ __global__ __launch_bounds__(256) void unlift_tensor_kernel(const int16_t *__res
 // per channel when Wo % 4 == 0 and `out` is aligned to 4 elements, element by element otherwise.  Source indices are clamped into the box
 // (only zero-weight taps ever are).  Latches the call's status words exactly as the other unlift kernels do.
 constexpr int kResizeTileH = 16, kResizeTileW = 64;
+// The tile body, ONE function for unlift_resize_tensor_kernel and unlift_views_tensor_kernel (the arithmetic exists once): the workgroup's tile
+// (blockIdx.x) of output slot `slot` of `out` -- [slot][3][Ho][Wo] -- from the box w0, w1 (tensor_win_pack, resize_ext_pack) of image b's planes.
 template <typename T>
-__global__ __launch_bounds__(256) void unlift_resize_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
-                                                                   int tiles_x, int antialias, const ResizeBoxes boxes, const TensorNorm nm,
-                                                                   const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
-                                                                   int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv)
+__device__ __forceinline__ void resize_tile(const int16_t *__restrict__ planes, T *__restrict__ out, long slot, int r, int Ho, int Wo, int tiles_x,
+                                            int antialias, uint32_t w0, uint32_t w1, const TensorNorm &nm, const ImgGeo *__restrict__ iv, int b)
 {
     __shared__ float wx[kResizeTileW][kResizeTapMax], wy[kResizeTileH][kResizeTapMax];
     __shared__ int xlo[kResizeTileW], ylo[kResizeTileH], ntap[2];
-    const int b = b0 + blockIdx.y;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (b == 0 && status[0] != 0) *latched = status[0];
-        if (img_latched) img_latched[b] = status[status_head + b];
-    }
-    const uint32_t w0 = boxes.w[2 * blockIdx.y], w1 = boxes.w[2 * blockIdx.y + 1];
     const int y0 = (int)(w0 & 0x1FFFu), x0 = (int)((w0 >> 13) & 0x1FFFu);
     const bool flip = ((w0 >> 26) & 1u) != 0;
     const int hs = (int)(w1 & 0x1FFFu), ws = (int)((w1 >> 13) & 0x1FFFu);
@@ -604,7 +598,7 @@ __global__ __launch_bounds__(256) void unlift_resize_tensor_kernel(const int16_t
             if (nm.on) f = __fdiv_rn(__fsub_rn(f, nm.mean[c]), nm.std[c]);
             q[c].e[k] = tensor_elem<T>(f);
         }
-    T *o = out + (long)b * 3 * oplane + (long)i * Wo + j;
+    T *o = out + slot * 3 * oplane + (long)i * Wo + j;
     const bool out_vec = (Wo & 3) == 0 && ((uintptr_t)out & (4 * sizeof(T) - 1)) == 0;
     if (out_vec) {
 #pragma unroll
@@ -614,4 +608,37 @@ __global__ __launch_bounds__(256) void unlift_resize_tensor_kernel(const int16_t
         for (int k = 0; k < 4; ++k)
             if (k < n) { o[k] = q[0].e[k]; o[oplane + k] = q[1].e[k]; o[2 * oplane + k] = q[2].e[k]; }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void unlift_resize_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
+                                                                   int tiles_x, int antialias, const ResizeBoxes boxes, const TensorNorm nm,
+                                                                   const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                                   int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv)
+{
+    const int b = b0 + blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (b == 0 && status[0] != 0) *latched = status[0];
+        if (img_latched) img_latched[b] = status[status_head + b];
+    }
+    resize_tile<T>(planes, out, (long)b, r, Ho, Wo, tiles_x, antialias, boxes.w[2 * blockIdx.y], boxes.w[2 * blockIdx.y + 1], nm, iv, b);
+}
+
+// The last kernel of llicti_decode_images_tensor_views: the same tile, of one VIEW's output.  View v0 + blockIdx.y of a group -- three words of
+// `views`, the call's kernel arguments: origin and flip, extent, the index of the view's IMAGE -- is resampled from that image's planes to
+// out[v0 + blockIdx.y][3][Ho][Wo]; views may name an image in any order, repeatedly or never.  The call's first launch (latch_n = B, every
+// other one 0) latches the status words of ALL B images, those no view names included, as the other unlift kernels do for theirs.
+template <typename T>
+__global__ __launch_bounds__(256) void unlift_views_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int v0,
+                                                                  int tiles_x, int antialias, const ViewSlice views, const TensorNorm nm,
+                                                                  const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                                  int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv, int latch_n)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && latch_n > 0) {
+        if (threadIdx.x == 0 && status[0] != 0) *latched = status[0];
+        if (img_latched)
+            for (int b = (int)threadIdx.x; b < latch_n; b += 256) img_latched[b] = status[status_head + b];
+    }
+    resize_tile<T>(planes, out, (long)v0 + blockIdx.y, r, Ho, Wo, tiles_x, antialias, views.w[3 * blockIdx.y], views.w[3 * blockIdx.y + 1], nm, iv,
+                   (int)views.w[3 * blockIdx.y + 2]);
 }

@@ -7,6 +7,7 @@
 //   lift_px_kernel / unlift_px_kernel the same on the caller's interleaved, pitched pixels (RGB8 / BGR8 / RGBA8 / BGRA8) (HBM bound)
 //   lift_f32_kernel / unlift_tensor_kernel  planar float32 in, the dense float / half / bfloat16 batch tensor (crop, flip, normalise) out (HBM bound)
 //   unlift_resize_tensor_kernel       the same tensor from a per-image source box RESAMPLED to the output size (triangle filter; a gather)
+//   unlift_views_tensor_kernel        the same tile per VIEW: several boxes per image, each naming its image, from one decode
 //   band_params_kernel<BAND>          interpolator CNN: 3 chained fp32-MFMA GEMMs per pixel tile,
 //                                     weights of one 88-channel head resident in LDS        (MFMA bound)
 //   cdf_pairs_kernel                  encoder: the two table entries per symbol (10 erfc)   (VALU)
@@ -994,6 +995,8 @@ extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, 
 struct TensorOut { int dtype, Ho, Wo; std::vector<uint32_t> wins; TensorNorm nm; };
 // llicti_decode_images_tensor_resized: the same for a resampled output (resolve_resize) -- two box words per image, the filter flag
 struct ResizeOut { int dtype, Ho, Wo, antialias; std::vector<uint32_t> boxes; TensorNorm nm; };
+// llicti_decode_images_tensor_views: the validated groups (resolve_views) -- three words per view -- and the call's normalisation constants
+struct ViewsOut { std::vector<ViewGroupOut> groups; TensorNorm nm; };
 
 // llicti_transcode_images: the target plan of the call and its part of the workspace.  decode_stages then launches cdf_pairs_kernel behind every
 // (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
@@ -1001,7 +1004,7 @@ struct TranscodeTarget { PlanDev *pd; uint8_t *ws; };
 
 static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
                          uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce, const TranscodeTarget *tc = nullptr, const TensorOut *tn = nullptr,
-                         const ResizeOut *rz = nullptr)
+                         const ResizeOut *rz = nullptr, const ViewsOut *vw = nullptr)
 {
     const Plan &p = pd->p;
     const int B = p.B, M = p.M, Q = p.Q;
@@ -1170,6 +1173,31 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
         HIPCHK(hipGetLastError());
         return 0;
     }
+    if (vw) {
+        // views (llicti_decode_images_tensor_views): group after group, kViewMax views per launch, a workgroup per 16 x 64 tile of a view's output;
+        // the views' words are kernel arguments.  The call's first launch latches the status words of all B images.
+        ProfSpan span(c, PROF_MISC, s);
+        int latch_n = B;
+        for (const ViewGroupOut &g : vw->groups) {
+            const int tiles_x = (g.Wo + kResizeTileW - 1) / kResizeTileW, tiles_y = (g.Ho + kResizeTileH - 1) / kResizeTileH;
+            for (int v0 = 0; v0 < g.n; v0 += kViewMax) {
+                const int nv = std::min(kViewMax, g.n - v0);
+                ViewSlice vs;
+                memset(&vs, 0, sizeof vs);
+                memcpy(vs.w, g.words.data() + 3 * (size_t)v0, 3 * (size_t)nv * sizeof(uint32_t));
+#define LLICTI_VIEWS_LAUNCH(T) unlift_views_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(planes, (T *)g.d_out, reduce, g.Ho, g.Wo, v0, tiles_x, \
+                                                                                                         g.antialias, vs, vw->nm, status, kStatusHead, \
+                                                                                                         c->d_status, c->d_img_status, d_img, latch_n)
+                if (g.dtype == LLICTI_T_F32) LLICTI_VIEWS_LAUNCH(float);
+                else if (g.dtype == LLICTI_T_F16) LLICTI_VIEWS_LAUNCH(_Float16);
+                else LLICTI_VIEWS_LAUNCH(bf16_bits);
+#undef LLICTI_VIEWS_LAUNCH
+                latch_n = 0;
+            }
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     if (!p.pix.empty()) {
         // interleaved output (llicti_decode_images_px), full size or reduced: one kernel, the window table behind the others
         const int gxp = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
@@ -1217,9 +1245,9 @@ static int reserve_img_status(llicti_ctx *c, int B)
 
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
                         const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0,
-                        const PixArgs *px = nullptr, const TensorArgs *tensor = nullptr, const ResizeArgs *resize = nullptr)
+                        const PixArgs *px = nullptr, const TensorArgs *tensor = nullptr, const ResizeArgs *resize = nullptr, const ViewArgs *views = nullptr)
 {
-    if (!c || !d_in || !d_seg_len || !d_workspace || !d_rgb) return fail(LLICTI_EINVAL, "decode_images: null pointer");
+    if (!c || !d_in || !d_seg_len || !d_workspace || (!d_rgb && !views)) return fail(LLICTI_EINVAL, "decode_images: null pointer");      // (views: every group has its own output)
     if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
     if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
     int ME = 0;
@@ -1243,6 +1271,10 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
         if (int rc = resolve_resize("decode_images_tensor_resized", B, Hs, Ws, reduce, *resize, rz.boxes, rz.nm)) return rc;
         rz.dtype = resize->dtype; rz.Ho = resize->Ho; rz.Wo = resize->Wo; rz.antialias = resize->antialias;
     }
+    ViewsOut vw;
+    if (views) {
+        if (int rc = resolve_views("decode_images_tensor_views", B, Hs, Ws, reduce, *views, vw.groups, vw.nm)) return rc;
+    }
     if (int rc = check_source_modes("decode_images", "container", ME)) return rc;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
@@ -1259,7 +1291,8 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
 
     if (int rc = reserve_img_status(c, B)) return rc;
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce, nullptr, tensor ? &tn : nullptr, resize ? &rz : nullptr)) return rc;
+    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce, nullptr, tensor ? &tn : nullptr, resize ? &rz : nullptr,
+                               views ? &vw : nullptr)) return rc;
     c->img_status_n = B;
     return LLICTI_OK;
 }
@@ -1349,6 +1382,17 @@ extern "C" int llicti_decode_images_tensor_resized(llicti_ctx *c, const uint8_t 
     const ResizeArgs resize{ dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias };
     return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, (uint8_t *)d_out, nullptr, stream, reduce, nullptr, nullptr,
                         &resize);
+}
+
+// (the plan: the same one -- image indices, boxes and flips of every view are kernel arguments of the groups' launches)
+extern "C" int llicti_decode_images_tensor_views(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                                 int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
+                                                 void *d_workspace, size_t workspace_bytes,
+                                                 const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream)
+{
+    const ViewArgs views{ groups, G, mean, std };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, nullptr, stream, reduce, nullptr, nullptr,
+                        nullptr, &views);
 }
 
 extern "C" int llicti_encode_images_f32(llicti_ctx *c, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,

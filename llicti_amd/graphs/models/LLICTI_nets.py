@@ -475,10 +475,18 @@ class LLICTI(nn.Module):
         the images' sizes may differ.  Not together with pixels= or flat=.
         tensor = dict(size=(Ho, Wo), boxes=[(y0, x0, hs, ws), ...], antialias=, dtype=, flip=, mean=, std=): with `boxes` every image's source box
         (decoded coordinates: the reduced ones for reduce >= 1; codec.resized_crop_plan maps full-resolution boxes and picks reduce) is RESAMPLED
-        to size by that kernel (HipCodec.decode_tensor_resized) -- a random resized crop per image; `origin` does not go with it."""
+        to size by that kernel (HipCodec.decode_tensor_resized) -- a random resized crop per image; `origin` does not go with it.
+        tensor = dict(views=[group, ...], mean=, std=): SEVERAL crops per image from one decode (HipCodec.decode_tensor_views, which describes a
+        group: size, image, boxes, flip, dtype, antialias, out) -> a list of one tensor [n, 3, Ho, Wo] per group; codec.multi_crop_plan picks
+        reduce.  `views` goes with neither `boxes`, `origin` nor `size` at the top level."""
         if tensor is not None and (pixels is not None or flat):
             raise ValueError("tensor=... gives one dense float tensor: it goes with neither pixels= nor flat=")
         codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
+        if tensor is not None and "views" in tensor:
+            if any(k in tensor for k in ("boxes", "origin", "size")):
+                raise ValueError("tensor=dict(views=...): every group has its own size and boxes; boxes=, origin= and size= do not go beside it")
+            rest = {k: v for k, v in tensor.items() if k != "views"}
+            return codec.decode_tensor_views(cont_d, seg_d, Hs, Ws, mode, tensor["views"], reduce=reduce, **rest)
         if tensor is not None and "boxes" in tensor:
             return codec.decode_tensor_resized(cont_d, seg_d, Hs, Ws, mode, reduce=reduce, **tensor)      # (an `origin` beside boxes: a TypeError)
         if tensor is not None:
