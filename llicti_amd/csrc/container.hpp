@@ -3,6 +3,19 @@
 #pragma once
 
 // ------------------------------------------------------------------------------------------------ container kernels
+// The part of a header that does not depend on where the pixels come from, by ONE thread of the three header writers below: the 17 fixed bytes
+// at o and the image's segment lengths sl[0 .. 3] (and zeros for the segments a model of fewer levels does not have); mm: the image's four
+// min / max words.  Each writer adds the raw DC band behind it.
+__device__ __forceinline__ void header_fixed(uint8_t *__restrict__ o, const ImgGeo &ig, const int32_t *__restrict__ mm, int32_t *__restrict__ sl)
+{
+    o[0] = (uint8_t)ig.byte0; o[1] = (uint8_t)ig.h4; o[2] = (uint8_t)ig.w4;    // LLICTI_nets.py:347 (AC: number of scales)
+    const int16_t v[6] = { 0, (int16_t)mm[0], (int16_t)mm[1], 255, (int16_t)mm[2], (int16_t)mm[3] };   // :139, :348
+    for (int k = 0; k < 6; ++k) { o[3 + 2 * k] = (uint8_t)(v[k] & 0xFF); o[4 + 2 * k] = (uint8_t)((v[k] >> 8) & 0xFF); }
+    o[15] = (uint8_t)(ig.padint & 0xFF); o[16] = (uint8_t)((ig.padint >> 8) & 0xFF);                   // :349
+    sl[0] = 3; sl[1] = 12; sl[2] = 2; sl[3] = 3 * ig.h4 * ig.w4;
+    for (int k = ig.nseg; k < LLICTI_NSEG; ++k) sl[k] = 0;
+}
+
 // encode: header segments straight into the container; seg_len[b][0..3]
 __global__ void header_write_kernel(const uint8_t *__restrict__ rgb, const int32_t *__restrict__ minmax, const ImgGeo *__restrict__ iv,
                                     uint8_t *__restrict__ out, long out_stride, int32_t *__restrict__ seg_len, unsigned long long *__restrict__ ssum)
@@ -11,19 +24,9 @@ __global__ void header_write_kernel(const uint8_t *__restrict__ rgb, const int32
     if (ssum && threadIdx.x == 0) ssum[b] = 0ull;       // "auto" encodes: the image's last-stage cost is summed into it later in the call (choose_streams_kernel)
     uint8_t *o = out + (long)b * out_stride;
     const ImgGeo ig = iv[b];
-    const int byte0 = ig.byte0;
-    const int W = ig.W, h4 = ig.h4, w4 = ig.w4, padint = ig.padint;
+    const int W = ig.W, h4 = ig.h4, w4 = ig.w4;
     const long plane = ig.plane;
-    if (threadIdx.x == 0) {
-        o[0] = (uint8_t)byte0; o[1] = (uint8_t)h4; o[2] = (uint8_t)w4;          // LLICTI_nets.py:347 (AC: number of scales)
-        const int32_t *mm = minmax + 4 * b;
-        const int16_t v[6] = { 0, (int16_t)mm[0], (int16_t)mm[1], 255, (int16_t)mm[2], (int16_t)mm[3] };   // :139, :348
-        for (int k = 0; k < 6; ++k) { o[3 + 2 * k] = (uint8_t)(v[k] & 0xFF); o[4 + 2 * k] = (uint8_t)((v[k] >> 8) & 0xFF); }
-        o[15] = (uint8_t)(padint & 0xFF); o[16] = (uint8_t)((padint >> 8) & 0xFF);                         // :349
-        int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
-        sl[0] = 3; sl[1] = 12; sl[2] = 2; sl[3] = 3 * h4 * w4;
-        for (int k = ig.nseg; k < LLICTI_NSEG; ++k) sl[k] = 0;                  // (a model of fewer levels: the segments it does not have)
-    }
+    if (threadIdx.x == 0) header_fixed(o, ig, minmax + 4 * b, seg_len + (long)b * LLICTI_NSEG);
     const int dcs = ig.dcs;                                                      // the last level's x00 (32 for 5 levels)
     for (int t = threadIdx.x; t < 3 * h4 * w4; t += blockDim.x) {                                        // :248-252, :350
         const int c = t / (h4 * w4), r = t - c * h4 * w4, i = r / w4, j = r - i * w4;
@@ -31,8 +34,8 @@ __global__ void header_write_kernel(const uint8_t *__restrict__ rgb, const int32
     }
 }
 
-// header_write_kernel of llicti_encode_images_px: the same header (thread 0's part to the letter); the raw DC band is read from the caller's
-// interleaved pixels through image b's window (PixGeo), colour c of a pixel at byte c of it (2 - c where blue comes first)
+// header_write_kernel of llicti_encode_images_px: the raw DC band is read from the caller's interleaved pixels through image b's window
+// (PixGeo), colour c of a pixel at byte c of it (2 - c where blue comes first)
 __global__ void header_write_px_kernel(const uint8_t *__restrict__ pix, const PixGeo *__restrict__ pv, const int32_t *__restrict__ minmax,
                                        const ImgGeo *__restrict__ iv, uint8_t *__restrict__ out, long out_stride, int32_t *__restrict__ seg_len,
                                        unsigned long long *__restrict__ ssum)
@@ -42,18 +45,8 @@ __global__ void header_write_px_kernel(const uint8_t *__restrict__ pix, const Pi
     uint8_t *o = out + (long)b * out_stride;
     const ImgGeo ig = iv[b];
     const PixGeo pg = pv[b];
-    const int byte0 = ig.byte0;
-    const int h4 = ig.h4, w4 = ig.w4, padint = ig.padint;
-    if (threadIdx.x == 0) {
-        o[0] = (uint8_t)byte0; o[1] = (uint8_t)h4; o[2] = (uint8_t)w4;
-        const int32_t *mm = minmax + 4 * b;
-        const int16_t v[6] = { 0, (int16_t)mm[0], (int16_t)mm[1], 255, (int16_t)mm[2], (int16_t)mm[3] };
-        for (int k = 0; k < 6; ++k) { o[3 + 2 * k] = (uint8_t)(v[k] & 0xFF); o[4 + 2 * k] = (uint8_t)((v[k] >> 8) & 0xFF); }
-        o[15] = (uint8_t)(padint & 0xFF); o[16] = (uint8_t)((padint >> 8) & 0xFF);
-        int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
-        sl[0] = 3; sl[1] = 12; sl[2] = 2; sl[3] = 3 * h4 * w4;
-        for (int k = ig.nseg; k < LLICTI_NSEG; ++k) sl[k] = 0;
-    }
+    const int h4 = ig.h4, w4 = ig.w4;
+    if (threadIdx.x == 0) header_fixed(o, ig, minmax + 4 * b, seg_len + (long)b * LLICTI_NSEG);
     const int dcs = ig.dcs, bpp = pix_bpp(pg.fmt);
     for (int t = threadIdx.x; t < 3 * h4 * w4; t += blockDim.x) {
         const int c = t / (h4 * w4), r = t - c * h4 * w4, i = r / w4, j = r - i * w4;
@@ -61,38 +54,28 @@ __global__ void header_write_px_kernel(const uint8_t *__restrict__ pix, const Pi
     }
 }
 
-// header_write_kernel of llicti_transcode_images, which has no pixels: the same header (thread 0's part to the letter) in the TARGET container's
-// form (iv: the target plan's table); the min / max words are the ones the decoder read from the source header, and the raw DC band is the
-// decoder's planes at the DC stride, taken back through the integer lift (header_read_kernel's forward form; a rejected source header left
-// mid grey there).  The call's first kernel on the target side: it clears the target plan's n_zero status words (block 0).
+// header_write_kernel of llicti_transcode_images, which has no pixels: the header in the TARGET container's form (iv: the target plan's
+// table); the min / max words are the ones the decoder read from the source header, and the raw DC band is the decoder's planes at the DC
+// stride, taken back through the integer lift (a rejected source header left mid grey there).  The call's first kernel on the target side:
+// it clears the target plan's n_zero status words (block 0; zero == nullptr: none, llicti_encode_images_f32 whose lift has cleared them).
 __global__ void header_transcode_kernel(const int16_t *__restrict__ planes, const int32_t *__restrict__ minmax, const ImgGeo *__restrict__ iv,
                                         uint8_t *__restrict__ out, long out_stride, int32_t *__restrict__ seg_len, unsigned long long *__restrict__ ssum,
                                         int32_t *__restrict__ zero, int n_zero)
 {
     const int b = blockIdx.x;
-    if (b == 0) for (int t = threadIdx.x; t < n_zero; t += blockDim.x) zero[t] = 0;
+    if (b == 0) clear_status(zero, n_zero);
     if (ssum && threadIdx.x == 0) ssum[b] = 0ull;
     uint8_t *o = out + (long)b * out_stride;
     const ImgGeo ig = iv[b];
-    const int byte0 = ig.byte0;
-    const int W = ig.W, h4 = ig.h4, w4 = ig.w4, padint = ig.padint;
+    const int W = ig.W, h4 = ig.h4, w4 = ig.w4;
     const long plane = ig.plane;
-    if (threadIdx.x == 0) {
-        o[0] = (uint8_t)byte0; o[1] = (uint8_t)h4; o[2] = (uint8_t)w4;
-        const int32_t *mm = minmax + 4 * b;
-        const int16_t v[6] = { 0, (int16_t)mm[0], (int16_t)mm[1], 255, (int16_t)mm[2], (int16_t)mm[3] };
-        for (int k = 0; k < 6; ++k) { o[3 + 2 * k] = (uint8_t)(v[k] & 0xFF); o[4 + 2 * k] = (uint8_t)((v[k] >> 8) & 0xFF); }
-        o[15] = (uint8_t)(padint & 0xFF); o[16] = (uint8_t)((padint >> 8) & 0xFF);
-        int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
-        sl[0] = 3; sl[1] = 12; sl[2] = 2; sl[3] = 3 * h4 * w4;
-        for (int k = ig.nseg; k < LLICTI_NSEG; ++k) sl[k] = 0;
-    }
+    if (threadIdx.x == 0) header_fixed(o, ig, minmax + 4 * b, seg_len + (long)b * LLICTI_NSEG);
     const int dcs = ig.dcs;
     for (int t = threadIdx.x; t < h4 * w4; t += blockDim.x) {
         const int i = t / w4, j = t - i * w4;
         const long off = ig.pix_off + (long)(dcs * i) * W + dcs * j;
-        const int Y = planes[off] + 127, Co = planes[off + plane], Cg = planes[off + 2 * plane];
-        const int tt = Y - (Cg >> 1), G = Cg + tt, Bl = tt - (Co >> 1), R = Bl + Co;
+        int R, G, Bl;
+        ycocg_inv(planes[off], planes[off + plane], planes[off + 2 * plane], R, G, Bl);
         o[17 + t] = (uint8_t)R; o[17 + h4 * w4 + t] = (uint8_t)G; o[17 + 2 * h4 * w4 + t] = (uint8_t)Bl;
     }
 }
@@ -168,7 +151,8 @@ __global__ void header_read_kernel(const uint8_t *__restrict__ in, long in_strid
     for (int t = threadIdx.x; t < h4 * w4; t += blockDim.x) {                              // :429-430, :443-444
         const int i = t / w4, j = t - i * w4;
         const int R = ok ? dc[t] : 128, G = ok ? dc[h4 * w4 + t] : 128, Bl = ok ? dc[2 * h4 * w4 + t] : 128;
-        const int Co = R - Bl, tt = Bl + (Co >> 1), Cg = G - tt, Y = tt + (Cg >> 1) - 127;
+        int Y, Co, Cg;
+        ycocg_fwd(R, G, Bl, Y, Co, Cg);
         const long off = ig.pix_off + (long)(dcs * i) * W + dcs * j;
         planes[off] = (int16_t)Y; planes[off + plane] = (int16_t)Co; planes[off + 2 * plane] = (int16_t)Cg;
         fplanes[off] = (float)Y / 255.0f; fplanes[off + plane] = (float)Co / 255.0f; fplanes[off + 2 * plane] = (float)Cg / 255.0f;

@@ -5,7 +5,7 @@
 // Kernels (reference call sites in include/llicti_hip.h):
 //   lift_kernel / unlift_kernel       integer YCoCg-R lift, min/max, float planes          (HBM bound)
 //   lift_px_kernel / unlift_px_kernel the same on the caller's interleaved, pitched pixels (RGB8 / BGR8 / RGBA8 / BGRA8) (HBM bound)
-//   lift_f32_kernel / unlift_tensor_kernel  planar float32 in, the dense float / half / bfloat16 batch tensor (crop, flip, normalise) out (HBM bound)
+//   lift_kernel<float> / unlift_tensor_kernel  planar float32 in, the dense float / half / bfloat16 batch tensor (crop, flip, normalise) out (HBM bound)
 //   unlift_resize_tensor_kernel       the same tensor from a per-image source box RESAMPLED to the output size (triangle filter; a gather)
 //   unlift_views_tensor_kernel        the same tile per VIEW: several boxes per image, each naming its image, from one decode
 //   band_params_kernel<BAND>          interpolator CNN: 3 chained fp32-MFMA GEMMs per pixel tile,
@@ -409,44 +409,28 @@ static int lift_grid(long units, int B, int *gx)
     return 0;
 }
 
-// part: scratch of kLiftMaxParts x 4 int32 (the workspace's for the whole-batch calls, the context's for llicti_lift_u8)
-static int launch_lift(const uint8_t *d_rgb, int B, long plane, bool vec_ok, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part, hipStream_t s,
-                       int32_t *zero = nullptr, int n_zero = 0, const ImgGeo *iv = nullptr)
-{
-    // plane: H * W (with a table: of the batch's largest image -- it sizes the grid); vec_ok: every image's plane size and placement allow
-    // 4-pixel accesses
-    const bool vec = vec_ok && (plane % 4 == 0) && (((uintptr_t)d_rgb | (uintptr_t)planes | (uintptr_t)fplanes) % 16 == 0);
-    int gx;
-    if (int rc = lift_grid(vec ? plane / 4 : plane, B, &gx)) return rc;
-    if (vec) lift_kernel<4><<<dim3(gx, B), 256, 0, s>>>(d_rgb, plane, planes, fplanes, part, zero, n_zero, iv);
-    else lift_kernel<1><<<dim3(gx, B), 256, 0, s>>>(d_rgb, plane, planes, fplanes, part, zero, n_zero, iv);
-    minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
+// where an encode's pixels come from: planar uint8, the caller's interleaved pixels (llicti_encode_images_px), planar float32 in {k/255}
+// (llicti_encode_images_f32)
+enum class PixelSrc { PlanarU8, Interleaved, PlanarF32 };
 
-// launch_lift on interleaved pixels: image b's window is pv[b]; units: the largest window in 4-pixel row pieces (Plan::pix_units)
-static int launch_lift_px(const uint8_t *d_pix, int B, long units, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part, hipStream_t s,
-                          int32_t *zero, int n_zero, const ImgGeo *iv, const PixGeo *pv)
+// One lift: the grid, the kernel of the source's kind, the fold of the partial min / max values, the check.
+// part: scratch of kLiftMaxParts x 4 int32 (the workspace's for the whole-batch calls, the context's for llicti_lift_u8).
+// units: H * W (with a table: of the batch's largest image -- it sizes the grid); Interleaved: the largest window in 4-pixel row pieces
+// (Plan::pix_units), pv the windows.  vec_ok: every image's plane size and placement (in ELEMENTS of the source) allow 4-pixel accesses.
+static int launch_lift(PixelSrc kind, const void *d_src, int B, long units, bool vec_ok, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part,
+                       hipStream_t s, int32_t *zero = nullptr, int n_zero = 0, const ImgGeo *iv = nullptr, const PixGeo *pv = nullptr)
 {
+    const bool vec = kind != PixelSrc::Interleaved && vec_ok && (units % 4 == 0) && (((uintptr_t)d_src | (uintptr_t)planes | (uintptr_t)fplanes) % 16 == 0);
     int gx;
-    if (int rc = lift_grid(units, B, &gx)) return rc;
-    lift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(d_pix, planes, fplanes, part, zero, n_zero, iv, pv);
-    minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// launch_lift on planar float32 (llicti_encode_images_f32): image b's block at element iv[b].rgb_off of d_x; plane: the batch's largest H * W
-static int launch_lift_f32(const float *d_x, int B, long plane, bool vec_ok, int16_t *planes, float *fplanes, int32_t *mm, int32_t *part, hipStream_t s,
-                           int32_t *zero, int n_zero, const ImgGeo *iv)
-{
-    // vec_ok: every image's plane size and ELEMENT offset are multiples of 4 (build_plan, on the offsets as given)
-    const bool vec = vec_ok && (((uintptr_t)d_x | (uintptr_t)planes | (uintptr_t)fplanes) % 16 == 0);
-    int gx;
-    if (int rc = lift_grid(vec ? plane / 4 : plane, B, &gx)) return rc;
-    if (vec) lift_f32_kernel<4><<<dim3(gx, B), 256, 0, s>>>(d_x, planes, fplanes, part, zero, n_zero, iv);
-    else lift_f32_kernel<1><<<dim3(gx, B), 256, 0, s>>>(d_x, planes, fplanes, part, zero, n_zero, iv);
+    if (int rc = lift_grid(vec ? units / 4 : units, B, &gx)) return rc;
+    const dim3 grid(gx, B);
+    const uint8_t *u8 = (const uint8_t *)d_src;
+    const float *f32 = (const float *)d_src;
+    if (kind == PixelSrc::Interleaved) lift_px_kernel<<<grid, 256, 0, s>>>(u8, planes, fplanes, part, zero, n_zero, iv, pv);
+    else if (kind == PixelSrc::PlanarF32 && vec) lift_kernel<float, 4><<<grid, 256, 0, s>>>(f32, units, planes, fplanes, part, zero, n_zero, iv);
+    else if (kind == PixelSrc::PlanarF32) lift_kernel<float, 1><<<grid, 256, 0, s>>>(f32, units, planes, fplanes, part, zero, n_zero, iv);
+    else if (vec) lift_kernel<uint8_t, 4><<<grid, 256, 0, s>>>(u8, units, planes, fplanes, part, zero, n_zero, iv);
+    else lift_kernel<uint8_t, 1><<<grid, 256, 0, s>>>(u8, units, planes, fplanes, part, zero, n_zero, iv);
     minmax_reduce_kernel<<<B, 64, 0, s>>>(part, gx, mm);
     HIPCHK(hipGetLastError());
     return 0;
@@ -486,7 +470,7 @@ extern "C" int llicti_lift_u8(llicti_ctx *c, const uint8_t *d_rgb, int B, int H,
     if (!c || !d_rgb || !d_planes || !d_fplanes || !d_minmax) return fail(LLICTI_EINVAL, "lift: null pointer");
     DeviceGuard guard(c);
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
-    return launch_lift(d_rgb, B, (long)H * W, true, d_planes, d_fplanes, d_minmax, c->d_lift_part, (hipStream_t)stream);
+    return launch_lift(PixelSrc::PlanarU8, d_rgb, B, (long)H * W, true, d_planes, d_fplanes, d_minmax, c->d_lift_part, (hipStream_t)stream);
 }
 
 extern "C" int llicti_unlift_u8(llicti_ctx *c, const int16_t *d_planes, int B, int H, int W, uint8_t *d_rgb, void *stream)
@@ -750,8 +734,7 @@ __global__ void zero_words_kernel(int32_t *p, int n)
 }
 __global__ void latch_status_kernel(const int32_t *status, int32_t *latched, int32_t *img_latched, int B)
 {
-    if (threadIdx.x == 0 && *status != 0) *latched = *status;
-    if (img_latched) for (int b = threadIdx.x; b < B; b += blockDim.x) img_latched[b] = status[kStatusHead + b];
+    latch_status_all(status, kStatusHead, latched, img_latched, B);
 }
 
 // The last kernel of llicti_transcode_images (which launches no unlift): the source plan's status words -- what the decoder's kernels flagged,
@@ -857,15 +840,18 @@ static int encode_back_end(llicti_ctx *c, PlanDev *pd, uint8_t *ws, const int16_
     return 0;
 }
 
-// f32 (llicti_encode_images_f32): d_rgb is planar float32 and rgb_off counts ELEMENTS -- the plan is the uint8 call's on the same numbers
-static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_off, int B, const int *Hs, const int *Ws, const int *modes, int n_modes,
-                        void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream, const PixArgs *px = nullptr,
-                        bool f32 = false)
+// The pixels of an encode: d of the kind's element type.  PlanarF32: rgb_off counts ELEMENTS -- the plan is the uint8 call's on the same numbers;
+// Interleaved: px, the windows as the caller gave them (rgb_off is not read).
+struct EncodeSrc { PixelSrc kind; const void *d; PixArgs px; };
+
+static int encode_batch(llicti_ctx *c, const EncodeSrc &src, const size_t *rgb_off, int B, const int *Hs, const int *Ws, const int *modes, int n_modes,
+                        void *d_workspace, size_t workspace_bytes, uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
 {
-    if (!c || !d_rgb || !d_workspace || !d_out || !d_seg_len) return fail(LLICTI_EINVAL, "encode_images: null pointer");
+    if (!c || !src.d || !d_workspace || !d_out || !d_seg_len) return fail(LLICTI_EINVAL, "encode_images: null pointer");
     if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
+    const bool px = src.kind == PixelSrc::Interleaved;
     std::vector<PixGeo> pix;
-    if (px) if (int rc = resolve_pixels("encode_images_px", B, Hs, Ws, px->fmt, px->off, px->pitch, pix)) return rc;
+    if (px) if (int rc = resolve_pixels("encode_images_px", B, Hs, Ws, src.px.fmt, src.px.off, src.px.pitch, pix)) return rc;
     int ME = 0;
     std::vector<int> Ms;
     if (int rc = resolve_modes("encode_images", modes, n_modes, B, &ME, Ms)) return rc;
@@ -900,18 +886,14 @@ static int encode_batch(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_o
         ProfSpan span(c, PROF_MISC, s);
         // (the lift is the call's first kernel and sets no status: it clears the call's status words on the way)
         unsigned long long *ssum0 = autoM ? (unsigned long long *)(ws + p.off_rpos) : nullptr;
-        if (px) {
-            const PixGeo *d_pv = pd->dev<PixGeo>(p.d_pix);
-            if (int rc = launch_lift_px(d_rgb, B, p.pix_units, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img, d_pv)) return rc;
-            header_write_px_kernel<<<B, 256, 0, s>>>(d_rgb, d_pv, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
-        } else if (f32) {
-            // (the header's raw DC band: the planes just made, back through the integer lift -- the pixel values, without a second conversion)
-            if (int rc = launch_lift_f32((const float *)d_rgb, B, p.max_plane, p.vec_ok, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img)) return rc;
-            header_transcode_kernel<<<B, 256, 0, s>>>(planes, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0, nullptr, 0);
-        } else {
-            if (int rc = launch_lift(d_rgb, B, p.max_plane, p.vec_ok, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status, kStatusHead + B, d_img)) return rc;
-            header_write_kernel<<<B, 256, 0, s>>>(d_rgb, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
-        }
+        const PixGeo *d_pv = px ? pd->dev<PixGeo>(p.d_pix) : nullptr;
+        const uint8_t *d_u8 = (const uint8_t *)src.d;
+        if (int rc = launch_lift(src.kind, src.d, B, px ? p.pix_units : p.max_plane, p.vec_ok, planes, fplanes, mm, (int32_t *)(ws + p.off_lift_part), s, status,
+                                 kStatusHead + B, d_img, d_pv)) return rc;
+        if (px) header_write_px_kernel<<<B, 256, 0, s>>>(d_u8, d_pv, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
+        // (float samples: the header's raw DC band is the planes just made, back through the integer lift -- the pixel values, without a second conversion)
+        else if (src.kind == PixelSrc::PlanarF32) header_transcode_kernel<<<B, 256, 0, s>>>(planes, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0, nullptr, 0);
+        else header_write_kernel<<<B, 256, 0, s>>>(d_u8, mm, d_img, d_out, (long)out_stride, d_seg_len, ssum0);
     }
     // The encoder has no dependency between stages: every (level, band) reads only original pixels.  With llicti_set_tuning("enc_side_levels", 1)
     // levels 4..1 (twelve CNN + twelve pairs launches, a quarter of the work) run on a side stream next to level 0's, with their own
@@ -972,14 +954,14 @@ extern "C" int llicti_encode_images_v(llicti_ctx *c, const uint8_t *d_rgb, const
                                       void *d_workspace, size_t workspace_bytes,
                                       uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
 {
-    return encode_batch(c, d_rgb, rgb_off, B, Hs, Ws, &mode, 1, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
+    return encode_batch(c, { PixelSrc::PlanarU8, d_rgb, {} }, rgb_off, B, Hs, Ws, &mode, 1, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
 }
 
 extern "C" int llicti_encode_images_vm(llicti_ctx *c, const uint8_t *d_rgb, const size_t *rgb_off, int B, const int *Hs, const int *Ws, const int *modes,
                                        void *d_workspace, size_t workspace_bytes,
                                        uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
 {
-    return encode_batch(c, d_rgb, rgb_off, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
+    return encode_batch(c, { PixelSrc::PlanarU8, d_rgb, {} }, rgb_off, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
 }
 
 extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, int H, int W, int mode,
@@ -988,23 +970,154 @@ extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, 
 {
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
     std::vector<int> Hs(B, H), Ws(B, W);
-    return encode_batch(c, d_rgb, nullptr, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
+    return encode_batch(c, { PixelSrc::PlanarU8, d_rgb, {} }, nullptr, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
 }
 
-// llicti_decode_images_tensor: the validated output description of the call (host_plan.hpp: resolve_tensor) -- kernel arguments of its last kernel
-struct TensorOut { int dtype, Ho, Wo; std::vector<uint32_t> wins; TensorNorm nm; };
-// llicti_decode_images_tensor_resized: the same for a resampled output (resolve_resize) -- two box words per image, the filter flag
-struct ResizeOut { int dtype, Ho, Wo, antialias; std::vector<uint32_t> boxes; TensorNorm nm; };
-// llicti_decode_images_tensor_views: the validated groups (resolve_views) -- three words per view -- and the call's normalisation constants
-struct ViewsOut { std::vector<ViewGroupOut> groups; TensorNorm nm; };
+// ------------------------------------------------------------------------------------------------ decode
+// What a whole-batch decode ends in: ONE value of one kind.  An entry point fills in what its caller gave; decode_batch validates that against
+// the call's images (resolve_sink: the kind's payload, which is all launch_sink reads) -- reduced planar output is Planar at reduce > 0.
+struct DecodeSink {
+    enum Kind { Planar, Interleaved, Tensor, Resized, Views, Transcode } kind = Planar;
+    uint8_t *d_out = nullptr;               // the caller's buffer (Views: none, every group has its own)
+    // as the caller gave them
+    PixArgs px{};                           // Interleaved
+    TensorArgs tensor{};                    // Tensor
+    ResizeArgs resize{};                    // Resized
+    ViewArgs views{};                       // Views
+    // validated
+    std::vector<PixGeo> pix;                // Interleaved: the windows (they enter the plan)
+    std::vector<uint32_t> wins;             // Tensor: a packed window per image; Resized: two packed words per image
+    std::vector<ViewGroupOut> groups;       // Views: three packed words per view
+    TensorNorm nm{};                        // Tensor, Resized, Views
+    // Transcode (llicti_transcode_images): the target plan of the call and its part of the workspace.  decode_stages launches cdf_pairs_kernel
+    // behind every (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
+    PlanDev *target = nullptr;
+    uint8_t *target_ws = nullptr;
+};
 
-// llicti_transcode_images: the target plan of the call and its part of the workspace.  decode_stages then launches cdf_pairs_kernel behind every
-// (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
-struct TranscodeTarget { PlanDev *pd; uint8_t *ws; };
+static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, int reduce)
+{
+    switch (k.kind) {
+    case DecodeSink::Interleaved: {
+        std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes
+        for (int b = 0; b < B; ++b) { Hw[b] = reduced_dim(Hs[b], reduce); Ww[b] = reduced_dim(Ws[b], reduce); }
+        return resolve_pixels("decode_images_px", B, Hw.data(), Ww.data(), k.px.fmt, k.px.off, k.px.pitch, k.pix);
+    }
+    case DecodeSink::Tensor:
+        return resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, k.tensor, k.wins, k.nm);
+    case DecodeSink::Resized:
+        return resolve_resize("decode_images_tensor_resized", B, Hs, Ws, reduce, k.resize, k.wins, k.nm);
+    case DecodeSink::Views:
+        return resolve_views("decode_images_tensor_views", B, Hs, Ws, reduce, k.views, k.groups, k.nm);
+    default:
+        return 0;
+    }
+}
 
-static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
-                         uint8_t *ws, uint8_t *d_rgb, hipStream_t s, int reduce, const TranscodeTarget *tc = nullptr, const TensorOut *tn = nullptr,
-                         const ResizeOut *rz = nullptr, const ViewsOut *vw = nullptr)
+// calls f with a value of the element type an output tensor's (validated) dtype names
+template <typename F> static void with_tensor_type(int dtype, F &&f)
+{
+    if (dtype == LLICTI_T_F32) f(float());
+    else if (dtype == LLICTI_T_F16) f(_Float16());
+    else f(bf16_bits());
+}
+// the by-value kernel argument S of one launch: entries first .. first + n - 1 of the call's table of k words per entry, zeros behind them
+template <typename S> static S arg_slice(const std::vector<uint32_t> &words, int k, int first, int n)
+{
+    S a;
+    memset(&a, 0, sizeof a);
+    memcpy(a.w, words.data() + (size_t)k * first, (size_t)k * n * sizeof(uint32_t));
+    return a;
+}
+
+// The last kernel(s) of a decode, one block per kind.  Each latches the call's status words into the context's (the workspace is the caller's:
+// it may be gone or reused by the time the words are read); every side stream of the reference-format pipeline was joined back onto `s` at the
+// end of its band, so nothing is pending here.
+static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t *ws, hipStream_t s, int reduce)
+{
+    const Plan &p = pd->p;
+    const int B = p.B;
+    const int16_t *planes = (const int16_t *)(ws + p.off_planes);
+    const int32_t *status = (const int32_t *)(ws + p.off_status);
+    const ImgGeo *d_img = pd->dev<ImgGeo>(p.d_img);
+    if (k.kind == DecodeSink::Transcode) return 0;      // (no pixels: the caller goes on with the target's header and coder, and latches the status words itself)
+    ProfSpan span(c, PROF_MISC, s);
+    switch (k.kind) {
+    case DecodeSink::Tensor: {
+        // full size or reduced: the windows are this call's kernel arguments, kTensorWinMax images per launch; every launch latches its own
+        // images' status words, the first one the call's
+        const TensorArgs &t = k.tensor;
+        const int gx = (int)std::min<long>(((long)t.Ho * ((t.Wo + 3) / 4) + 255) / 256, 1024);
+        for (int b0 = 0; b0 < B; b0 += kTensorWinMax) {
+            const int nb = std::min(kTensorWinMax, B - b0);
+            const TensorWins tw = arg_slice<TensorWins>(k.wins, 1, b0, nb);
+            with_tensor_type(t.dtype, [&](auto e) {
+                using T = decltype(e);
+                unlift_tensor_kernel<T><<<dim3(gx, nb), 256, 0, s>>>(planes, (T *)k.d_out, reduce, t.Ho, t.Wo, b0, tw, k.nm, status, kStatusHead, c->d_status,
+                                                                    c->d_img_status, d_img);
+            });
+        }
+        break;
+    }
+    case DecodeSink::Resized: {
+        // boxes, flips, output size and filter flag are this call's kernel arguments, kResizeBoxMax images per launch; a workgroup per 16 x 64
+        // tile of an image's output; the status words as above
+        const ResizeArgs &t = k.resize;
+        const int tiles_x = (t.Wo + kResizeTileW - 1) / kResizeTileW, tiles_y = (t.Ho + kResizeTileH - 1) / kResizeTileH;
+        for (int b0 = 0; b0 < B; b0 += kResizeBoxMax) {
+            const int nb = std::min(kResizeBoxMax, B - b0);
+            const ResizeBoxes bx = arg_slice<ResizeBoxes>(k.wins, 2, b0, nb);
+            with_tensor_type(t.dtype, [&](auto e) {
+                using T = decltype(e);
+                unlift_resize_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(planes, (T *)k.d_out, reduce, t.Ho, t.Wo, b0, tiles_x, t.antialias, bx, k.nm,
+                                                                                          status, kStatusHead, c->d_status, c->d_img_status, d_img);
+            });
+        }
+        break;
+    }
+    case DecodeSink::Views: {
+        // group after group, kViewMax views per launch, a workgroup per 16 x 64 tile of a view's output; boxes, flips, image indices, output size
+        // and filter flag are kernel arguments.  The call's first launch latches the status words of all B images.
+        int latch_n = B;
+        for (const ViewGroupOut &g : k.groups) {
+            const int tiles_x = (g.Wo + kResizeTileW - 1) / kResizeTileW, tiles_y = (g.Ho + kResizeTileH - 1) / kResizeTileH;
+            for (int v0 = 0; v0 < g.n; v0 += kViewMax) {
+                const int nv = std::min(kViewMax, g.n - v0);
+                const ViewSlice vs = arg_slice<ViewSlice>(g.words, 3, v0, nv);
+                with_tensor_type(g.dtype, [&](auto e) {
+                    using T = decltype(e);
+                    unlift_views_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(planes, (T *)g.d_out, reduce, g.Ho, g.Wo, v0, tiles_x, g.antialias, vs, k.nm,
+                                                                                             status, kStatusHead, c->d_status, c->d_img_status, d_img, latch_n);
+                });
+                latch_n = 0;
+            }
+        }
+        break;
+    }
+    case DecodeSink::Interleaved: {
+        // full size or reduced: one kernel, the window table behind the plan's others
+        const int gx = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
+        unlift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, k.d_out, reduce, status, kStatusHead, c->d_status, c->d_img_status, d_img,
+                                                     reduce > 0 ? pd->dev<RedGeo>(p.d_red) : nullptr, pd->dev<PixGeo>(p.d_pix));
+        break;
+    }
+    default:                                            // Planar (Transcode has returned above)
+        if (reduce > 0) {
+            long max_rplane = 0;
+            for (const RedGeo &rg : p.red) max_rplane = std::max(max_rplane, (long)rg.Hr * rg.Wr);
+            unlift_reduced_kernel<<<dim3((unsigned)((max_rplane + 255) / 256), B), 256, 0, s>>>(planes, k.d_out, reduce, status, kStatusHead, c->d_status,
+                                                                                                c->d_img_status, d_img, pd->dev<RedGeo>(p.d_red));
+        } else {
+            const int gx = (int)std::min<long>((p.max_plane + 255) / 256, 1024);
+            unlift_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, p.max_plane, k.d_out, status, kStatusHead, c->d_status, c->d_img_status, d_img);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, uint8_t *ws, hipStream_t s, int reduce,
+                         const DecodeSink &sink)
 {
     const Plan &p = pd->p;
     const int B = p.B, M = p.M, Q = p.Q;
@@ -1119,113 +1232,20 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
                     }
                 }
             }
-            if (tc) {
+            if (sink.kind == DecodeSink::Transcode) {
                 // (the reference format's colour queues have been joined back onto `s` above; the next band's CNN launch, which overwrites
                 // `params`, follows on `s`)
-                const Plan &q = tc->pd->p;
+                const Plan &q = sink.target->p;
                 const int k = lvl * 3 + band;
                 ProfSpan span(c, PROF_PAIRS, s);
                 cdf_pairs_kernel<<<dim3((unsigned)((q.lev_maxpos[lvl] + kPairsThreads - 1) / kPairsThreads), B), kPairsThreads, 0, s>>>(
-                    planes, params, mm, q.sg[(size_t)k * B], tc->pd->dev<StageGeom>(q.d_sg) + (size_t)k * B, (uint32_t *)(tc->ws + q.off_pairs) + q.pair_base[k]);
+                    planes, params, mm, q.sg[(size_t)k * B], sink.target->dev<StageGeom>(q.d_sg) + (size_t)k * B,
+                    (uint32_t *)(sink.target_ws + q.off_pairs) + q.pair_base[k]);
                 HIPCHK(hipGetLastError());
             }
         }
     }
-    if (tc) return 0;      // (no pixels: the caller goes on with the target's header and coder, and latches the status words itself)
-    if (tn) {
-        // float tensor output (llicti_decode_images_tensor), full size or reduced: the windows are this call's kernel arguments, kTensorWinMax
-        // images per launch; every launch latches its own images' status words, the first one the call's
-        const int gxt = (int)std::min<long>(((long)tn->Ho * ((tn->Wo + 3) / 4) + 255) / 256, 1024);
-        ProfSpan span(c, PROF_MISC, s);
-        for (int b0 = 0; b0 < B; b0 += kTensorWinMax) {
-            const int nb = std::min(kTensorWinMax, B - b0);
-            TensorWins tw;
-            memset(&tw, 0, sizeof tw);
-            memcpy(tw.w, tn->wins.data() + b0, (size_t)nb * sizeof(uint32_t));
-#define LLICTI_TENSOR_LAUNCH(T) unlift_tensor_kernel<T><<<dim3(gxt, nb), 256, 0, s>>>(planes, (T *)d_rgb, reduce, tn->Ho, tn->Wo, b0, tw, tn->nm, status, kStatusHead, \
-                                                                                    c->d_status, c->d_img_status, d_img)
-            if (tn->dtype == LLICTI_T_F32) LLICTI_TENSOR_LAUNCH(float);
-            else if (tn->dtype == LLICTI_T_F16) LLICTI_TENSOR_LAUNCH(_Float16);
-            else LLICTI_TENSOR_LAUNCH(bf16_bits);
-#undef LLICTI_TENSOR_LAUNCH
-        }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (rz) {
-        // resized crops (llicti_decode_images_tensor_resized): boxes, flips, output size and filter flag are this call's kernel arguments,
-        // kResizeBoxMax images per launch; a workgroup per 16 x 64 tile of an image's output; the status words as above
-        const int tiles_x = (rz->Wo + kResizeTileW - 1) / kResizeTileW, tiles_y = (rz->Ho + kResizeTileH - 1) / kResizeTileH;
-        ProfSpan span(c, PROF_MISC, s);
-        for (int b0 = 0; b0 < B; b0 += kResizeBoxMax) {
-            const int nb = std::min(kResizeBoxMax, B - b0);
-            ResizeBoxes bx;
-            memset(&bx, 0, sizeof bx);
-            memcpy(bx.w, rz->boxes.data() + 2 * (size_t)b0, 2 * (size_t)nb * sizeof(uint32_t));
-#define LLICTI_RESIZE_LAUNCH(T) unlift_resize_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(planes, (T *)d_rgb, reduce, rz->Ho, rz->Wo, b0, tiles_x, \
-                                                                                                          rz->antialias, bx, rz->nm, status, kStatusHead, \
-                                                                                                          c->d_status, c->d_img_status, d_img)
-            if (rz->dtype == LLICTI_T_F32) LLICTI_RESIZE_LAUNCH(float);
-            else if (rz->dtype == LLICTI_T_F16) LLICTI_RESIZE_LAUNCH(_Float16);
-            else LLICTI_RESIZE_LAUNCH(bf16_bits);
-#undef LLICTI_RESIZE_LAUNCH
-        }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (vw) {
-        // views (llicti_decode_images_tensor_views): group after group, kViewMax views per launch, a workgroup per 16 x 64 tile of a view's output;
-        // the views' words are kernel arguments.  The call's first launch latches the status words of all B images.
-        ProfSpan span(c, PROF_MISC, s);
-        int latch_n = B;
-        for (const ViewGroupOut &g : vw->groups) {
-            const int tiles_x = (g.Wo + kResizeTileW - 1) / kResizeTileW, tiles_y = (g.Ho + kResizeTileH - 1) / kResizeTileH;
-            for (int v0 = 0; v0 < g.n; v0 += kViewMax) {
-                const int nv = std::min(kViewMax, g.n - v0);
-                ViewSlice vs;
-                memset(&vs, 0, sizeof vs);
-                memcpy(vs.w, g.words.data() + 3 * (size_t)v0, 3 * (size_t)nv * sizeof(uint32_t));
-#define LLICTI_VIEWS_LAUNCH(T) unlift_views_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(planes, (T *)g.d_out, reduce, g.Ho, g.Wo, v0, tiles_x, \
-                                                                                                         g.antialias, vs, vw->nm, status, kStatusHead, \
-                                                                                                         c->d_status, c->d_img_status, d_img, latch_n)
-                if (g.dtype == LLICTI_T_F32) LLICTI_VIEWS_LAUNCH(float);
-                else if (g.dtype == LLICTI_T_F16) LLICTI_VIEWS_LAUNCH(_Float16);
-                else LLICTI_VIEWS_LAUNCH(bf16_bits);
-#undef LLICTI_VIEWS_LAUNCH
-                latch_n = 0;
-            }
-        }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (!p.pix.empty()) {
-        // interleaved output (llicti_decode_images_px), full size or reduced: one kernel, the window table behind the others
-        const int gxp = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
-        ProfSpan span(c, PROF_MISC, s);
-        unlift_px_kernel<<<dim3(gxp, B), 256, 0, s>>>(planes, d_rgb, reduce, status, kStatusHead, c->d_status, c->d_img_status, d_img,
-                                                      reduce > 0 ? pd->dev<RedGeo>(p.d_red) : nullptr, pd->dev<PixGeo>(p.d_pix));
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (reduce > 0) {
-        // (every side stream of the reference-format pipeline was joined back onto `s` at the end of its band: nothing is pending here)
-        long max_rplane = 0;
-        for (const RedGeo &rg : p.red) max_rplane = std::max(max_rplane, (long)rg.Hr * rg.Wr);
-        ProfSpan span(c, PROF_MISC, s);
-        unlift_reduced_kernel<<<dim3((unsigned)((max_rplane + 255) / 256), B), 256, 0, s>>>(planes, d_rgb, reduce, status, kStatusHead, c->d_status, c->d_img_status,
-                                                                                            d_img, pd->dev<RedGeo>(p.d_red));
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    const int gx = (int)std::min<long>((p.max_plane + 255) / 256, 1024);
-    {
-        ProfSpan span(c, PROF_MISC, s);
-        // (the call's status words are latched into the context's by this kernel: the workspace is the caller's, it may be gone or reused by the
-        // time the words are read)
-        unlift_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, p.max_plane, d_rgb, status, kStatusHead, c->d_status, c->d_img_status, d_img);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_sink(c, pd, sink, ws, s, reduce);
 }
 
 // Room for the per-image status words of a call on B images in the context's own copy (llicti_image_status); none are valid until the call has run
@@ -1243,11 +1263,12 @@ static int reserve_img_status(llicti_ctx *c, int B)
     return 0;
 }
 
+// rgb_off: the images' placement in a Planar sink's buffer (NULL: tight, and for every other kind)
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
-                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream, int reduce = 0,
-                        const PixArgs *px = nullptr, const TensorArgs *tensor = nullptr, const ResizeArgs *resize = nullptr, const ViewArgs *views = nullptr)
+                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, const size_t *rgb_off, void *stream, int reduce, DecodeSink sink)
 {
-    if (!c || !d_in || !d_seg_len || !d_workspace || (!d_rgb && !views)) return fail(LLICTI_EINVAL, "decode_images: null pointer");      // (views: every group has its own output)
+    const bool own_out = sink.kind == DecodeSink::Views;      // (every group has its own output)
+    if (!c || !d_in || !d_seg_len || !d_workspace || (!sink.d_out && !own_out)) return fail(LLICTI_EINVAL, "decode_images: null pointer");
     if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
     if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
     int ME = 0;
@@ -1255,60 +1276,41 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
     if (int rc = resolve_modes("decode_images", modes, n_modes, B, &ME, Ms)) return rc;
     if (int rc = check_model(c->nlev, "decode_images", ME, Ms)) return rc;
     if (int rc = check_stream_bits("decode_images", c->nlev, B, Hs, Ws, ME, Ms)) return rc;
-    std::vector<PixGeo> pix;
-    if (px) {
-        std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes
-        for (int b = 0; b < B; ++b) { Hw[b] = reduced_dim(Hs[b], reduce); Ww[b] = reduced_dim(Ws[b], reduce); }
-        if (int rc = resolve_pixels("decode_images_px", B, Hw.data(), Ww.data(), px->fmt, px->off, px->pitch, pix)) return rc;
-    }
-    TensorOut tn;
-    if (tensor) {
-        if (int rc = resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, *tensor, tn.wins, tn.nm)) return rc;
-        tn.dtype = tensor->dtype; tn.Ho = tensor->Ho; tn.Wo = tensor->Wo;
-    }
-    ResizeOut rz;
-    if (resize) {
-        if (int rc = resolve_resize("decode_images_tensor_resized", B, Hs, Ws, reduce, *resize, rz.boxes, rz.nm)) return rc;
-        rz.dtype = resize->dtype; rz.Ho = resize->Ho; rz.Wo = resize->Wo; rz.antialias = resize->antialias;
-    }
-    ViewsOut vw;
-    if (views) {
-        if (int rc = resolve_views("decode_images_tensor_views", B, Hs, Ws, reduce, *views, vw.groups, vw.nm)) return rc;
-    }
+    if (int rc = resolve_sink(sink, B, Hs, Ws, reduce)) return rc;
     if (int rc = check_source_modes("decode_images", "container", ME)) return rc;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
     PlanDev *pd = nullptr;
-    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, modes_ptr(Ms), s, &pd, reduce, px ? &pix : nullptr)) return rc;
+    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, modes_ptr(Ms), s, &pd, reduce, sink.kind == DecodeSink::Interleaved ? &sink.pix : nullptr)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     if (!p.uniform && p.M == 0) return fail(LLICTI_EINVAL, "decode_images: a batch of mixed sizes needs a rANS container (the reference-format container codes equal sizes per call)");
     if (int rc = check_in_stride("decode_images", p.nlev, B, Hs, Ws, in_stride)) return rc;
     if (workspace_bytes < p.total)
         return fail(LLICTI_ENOSPACE, "decode_images: workspace %zu < %zu", workspace_bytes, p.total);
-    uint8_t *ws = (uint8_t *)d_workspace;
 
     if (int rc = reserve_img_status(c, B)) return rc;
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, ws, d_rgb, s, reduce, nullptr, tensor ? &tn : nullptr, resize ? &rz : nullptr,
-                               views ? &vw : nullptr)) return rc;
+    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, (uint8_t *)d_workspace, s, reduce, sink)) return rc;
     c->img_status_n = B;
     return LLICTI_OK;
 }
+// a Planar sink into d_rgb
+static DecodeSink planar_sink(uint8_t *d_rgb) { DecodeSink k; k.d_out = d_rgb; return k; }
 
 extern "C" int llicti_decode_images_v(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
                                       int B, const int *Hs, const int *Ws, int mode, void *d_workspace, size_t workspace_bytes,
                                       uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, &mode, 1, d_workspace, workspace_bytes, d_rgb, rgb_off, stream);
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, &mode, 1, d_workspace, workspace_bytes, rgb_off, stream, 0, planar_sink(d_rgb));
 }
 
 extern "C" int llicti_decode_images_vm(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
                                        int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
                                        uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_rgb, rgb_off, stream);
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, rgb_off, stream, 0, planar_sink(d_rgb));
 }
 
 extern "C" int llicti_reduced_dims(int H, int W, int reduce, int *Hr, int *Wr)
@@ -1323,7 +1325,7 @@ extern "C" int llicti_decode_images_reduced(llicti_ctx *c, const uint8_t *d_in, 
                                             int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
                                             void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, d_rgb, rgb_off, stream, reduce);
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, rgb_off, stream, reduce, planar_sink(d_rgb));
 }
 
 extern "C" int llicti_pixel_bytes(int format) { return pix_format_bytes(format); }
@@ -1333,8 +1335,8 @@ extern "C" int llicti_encode_images_px(llicti_ctx *c, const uint8_t *d_pix, int 
                                        int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
                                        uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
 {
-    const PixArgs px{ format, px_off, pitch };
-    return encode_batch(c, d_pix, nullptr, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream, &px);
+    return encode_batch(c, { PixelSrc::Interleaved, d_pix, { format, px_off, pitch } }, nullptr, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride,
+                        d_seg_len, stream);
 }
 
 extern "C" int llicti_decode_images_px(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
@@ -1342,8 +1344,9 @@ extern "C" int llicti_decode_images_px(llicti_ctx *c, const uint8_t *d_in, size_
                                        void *d_workspace, size_t workspace_bytes,
                                        uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream)
 {
-    const PixArgs px{ format, px_off, pitch };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, d_pix, nullptr, stream, reduce, &px);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Interleaved; sink.d_out = d_pix; sink.px = { format, px_off, pitch };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
 }
 
 extern "C" int llicti_tensor_elem_bytes(int dtype) { return tensor_elem_bytes(dtype); }
@@ -1357,15 +1360,16 @@ extern "C" int llicti_decode_images_tensor(llicti_ctx *c, const uint8_t *d_in, s
                                            void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
                                            const float *mean, const float *std, void *stream)
 {
-    const TensorArgs tensor{ dtype, Ho, Wo, y0, x0, flip, mean, std };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, (uint8_t *)d_out, nullptr, stream, reduce, nullptr, &tensor);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Tensor; sink.d_out = (uint8_t *)d_out; sink.tensor = { dtype, Ho, Wo, y0, x0, flip, mean, std };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
 }
 
 extern "C" int llicti_resize_window_ok(int H, int W, int reduce, int y0, int x0, int hs, int ws, int Ho, int Wo, int antialias)
 {
     return resize_window_ok(H, W, reduce, y0, x0, hs, ws, Ho, Wo, antialias) ? 1 : 0;
 }
-// (the host's compile of resize_axis: the function unlift_resize_tensor_kernel calls)
+// (the host's compile of resize_axis: the function the resampling kernel calls)
 extern "C" int llicti_resize_axis(int n, int m, int antialias, int i, int *lo, float *w, int cap)
 {
     if (n < 1 || m < 1 || i < 0 || i >= m || !lo || cap < 0 || (cap > 0 && !w)) return 0;
@@ -1379,9 +1383,9 @@ extern "C" int llicti_decode_images_tensor_resized(llicti_ctx *c, const uint8_t 
                                                    void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
                                                    const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream)
 {
-    const ResizeArgs resize{ dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, (uint8_t *)d_out, nullptr, stream, reduce, nullptr, nullptr,
-                        &resize);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Resized; sink.d_out = (uint8_t *)d_out; sink.resize = { dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
 }
 
 // (the plan: the same one -- image indices, boxes and flips of every view are kernel arguments of the groups' launches)
@@ -1390,16 +1394,16 @@ extern "C" int llicti_decode_images_tensor_views(llicti_ctx *c, const uint8_t *d
                                                  void *d_workspace, size_t workspace_bytes,
                                                  const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream)
 {
-    const ViewArgs views{ groups, G, mean, std };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, nullptr, stream, reduce, nullptr, nullptr,
-                        nullptr, &views);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Views; sink.views = { groups, G, mean, std };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
 }
 
 extern "C" int llicti_encode_images_f32(llicti_ctx *c, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,
                                         void *d_workspace, size_t workspace_bytes,
                                         uint8_t *d_out, size_t out_stride, int32_t *d_seg_len, void *stream)
 {
-    return encode_batch(c, (const uint8_t *)d_x, x_off, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream, nullptr, true);
+    return encode_batch(c, { PixelSrc::PlanarF32, d_x, {} }, x_off, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, d_out, out_stride, d_seg_len, stream);
 }
 
 extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
@@ -1408,7 +1412,7 @@ extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t i
 {
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
     std::vector<int> Hs(B, H), Ws(B, W);
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, d_rgb, nullptr, stream);
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, nullptr, stream, 0, planar_sink(d_rgb));
 }
 
 // ------------------------------------------------------------------------------------------------ transcode
@@ -1465,20 +1469,21 @@ extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_
     const TranscodeLayout lay = transcode_layout(ps, pt);
     if (workspace_bytes < lay.total) return fail(LLICTI_ENOSPACE, "transcode_images: workspace %zu < %zu", workspace_bytes, lay.total);
     uint8_t *ws = (uint8_t *)d_workspace;
-    const TranscodeTarget tc{ pdd, ws + lay.off_dst };
+    DecodeSink tc;
+    tc.kind = DecodeSink::Transcode; tc.target = pdd; tc.target_ws = ws + lay.off_dst;
 
     if (int rc = reserve_img_status(c, B)) return rc;
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pds, d_in, in_stride, d_seg_len_in, ws, nullptr, s, 0, &tc)) return rc;
+    if (int rc = decode_stages(c, pds, d_in, in_stride, d_seg_len_in, ws, s, 0, tc)) return rc;
     const int16_t *planes = (const int16_t *)(ws + ps.off_planes);
     const int32_t *mm = (const int32_t *)(ws + ps.off_minmax);
-    int32_t *status_dst = (int32_t *)(tc.ws + pt.off_status);
+    int32_t *status_dst = (int32_t *)(tc.target_ws + pt.off_status);
     {
         ProfSpan span(c, PROF_MISC, s);
-        unsigned long long *ssum0 = (pt.ME & 0x1000) ? (unsigned long long *)(tc.ws + pt.off_rpos) : nullptr;
+        unsigned long long *ssum0 = (pt.ME & 0x1000) ? (unsigned long long *)(tc.target_ws + pt.off_rpos) : nullptr;
         header_transcode_kernel<<<B, 256, 0, s>>>(planes, mm, pdd->dev<ImgGeo>(pt.d_img), d_out, (long)out_stride, d_seg_len_out, ssum0, status_dst, kStatusHead + B);
     }
-    if (int rc = encode_back_end(c, pdd, tc.ws, planes, mm, d_out, out_stride, d_seg_len_out, s)) return rc;
+    if (int rc = encode_back_end(c, pdd, tc.target_ws, planes, mm, d_out, out_stride, d_seg_len_out, s)) return rc;
     {
         ProfSpan span(c, PROF_MISC, s);
         transcode_latch_kernel<<<(B * LLICTI_NSEG + 255) / 256, 256, 0, s>>>((const int32_t *)(ws + ps.off_status), status_dst, c->d_status, c->d_img_status, B, d_seg_len_out);
