@@ -39,8 +39,24 @@ def build(force: bool = False) -> str:
     return SO_PATH
 
 
+PROBE_SRC = os.path.join(ROOT, "tests", "numerics_probe.hip")
+PROBE_PATH = os.path.join(ROOT, "tests", "numerics_probe")
+
+
+def build_probe(force: bool = False) -> str:
+    """Compile tests/numerics_probe.hip (test infrastructure: the exhaustive sweep of numerics.hpp's scalar functions) with the library's own
+    flags -- the same -O3 -ffp-contract=off --offload-arch=gfx950 decide the bits -- as a program instead of a shared object."""
+    deps = [PROBE_SRC, os.path.join(_CSRC, "numerics.hpp")]
+    stale = force or not os.path.exists(PROBE_PATH) or any(os.path.getmtime(s) > os.path.getmtime(PROBE_PATH) for s in deps)
+    if stale:
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        flags = [f for f in HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
+        subprocess.check_call([hipcc] + flags + ["-o", PROBE_PATH, PROBE_SRC])
+    return PROBE_PATH
+
+
 _lib = None
-_vp, _i, _l, _sz = C.c_void_p, C.c_int, C.c_long, C.c_size_t
+_vp, _i, _l, _sz =C.c_void_p, C.c_int, C.c_long, C.c_size_t
 VIEW_GROUPS_MAX = 16           # LLICTI_VIEW_GROUPS_MAX
 
 

@@ -37,8 +37,9 @@ __device__ __forceinline__ float exp_spec(float y)          // y in [-49, 0]
 
 // 1.0f / d for d in [2, 9], bit for bit: hipcc expands an IEEE fp32 division into v_div_scale x2, v_rcp, four fma, a mul,
 // v_div_fmas and v_div_fixup; on this range both scales are 1, the fix-up is the identity and the mul is by 1.0, so
-// the seven operations below ARE that expansion.  Exhaustively checked on the GPU for every float in [2, 9]
-// (tools/hipchecks/check_recip.hip: 0 mismatches).  Saves five vector operations per erfc.
+// the seven operations below ARE that expansion.  Held on the GPU for every float in [2, 9], against the division as the compiler of
+// the day expands it and against the host's: tests/test_hip_numerics.py::test_recip_2_9_is_the_division (this header, through
+// tests/numerics_probe.hip).  Saves five vector operations per erfc.
 __device__ __forceinline__ float recip_2_9(float d)
 {
     float y = __builtin_amdgcn_rcpf(d);
@@ -79,7 +80,9 @@ __device__ __forceinline__ float erfc_pos(float x)          // x >= 0;  := 0 for
     return erfc_pos_body(x);
 }
 
-// same bits as erfc_spec, without control flow: the saturated result is selected, not branched to
+// same bits as erfc_spec, without control flow: the saturated result is selected, not branched to.  Held for all 2^32 inputs by
+// tests/test_hip_numerics.py::test_erfc_nobranch_has_erfc_spec_bits; erfc_spec itself is held to the oracle's bits on all of them by
+// ::test_device_erfc_sums_equal_oracle.
 __device__ __forceinline__ float erfc_spec_nobranch(float x)
 {
     const float a = __builtin_fabsf(x);
@@ -196,7 +199,8 @@ __device__ __forceinline__ Grid make_grid(int minv, int maxv)
 }
 // x / 255.0f for half-integers |x| <= 350 (every regular sample point), in three operations instead of the
 // ~10 of an IEEE division: q = x * RN(1/255), one fma residual, one fma correction.  Bit-identical to the
-// division on that whole domain (exhaustive check: tests/test_host_cpu.py::test_div255_shortcut_is_exact).
+// division on that whole domain (exhaustive checks: in exact arithmetic tests/test_host_cpu.py::test_div255_shortcut_is_exact; on the
+// device, against its own division and for the integers |v| <= 255 too, tests/test_hip_numerics.py::test_div255_exact_is_the_division).
 __device__ __forceinline__ float div255_exact(float x)
 {
     const float r = 0x1.010102p-8f;

@@ -124,20 +124,11 @@ def test_cdf_tables_and_pairs_bitexact(torch_mod, codecs, golden_index, oracle_w
                     assert (tab[n, Lp:] == 0xFFFF).all()
 
 
-def test_cdf_table_kernel_adversarial_params(torch_mod, codecs):
-    """Every row of the full-table kernel against the oracle for hand-made CNN outputs: very narrow and very
-    wide components, means far outside / on the edges of the range, saturating weights -- the cases the
-    kernel's constant-fill intervals (entries it does not evaluate) must get exactly right."""
-    from oracle import oracle as orc
-    torch = torch_mod
-    c = codecs("rand1337")
-    H = W = 32
+def _adversarial_params(n):
+    """Hand-made CNN outputs of n positions: par60 [n, 60] (reference channel order), the kind drawn per position, and the same values in the
+    channel-planar device layout [1, 64, n]: very narrow and very wide components, means far outside / on the edges of the range, saturating
+    weights."""
     rng = np.random.default_rng(7)
-    rgb = make_batch("noise", 1, H, W, seed0=3)
-    planes, fplanes, mm = c.lift(_dev(torch, rgb))
-    p_host, _ = orc.lift(rgb[0])
-    h = w = 16
-    n = h * w
     par60 = np.zeros((n, 60), np.float32)
     kinds = rng.integers(0, 6, size=n)
     for r in range(n):
@@ -153,8 +144,28 @@ def test_cdf_table_kernel_adversarial_params(torch_mod, codecs):
         par60[r, 45:60] = rng.uniform(-1, 1, 15)
     par64 = np.zeros((1, 4, 16, n), np.float32)                    # channel-planar device layout: [B][64 planes][h * w]
     par64[0, :, :15, :] = par60.reshape(n, 4, 15).transpose(1, 2, 0)
+    return par60, kinds, par64.reshape(1, 64, n)
+
+
+ADVERSARIAL_RANGES = ((-255, -255, 255, 255), (-3, -40, 5, 61), (0, -1, 0, 0))      # (min Co, min Cg, max Co, max Cg)
+
+
+def test_cdf_table_kernel_adversarial_params(torch_mod, codecs):
+    """Every row of the full-table kernel against the oracle for hand-made CNN outputs: very narrow and very
+    wide components, means far outside / on the edges of the range, saturating weights -- the cases the
+    kernel's constant-fill intervals (entries it does not evaluate) must get exactly right."""
+    from oracle import oracle as orc
+    torch = torch_mod
+    c = codecs("rand1337")
+    H = W = 32
+    rgb = make_batch("noise", 1, H, W, seed0=3)
+    planes, fplanes, mm = c.lift(_dev(torch, rgb))
+    p_host, _ = orc.lift(rgb[0])
+    h = w = 16
+    n = h * w
+    par60, kinds, par64 = _adversarial_params(n)
     params = _dev(torch, par64.reshape(1, 64, h, w))
-    for (mnco, mncg, mxco, mxcg) in ((-255, -255, 255, 255), (-3, -40, 5, 61), (0, -1, 0, 0)):
+    for (mnco, mncg, mxco, mxcg) in ADVERSARIAL_RANGES:
         mm2 = _dev(torch, np.array([[mnco, mncg, mxco, mxcg]], np.int32))
         for clr in range(3):
             minv = -127 if clr == 0 else (mnco, mncg)[clr - 1]
@@ -169,6 +180,51 @@ def test_cdf_table_kernel_adversarial_params(torch_mod, codecs):
                                       np.float32(p_host[1, R, Cc]) / np.float32(255), minv, maxv)
                     assert np.array_equal(tab[r, :Lp], row), (clr, r, int(kinds[r]), stride)
                     assert (tab[r, Lp:] == 0xFFFF).all()
+
+
+def test_cdf_pairs_kernel_adversarial_params(torch_mod, codecs):
+    """The encoder's pairs kernel at the same hand-made CNN outputs and the same three Co / Cg ranges: at each of the 256 positions and each
+    colour, the pair's low half is row[sym] and its high half row[sym + 1] of the oracle's row (0 past the top symbol), sym = the plane value
+    minus the range's lower end.  The pairs kernel evaluates its two entries through mix_cdf / erfc_spec_nobranch where the table kernel calls
+    erfc_spec and fills saturated stretches with constants: held to the oracle at a CNN's parameters alone
+    (test_cdf_tables_and_pairs_bitexact) it never met an argument deep in either tail, a mean on a grid point or a weight at its bound.
+    A pair exists only for a value inside its range (the encoder's ranges are the planes' own minima and maxima), so for the two narrow
+    ranges the Co and Cg planes are clamped into the range first -- on the device and for the oracle alike (Co is also an input: Cg's means
+    depend on it); with the full range the planes are the image's own."""
+    from oracle import oracle as orc
+    torch = torch_mod
+    c = codecs("rand1337")
+    H = W = 32
+    rgb = make_batch("noise", 1, H, W, seed0=3)
+    planes, fplanes, mm = c.lift(_dev(torch, rgb))
+    p_lift, _ = orc.lift(rgb[0])
+    h = w = 16
+    n = h * w
+    par60, kinds, par64 = _adversarial_params(n)
+    params = _dev(torch, par64.reshape(1, 64, h, w))
+    for (mnco, mncg, mxco, mxcg) in ADVERSARIAL_RANGES:
+        p_host = p_lift.copy()
+        p_host[1] = np.clip(p_lift[1], mnco, mxco)
+        p_host[2] = np.clip(p_lift[2], mncg, mxcg)
+        if (mnco, mncg, mxco, mxcg) == ADVERSARIAL_RANGES[0]:
+            assert np.array_equal(p_host, p_lift) and np.array_equal(planes[0].cpu().numpy(), p_lift)
+        mm2 = _dev(torch, np.array([[mnco, mncg, mxco, mxcg]], np.int32))
+        pairs = c.cdf_pairs(_dev(torch, p_host[None]), params, mm2, 0, 0).cpu().numpy().view(np.uint32)
+        assert pairs.shape == (3, 1, n)
+        for clr in range(3):
+            minv = -127 if clr == 0 else (mnco, mncg)[clr - 1]
+            maxv = 128 if clr == 0 else (mxco, mxcg)[clr - 1]
+            Lp = maxv - minv + 2
+            for r in range(n):
+                i, j = divmod(r, w)
+                R, Cc = 2 * i + 1, 2 * j + 1
+                row = orc.cdf_row(par60[r], clr, np.float32(p_host[0, R, Cc]) / np.float32(255),
+                                  np.float32(p_host[1, R, Cc]) / np.float32(255), minv, maxv)
+                sym = int(p_host[clr, R, Cc]) - minv
+                assert 0 <= sym <= Lp - 2
+                lo, hi = int(row[sym]), (int(row[sym + 1]) if sym + 1 <= Lp - 2 else 0)
+                got = int(pairs[clr, 0, r])
+                assert (got & 0xFFFF, got >> 16) == (lo, hi), (clr, r, int(kinds[r]), sym, (mnco, mncg, mxco, mxcg))
 
 
 def test_ac_seam_matches_oracle(torch_mod, codecs):
