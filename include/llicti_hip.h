@@ -448,6 +448,48 @@ int llicti_transcode_images(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stri
                             const int *dst_modes, int n_dst, void *d_workspace, size_t workspace_bytes,
                             uint8_t *d_out, size_t out_stride, int32_t *d_seg_len_out, void *stream);
 
+/* RECORDS: the strided device containers of a batch <-> ONE dense blob of .llic records, on the device -- what an archive file holds and what
+ * one dense PCIe copy moves.  A record is exactly the bytes of one .llic file (llicti_amd/fileio.py: dumps_llic): b"LLIC", a version byte (1), a
+ * byte n -- the model's segment count, 4 + 9 x levels: 49 for config A, 22 for config B --, n little-endian uint32 segment lengths, then the n
+ * segments back to back.  A device container is already its segments back to back, so a record's payload is the sum(seg_len) bytes at
+ * d_cont + b * stride.  Both calls are asynchronous on `stream`, neither synchronises nor allocates on a warm context (the first call with a
+ * larger B than any whole-batch call before grows the per-image status words, as a decode does), and both report through the latched status:
+ * llicti_check_status, and llicti_image_status for the call's B images (a later decode replaces those words with its own).
+ * LLICTI_EINVAL before anything is launched: a null pointer, B < 1 or above 1,048,576, stride < 1, a blob_cap / blob_bytes above 2^62, and a blob
+ * that overlaps the containers, the segment lengths or the offsets.
+ *
+ * llicti_record_bytes (host helper, no device): bytes of the record of one image from its n segment lengths, 6 + 4n + sum; 0 for a null
+ * h_seg_len or a negative length.  n is the context's; ctx = NULL: config A's 49.
+ *
+ * llicti_pack_records: d_rec_off[b] = first byte of record b in d_blob, d_rec_off[B] = their total (a scan on the device); the records densely
+ * from d_blob: the blob equals the concatenation of the images' .llic files byte for byte.  No byte at or past d_rec_off[B] is written.
+ *   - an image whose seg_len row has a negative entry or sums to more than `stride` gets a ZERO-LENGTH record and LLICTI_EFORMAT in its status
+ *     word; its neighbours are unaffected
+ *   - a total above blob_cap latches LLICTI_ENOSPACE: d_rec_off is still filled completely -- d_rec_off[B] is the capacity the call needs --, the
+ *     records that end at or before blob_cap are written, the others are not: nothing at or past blob_cap is written
+ *   d_seg_len [B][49] as the encoders write it; only the first n entries of a row are read.
+ *
+ * llicti_unpack_records: the inverse, for records at d_blob + d_rec_off[b] .. d_rec_off[b + 1] (any offsets: the blob may hold more than the
+ * call's records, in any order).  Every record is VALIDATED ON THE DEVICE BEFORE A PAYLOAD BYTE IS READ: 0 <= off[b] <= off[b+1] <= blob_bytes,
+ * length >= 6 + 4n, magic, version, n equal to the context's, every length below 2^31, 6 + 4n + sum == off[b+1] - off[b], sum <= stride.
+ *   - a good record gives its n lengths and zeros up to 49 in d_seg_len[b], its payload at d_cont + b * stride
+ *   - a record that fails gets LLICTI_EFORMAT for that image and an all-zero d_seg_len row; no byte of its container is written.  Every decode
+ *     call refuses a zero row with the same flag, so a caller may decode straight behind the unpack and read the status once
+ *   - no read leaves [d_blob, d_blob + blob_bytes), no write leaves [d_cont + b * stride, + stride)
+ *   stride: any value that holds the call's largest payload -- it need not be llicti_max_container_bytes, the decoders only require the header
+ *   bytes of every image inside it -- so a loader can stage a batch tightly.
+ *
+ * THE COPY: a payload is cut into chunks of LLICTI_RECORD_CHUNK bytes, one workgroup each (a 4K image's tens of megabytes go over hundreds of
+ * compute units); source and destination are misaligned against each other by any number of bytes, and every chunk moves as aligned 16-byte
+ * loads, a byte realign in registers and aligned 16-byte stores, with up to 15 bytes at either end byte by byte.  All offsets are 64-bit. */
+#define LLICTI_RECORD_CHUNK 32768
+size_t llicti_record_bytes(const llicti_ctx *ctx, const int32_t *h_seg_len);
+size_t llicti_record_bytes_n(int n, const int32_t *h_seg_len);      /* the same for a segment count given outright (49 or 22, else 0): needs no context */
+int llicti_pack_records(llicti_ctx *ctx, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B,
+                        uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off /* [B+1] */, void *stream);
+int llicti_unpack_records(llicti_ctx *ctx, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off /* [B+1] */, int B,
+                          uint8_t *d_cont, size_t stride, int32_t *d_seg_len /* [B][49] */, void *stream);
+
 /* Where llicti_encode_images / llicti_decode_images of B images of H x W in `mode` keep the YCoCg-R planes inside the caller's workspace
  * (byte offsets): int16 [B][3][H][W] (Y - 127, Co, Cg) and float32 [B][3][H][W] = planes / 255 -- the second is the `x_ycocg` the
  * reference's compress() returns beside the streams (LLICTI_nets.py:143-144, :159), so a caller that wants it reads it from the workspace

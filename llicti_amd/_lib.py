@@ -58,6 +58,7 @@ def build_probe(force: bool = False) -> str:
 _lib = None
 _vp, _i, _l, _sz =C.c_void_p, C.c_int, C.c_long, C.c_size_t
 VIEW_GROUPS_MAX = 16           # LLICTI_VIEW_GROUPS_MAX
+RECORD_CHUNK = 32768           # LLICTI_RECORD_CHUNK: payload bytes one workgroup of the record copy kernels moves
 
 
 class ViewGroup(C.Structure):
@@ -109,6 +110,10 @@ _SIGS = {
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_transcode_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
     "llicti_transcode_images": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "llicti_record_bytes": (_sz, [_vp, _vp]),
+    "llicti_record_bytes_n": (_sz, [_i, _vp]),
+    "llicti_pack_records": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz, _vp, _vp]),
+    "llicti_unpack_records": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz, _vp, _vp]),
     "llicti_encode_images": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "llicti_check_status": (_i, [_vp, _vp]),

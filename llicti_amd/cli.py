@@ -2,7 +2,9 @@
                                 [--config llicti_B.json]
    python -m llicti_amd.cli decode IN.llic OUT.(png|ppm) [--reduce R] [--checkpoint model_best.pth.tar] [--config llicti_B.json]
    python -m llicti_amd.cli transcode IN.llic OUT.llic [--container ac|auto|rans<M>|wrans<M>|xrans<M>] [--checkpoint model_best.pth.tar] [--config llicti_B.json]
-   python -m llicti_amd.cli info   IN.llic
+   python -m llicti_amd.cli info   IN.llic | ARCHIVE.llia
+   python -m llicti_amd.cli pack   ARCHIVE.llia SRC... [--container ...] [--checkpoint ...] [--config ...] [--batch N]
+   python -m llicti_amd.cli unpack ARCHIVE.llia DIR [--as llic|png|ppm] [--checkpoint ...] [--config ...] [--batch N]
 
 File-level front end of the MI355X hot path (needs a GPU: there is no CPU fallback).  Without a checkpoint the
 seed-1337 default init is used, as the reference does when `model_best.pth.tar` is missing (agents/base.py:78-80).  --config names the
@@ -11,7 +13,10 @@ compress and decompress with the json file that was used to train the model.  de
 (R = 0 .. the model's levels: 5 for config A, 2 for config B; `info` lists the sizes): exactly every 2^R-th pixel of every 2^R-th row, decoded
 from the coarse levels alone -- a decimation without smoothing, so fine texture aliases.  transcode rewrites a file in another container
 (default "auto") -- the bytes `encode --container ...` gives for the image the file holds -- on the device, at the cost of one decode: no pixels
-are made (it needs the model the file was written with, like decode)."""
+are made (it needs the model the file was written with, like decode).  pack writes an image archive (llicti_amd/archive.py): SRC are images, coded
+in batches of --batch (one encode, one on-device pack of the records and one dense download per batch), or .llic files, taken as they are; unpack
+writes every image of an archive into DIR under its name, as the .llic file it holds (no GPU) or decoded to png / ppm (one dense upload, one
+on-device unpack and one decode per batch); info on an archive lists its images."""
 from __future__ import annotations
 
 import argparse
@@ -53,12 +58,122 @@ def build_parser():
     t = sub.add_parser("transcode"); t.add_argument("src"); t.add_argument("dst")
     t.add_argument("--container", default="auto"); t.add_argument("--checkpoint", default=None); t.add_argument("--config", default=None)
     i = sub.add_parser("info"); i.add_argument("src")
+    p = sub.add_parser("pack"); p.add_argument("archive"); p.add_argument("src", nargs="+")
+    p.add_argument("--container", default="ac"); p.add_argument("--checkpoint", default=None); p.add_argument("--config", default=None)
+    p.add_argument("--batch", type=_batch_arg, default=24, metavar="N", help="images per batched encode")
+    u = sub.add_parser("unpack"); u.add_argument("archive"); u.add_argument("dir")
+    u.add_argument("--as", dest="fmt", choices=("llic", "png", "ppm"), default="llic")
+    u.add_argument("--checkpoint", default=None); u.add_argument("--config", default=None)
+    u.add_argument("--batch", type=_batch_arg, default=24, metavar="N", help="images per batched decode")
     return ap
+
+
+def _batch_arg(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError("--batch takes a positive number of images")
+    return n
+
+
+def _is_archive(path):
+    from .archive import MAGIC, TRAILER_BYTES
+    with open(path, "rb") as fh:
+        size = fh.seek(0, 2)
+        if size < TRAILER_BYTES:
+            return False
+        fh.seek(size - TRAILER_BYTES)
+        return fh.read(4) == MAGIC
+
+
+def _groups(keys, limit):
+    """Runs of consecutive positions with equal keys, each at most `limit` long -> [(first, end), ...]"""
+    out, k = [], 0
+    while k < len(keys):
+        e = k + 1
+        while e < len(keys) and e - k < limit and keys[e] == keys[k]:
+            e += 1
+        out.append((k, e))
+        k = e
+    return out
+
+
+def _info_archive(path):
+    from .archive import ArchiveReader
+    from .codec import name_of_mode
+    with ArchiveReader(path) as ar:
+        print(f"{path}: {len(ar)} images, n = {ar.nseg} segments per record, {ar.total_bytes} bytes of records")
+        for k in range(len(ar)):
+            (H, W), nb = ar.sizes[k], int(ar.offsets[k + 1] - ar.offsets[k])
+            print(f"  {ar.names[k]}: {W}x{H}, container {name_of_mode(ar.modes[k])}, {nb} bytes, {8.0 * nb / (H * W):.4f} bpp")
+    return 0
+
+
+def _pack(a):
+    import os
+    from . import fileio
+    from .archive import ArchiveWriter
+    names = [os.path.splitext(os.path.basename(s))[0] for s in a.src]
+    is_llic = [s.lower().endswith(".llic") for s in a.src]
+    model = torch = None
+    if not all(is_llic):
+        model, torch = _model(a.container, a.checkpoint, a.config)
+        nseg = model.codec().nseg
+    else:
+        with open(a.src[0], "rb") as fh:
+            nseg = fh.read(6)[5]
+    t0, total = time.time(), 0
+    with ArchiveWriter(a.archive, nseg) as aw:
+        imgs = {k: fileio.read_image(s, layout="hwc") for k, s in enumerate(a.src) if not is_llic[k]}
+        # a batch is a run of images; the reference format codes one size per call
+        keys = [("llic", k) if is_llic[k] else ("img", imgs[k].shape[:2] if a.container == "ac" else None) for k in range(len(a.src))]
+        for g0, g1 in _groups(keys, a.batch):
+            if is_llic[g0]:
+                with open(a.src[g0], "rb") as fh:
+                    data = fh.read()
+                aw.append_llic(data, names[g0])
+                total += len(data)
+                continue
+            blob, rec_off = model.encode_batch_async([imgs[k] for k in range(g0, g1)], pixels="rgb").records()
+            aw.append_records(blob, rec_off, names[g0:g1])
+            total += int(rec_off[-1])
+    print(f"{len(a.src)} images -> {a.archive}: {total} bytes of records, {time.time() - t0:.3f} s")
+    return 0
+
+
+def _unpack(a):
+    import os
+    from . import fileio
+    from .archive import ArchiveReader
+    os.makedirs(a.dir, exist_ok=True)
+    t0 = time.time()
+    with ArchiveReader(a.archive) as ar:
+        names = [os.path.basename(n) or str(k) for k, n in enumerate(ar.names)]
+        if a.fmt == "llic":
+            for k in range(len(ar)):
+                with open(os.path.join(a.dir, names[k] + ".llic"), "wb") as fh:
+                    fh.write(ar.record(k))
+        else:
+            model, torch = _model("ac", a.checkpoint, a.config)
+            # a batch is a run of images of one container kind (the reference format: of one size too)
+            keys = [(m & ~0xFF, ar.sizes[k] if m == 0 else None) for k, m in enumerate(ar.modes)]
+            for g0, g1 in _groups(keys, a.batch):
+                outs = model.decode_batch_async(ar.read_batch(range(g0, g1)), torch.device("cuda:0"), pixels="rgb")
+                model.codec().check()
+                for k, hwc in zip(range(g0, g1), outs):
+                    fileio.write_image(os.path.join(a.dir, names[k] + "." + a.fmt), hwc.cpu().numpy(), layout="hwc")
+        print(f"{a.archive} -> {a.dir}: {len(ar)} images as {a.fmt}, {time.time() - t0:.3f} s")
+    return 0
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     from . import fileio
+    if a.cmd == "pack":
+        return _pack(a)
+    if a.cmd == "unpack":
+        return _unpack(a)
+    if a.cmd == "info" and _is_archive(a.src):
+        return _info_archive(a.src)
     if a.cmd == "info":
         from .codec import header_dims, levels_of_header, mode_of_header, name_of_mode, reduced_dims
         bl = fileio.read_llic(a.src)

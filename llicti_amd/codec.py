@@ -939,6 +939,77 @@ class HipCodec:
                                                   _ptr(out), out.shape[1], _ptr(seg_len_out), _stream_ptr(self.device)))
         return out, seg_len_out
 
+    # ---- records (llicti_pack_records / llicti_unpack_records): the strided containers of a batch <-> one dense blob of .llic records
+    @property
+    def nseg(self):
+        """Segments per container of the context's model: 4 + 9 x levels (49 config A, 22 config B) -- the `n` of a .llic record."""
+        return 4 + 9 * self.nlevels
+
+    def record_bytes(self, seg_len):
+        """Bytes of the .llic record of one image from its segment lengths (host array; llicti_record_bytes, works without a device call):
+        6 + 4n + sum, 0 for a negative length."""
+        sl = np.ascontiguousarray(seg_len, dtype=np.int32)
+        assert sl.ndim == 1 and sl.size >= self.nseg
+        return int(self.L.llicti_record_bytes(self.ctx, _ptr(sl)))
+
+    def pack_records(self, containers, seg_len, out=None, rec_off=None):
+        """device containers uint8 [B, stride] + seg_len int32 [B, 49] -> (blob, rec_off): the images' .llic records back to back from blob[0]
+        (flat uint8 device tensor) and their offsets, int64 device tensor [B + 1] -- rec_off[b] the first byte of record b, rec_off[B] the
+        total, from a scan on the device.  Async: neither the sizes nor the total come to the host here (rec_off.cpu() when they are needed).
+        blob[:rec_off[B]] equals b"".join(dumps_llic(...)) of the same containers; nothing at or past rec_off[B] is written.  out: the blob to
+        write into (its numel is the capacity; None: the worst case, B x (header + stride)); a total above the capacity makes check() raise
+        ENOSPACE with rec_off[B] = the capacity needed.  An image whose seg_len row is unusable (a negative entry, a sum above stride) gets a
+        zero-length record and EFORMAT in image_status()."""
+        assert containers.dtype == torch.uint8 and containers.is_cuda and containers.dim() == 2 and containers.stride(1) == 1
+        B, stride = int(containers.shape[0]), int(containers.stride(0)) if containers.shape[0] > 1 else int(containers.shape[1])
+        assert stride >= containers.shape[1]
+        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
+        if out is None:
+            out = torch.empty((B * (6 + 4 * self.nseg + int(containers.shape[1])),), dtype=torch.uint8, device=self.device)
+        if rec_off is None:
+            rec_off = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1 and out.stride(0) == 1
+        assert rec_off.dtype == torch.int64 and rec_off.is_cuda and rec_off.numel() == B + 1 and rec_off.is_contiguous()
+        _lib.check(self.L.llicti_pack_records(self.ctx, C.c_void_p(containers.data_ptr()), stride, _ptr(seg_len), B,
+                                              C.c_void_p(out.data_ptr()), out.numel(), _ptr(rec_off), _stream_ptr(self.device)))
+        return out, rec_off
+
+    @staticmethod
+    def tight_stride(rec_off, nseg):
+        """The default stride of unpack_records from HOST offsets: the largest payload, rounded up to 16 (at least 16)."""
+        ro = np.asarray(rec_off, dtype=np.int64)
+        pay = int((np.diff(ro) - (6 + 4 * int(nseg))).max()) if ro.size > 1 else 0
+        return max(16, (pay + 15) // 16 * 16)
+
+    def unpack_records(self, blob, rec_off, stride=None, out=None, seg_len=None):
+        """blob (flat uint8 device tensor) + rec_off ([B + 1] int64 offsets of B records in it: a host array / tensor, or a device tensor) ->
+        (containers uint8 [B, stride], seg_len int32 [B, 49]) on the device, async: what the decode calls take.  Every record is validated on
+        the device before a payload byte is read; one that fails gives an all-zero seg_len row, EFORMAT in image_status() (and check()), and
+        leaves its container untouched -- a decode behind it refuses that image the same way.  stride=None: the largest payload rounded up to
+        16, from rec_off when that is on the host; with device offsets the caller gives it (the decoders need no more than the payloads)."""
+        assert blob.dtype == torch.uint8 and blob.is_cuda and blob.dim() == 1 and blob.stride(0) == 1
+        if isinstance(rec_off, torch.Tensor) and rec_off.is_cuda:
+            if stride is None and out is None:
+                raise ValueError("unpack_records: with rec_off on the device the caller gives stride (or out)")
+            ro_d = rec_off
+        else:
+            ro_h = np.ascontiguousarray(rec_off.numpy() if isinstance(rec_off, torch.Tensor) else rec_off, dtype=np.int64)
+            if stride is None and out is None:
+                stride = self.tight_stride(ro_h, self.nseg)
+            ro_d = torch.from_numpy(ro_h).to(self.device, non_blocking=True)
+        assert ro_d.dtype == torch.int64 and ro_d.dim() == 1 and ro_d.numel() >= 2 and ro_d.is_contiguous()
+        B = ro_d.numel() - 1
+        if out is None:
+            out = torch.empty((B, int(stride)), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1
+        cstride = int(out.stride(0)) if B > 1 else int(out.shape[1])
+        if seg_len is None:
+            seg_len = torch.empty((B, NSEG), dtype=torch.int32, device=self.device)
+        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
+        _lib.check(self.L.llicti_unpack_records(self.ctx, C.c_void_p(blob.data_ptr()), blob.numel(), _ptr(ro_d), B,
+                                                C.c_void_p(out.data_ptr()), cstride, _ptr(seg_len), _stream_ptr(self.device)))
+        return out, seg_len
+
     def container_modes(self, containers):
         """The modes the headers of device containers [B, stride] name (a small download: 17 bytes per image; synchronises the current stream) --
         what decode() / decode_v() take for containers that came out of an "auto" encode (MODE_RANS_AUTO: the encoder picked the stream counts)."""

@@ -19,6 +19,7 @@
 //                                     lanes (the timed mode: rans_decode_stage_lane_kernel<4>)    (VALU issue bound)
 //   rans_tail_kernel<Q>               the serial tail coder behind the lanes' initial states      (latency bound)
 //   header / pack / unpack kernels    container assembly in HBM
+//   record_* kernels                  strided containers <-> one dense blob of .llic records: validation + a realigning 16-byte copy (HBM bound)
 //
 // No CPU path exists in this library: every entry point needs a gfx950 device.
 #include <hip/hip_runtime.h>
@@ -48,6 +49,7 @@ using namespace llicti;
 #include "ac_coder.hpp"
 #include "rans_coder.hpp"
 #include "container.hpp"
+#include "records.hpp"
 #include "host_plan.hpp"
 
 // ------------------------------------------------------------------------------------------------ context
@@ -1493,6 +1495,85 @@ extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_
     return LLICTI_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ records
+extern "C" size_t llicti_record_bytes(const llicti_ctx *c, const int32_t *h_seg_len)
+{
+    return llicti_record_bytes_n(c ? 4 + 9 * c->nlev : LLICTI_NSEG, h_seg_len);      // (no context: config A, as the size queries)
+}
+extern "C" size_t llicti_record_bytes_n(int n, const int32_t *h_seg_len)
+{
+    if (!h_seg_len || (n != LLICTI_NSEG && n != 4 + 9 * kLevelsB)) return 0;
+    size_t tot = (size_t)record_header_bytes(n);
+    for (int k = 0; k < n; ++k) {
+        if (h_seg_len[k] < 0) return 0;
+        tot += (size_t)h_seg_len[k];
+    }
+    return tot;
+}
+
+constexpr int kRecMaxBatch = 1 << 20;
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+// what both record calls refuse before they launch: the blob against the three other buffers of the call
+static int admit_records(const char *who, const llicti_ctx *c, const void *d_cont, size_t stride, const void *d_seg_len, int B,
+                         const void *d_blob, size_t blob_bytes, const void *d_rec_off)
+{
+    if (!c || !d_cont || !d_seg_len || !d_blob || !d_rec_off) return fail(LLICTI_EINVAL, "%s: null pointer", who);
+    if (B < 1 || B > kRecMaxBatch) return fail(LLICTI_EINVAL, "%s: B=%d (need 1 <= B <= %d)", who, B, kRecMaxBatch);
+    if (stride < 1 || stride > ((size_t)1 << 62) / (size_t)B) return fail(LLICTI_EINVAL, "%s: stride %zu", who, stride);
+    if (blob_bytes > ((size_t)1 << 62)) return fail(LLICTI_EINVAL, "%s: a blob of %zu bytes", who, blob_bytes);
+    if (ranges_overlap(d_blob, blob_bytes, d_cont, (size_t)B * stride)) return fail(LLICTI_EINVAL, "%s: the blob overlaps the containers", who);
+    if (ranges_overlap(d_blob, blob_bytes, d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t))) return fail(LLICTI_EINVAL, "%s: the blob overlaps the segment lengths", who);
+    if (ranges_overlap(d_blob, blob_bytes, d_rec_off, ((size_t)B + 1) * sizeof(int64_t))) return fail(LLICTI_EINVAL, "%s: the blob overlaps the record offsets", who);
+    if (ranges_overlap(d_cont, (size_t)B * stride, d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t)) ||
+        ranges_overlap(d_cont, (size_t)B * stride, d_rec_off, ((size_t)B + 1) * sizeof(int64_t)) ||
+        ranges_overlap(d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t), d_rec_off, ((size_t)B + 1) * sizeof(int64_t)))
+        return fail(LLICTI_EINVAL, "%s: the containers, the segment lengths and the record offsets overlap", who);
+    return 0;
+}
+// grid of the two copy kernels: x walks the chunks of the longest payload the call can hold, y the images
+static dim3 record_grid(size_t max_payload, int B)
+{
+    const size_t chunks = std::max<size_t>(1, (max_payload + kRecChunk - 1) / kRecChunk);
+    return dim3((unsigned)std::min<size_t>(chunks, 0x7FFFFFFFu), (unsigned)std::min(B, 65535));
+}
+
+extern "C" int llicti_pack_records(llicti_ctx *c, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B,
+                                   uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off, void *stream)
+{
+    if (int rc = admit_records("pack_records", c, d_cont, stride, d_seg_len, B, d_blob, blob_cap, d_rec_off)) return rc;
+    const int n = 4 + 9 * c->nlev;
+    if ((stride + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "pack_records: stride %zu", stride);
+    DeviceGuard guard(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = reserve_img_status(c, B)) return rc;
+    record_scan_kernel<<<1, kRecThreads, 0, s>>>(d_seg_len, B, n, (long)stride, (long)blob_cap, d_rec_off, c->d_status, c->d_img_status);
+    record_pack_kernel<<<record_grid(stride, B), kRecThreads, 0, s>>>(d_cont, (long)stride, d_seg_len, B, n, d_blob, (long)blob_cap, d_rec_off);
+    HIPCHK(hipGetLastError());
+    c->img_status_n = B;
+    return LLICTI_OK;
+}
+
+extern "C" int llicti_unpack_records(llicti_ctx *c, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off, int B,
+                                     uint8_t *d_cont, size_t stride, int32_t *d_seg_len, void *stream)
+{
+    if (int rc = admit_records("unpack_records", c, d_cont, stride, d_seg_len, B, d_blob, blob_bytes, d_rec_off)) return rc;
+    const int n = 4 + 9 * c->nlev;
+    const size_t max_payload = std::min(stride, blob_bytes);
+    if ((max_payload + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "unpack_records: stride %zu", stride);
+    DeviceGuard guard(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = reserve_img_status(c, B)) return rc;
+    record_check_kernel<<<B, 64, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, n, (long)stride, d_seg_len, c->d_status, c->d_img_status);
+    record_unpack_kernel<<<record_grid(max_payload, B), kRecThreads, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, B, n, d_cont, (long)stride, c->d_img_status);
+    HIPCHK(hipGetLastError());
+    c->img_status_n = B;
+    return LLICTI_OK;
+}
+
 extern "C" int llicti_check_status(llicti_ctx *c, void *stream)
 {
     if (!c) return fail(LLICTI_EINVAL, "null ctx");
@@ -1505,7 +1586,7 @@ extern "C" int llicti_check_status(llicti_ctx *c, void *stream)
     HIPCHK(hipMemsetAsync(c->d_status, 0, 4, s));
     HIPCHK(hipStreamSynchronize(s));
     if (st == LLICTI_EFORMAT) return fail(LLICTI_EFORMAT, "malformed container (header does not match the requested shape, or a stream is too long)");
-    if (st == LLICTI_ENOSPACE) return fail(LLICTI_ENOSPACE, "output buffer too small for the encoded streams");
+    if (st == LLICTI_ENOSPACE) return fail(LLICTI_ENOSPACE, "output buffer too small for the encoded streams (or the blob for the packed records)");
     if (st != 0) return fail(st, "device-side status %d", st);
     return LLICTI_OK;
 }

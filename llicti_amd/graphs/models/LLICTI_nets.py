@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from ...codec import (MODE_AC, MODE_RANS, NSEG, HipCodec, auto_modes, bytestream_list_to_container, container_to_bytestream_list, header_dims, mode_of_header, mode_of_name, pixel_bytes, pixel_format, reduced_dims)
+from ...archive import Batch
 from ...config import check_supported, model_shape
 
 
@@ -289,7 +290,7 @@ class LLICTI(nn.Module):
         seg.record_stream(down)
         enc = EncodedBatch(codec, rgb, cont_h, seg_h, ev, x_ycocg, mode, Hs, Ws)
         enc.t0 = t0
-        return enc
+        return self._with_records(enc, cont, seg, slot)
 
     def _encode_f32_async(self, x, slot):
         """encode_batch_async(pixels="f32"): float32 device tensors in, EncodedBatch out."""
@@ -327,7 +328,14 @@ class LLICTI(nn.Module):
         self._pinned_mark(("cont_out", slot), down)
         cont.record_stream(down)
         seg.record_stream(down)
-        return EncodedBatch(codec, flat, cont_h, seg_h, ev, None, mode, Hs, Ws)
+        return self._with_records(EncodedBatch(codec, flat, cont_h, seg_h, ev, None, mode, Hs, Ws), cont, seg, slot)
+
+    def _with_records(self, enc, cont, seg, slot):
+        """What EncodedBatch.records() needs: the device containers and segment lengths of the encode (kept alive by the handle) and the pinned
+        staging buffer of the dense download."""
+        enc.cont_d, enc.seg_d = cont, seg
+        enc._rec_stage = lambda nbytes: self._pinned(("rec_out", slot), nbytes)
+        return enc
 
     def _copy_streams(self, device):
         """(upload, download) HIP streams of a device for the batched calls' transfers (created once): PCIe copies next to the kernels, not
@@ -427,6 +435,36 @@ class LLICTI(nn.Module):
         seg_d.record_stream(cur)
         return codec, cont_d, seg_d, Hs, Ws, mode, mixed
 
+    def _upload_batch(self, batch, devc=None):
+        """_upload_lists for an archive.Batch (ArchiveReader.read_batch): ONE copy of the dense blob and its offsets on the copy stream, then
+        HipCodec.unpack_records on the compute stream cuts it into containers of the batch's tight stride -- no per-image host work, no padding
+        over PCIe.  Sizes and modes are the index's; a record the device refuses (or whose header contradicts the index) is flagged per image
+        by the decode that follows."""
+        codec = self.codec(devc if (devc is not None and torch.device(devc).type == "cuda") else None)
+        Hs, Ws, modes = [int(h) for h in batch.Hs], [int(w) for w in batch.Ws], [int(m) for m in batch.modes]
+        B = len(Hs)
+        if B < 1 or len(batch.rec_off) != B + 1:
+            raise ValueError("an archive batch holds B >= 1 images and B + 1 record offsets")
+        if any((m & ~0xFF) != (modes[0] & ~0xFF) for m in modes):
+            raise ValueError("all images of one decompres_batch call must be in the same kind of container (their stream counts may differ)")
+        mode = modes[0] if all(m == modes[0] for m in modes) else modes
+        mixed = any(h != Hs[0] or w != Ws[0] for h, w in zip(Hs, Ws)) or isinstance(mode, list)
+        if mixed and modes[0] == MODE_AC:
+            raise ValueError("images of different sizes in the reference-format container decode one size per call")
+        blob_h = batch.blob if isinstance(batch.blob, torch.Tensor) else torch.from_numpy(np.frombuffer(batch.blob, dtype=np.uint8).copy())
+        ro_h = torch.from_numpy(np.ascontiguousarray(batch.rec_off, dtype=np.int64))
+        cur = torch.cuda.current_stream(codec.device)
+        up, _ = self._copy_streams(codec.device)
+        with torch.cuda.stream(up):
+            blob_d = blob_h.to(codec.device, non_blocking=True)
+            ro_d = ro_h.to(codec.device, non_blocking=True)
+        cur.wait_stream(up)
+        blob_d.record_stream(cur)
+        ro_d.record_stream(cur)
+        with torch.cuda.device(codec.device):
+            cont_d, seg_d = codec.unpack_records(blob_d, ro_d, stride=int(batch.stride))
+        return codec, cont_d, seg_d, Hs, Ws, mode, mixed
+
     @torch.no_grad()
     def transcode_batch(self, lists, container=None, devc=None, slot=0):
         """bytestream_lists of B images -> their bytestream_lists in `container` ("ac", "rans<M>", "wrans<M>", "xrans<M>", "auto"; default: the
@@ -478,10 +516,16 @@ class LLICTI(nn.Module):
         to size by that kernel (HipCodec.decode_tensor_resized) -- a random resized crop per image; `origin` does not go with it.
         tensor = dict(views=[group, ...], mean=, std=): SEVERAL crops per image from one decode (HipCodec.decode_tensor_views, which describes a
         group: size, image, boxes, flip, dtype, antialias, out) -> a list of one tensor [n, 3, Ho, Wo] per group; codec.multi_crop_plan picks
-        reduce.  `views` goes with neither `boxes`, `origin` nor `size` at the top level."""
+        reduce.  `views` goes with neither `boxes`, `origin` nor `size` at the top level.
+        lists may be an archive.Batch (ArchiveReader.read_batch) instead: the records of B images in one host buffer -- one dense upload and
+        HipCodec.unpack_records in place of the per-image staging (`slot` is not used: the batch owns its buffer, which must stay untouched until
+        the upload has run); sizes and modes are the archive index's, everything behind the containers is the same path."""
         if tensor is not None and (pixels is not None or flat):
             raise ValueError("tensor=... gives one dense float tensor: it goes with neither pixels= nor flat=")
-        codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
+        if isinstance(lists, Batch):        # an archive's records: one dense upload, cut into containers on the device
+            codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_batch(lists, devc)
+        else:
+            codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
         if tensor is not None and "views" in tensor:
             if any(k in tensor for k in ("boxes", "origin", "size")):
                 raise ValueError("tensor=dict(views=...): every group has its own size and boxes; boxes=, origin= and size= do not go beside it")
@@ -518,6 +562,32 @@ class EncodedBatch:
         self.Hs, self.Ws = Hs, Ws           # per image (a list batch: rgb is the flat device buffer, the images back to back)
         self.t0 = None                      # list batches: timing event on the compute stream behind the wait for the upload
         self._lists = None
+        self.cont_d = self.seg_d = None     # the device containers / segment lengths of the encode (records())
+        self._rec_stage = None              # pinned staging buffer of records(): nbytes -> flat uint8 host tensor
+        self._records = None
+
+    def records(self, check=True):
+        """The batch as ONE dense blob of .llic records -> (blob, rec_off): blob a uint8 numpy view of the pinned staging buffer (valid until
+        the next records() of the same slot), rec_off int64 [B + 1]; blob[rec_off[b]:rec_off[b + 1]] is image b's .llic file, the whole blob what
+        archive.ArchiveWriter.append_records takes.  Made on the device (HipCodec.pack_records) behind the encode and downloaded as one dense
+        copy of rec_off[B] bytes -- the real bytes, not B container strides.  Synchronous; check as for lists()."""
+        if self._records is None:
+            if self.cont_d is None:
+                raise ValueError("this handle does not hold its device containers")
+            codec = self.codec
+            cur = torch.cuda.current_stream(codec.device)
+            cur.wait_event(self.ev)
+            with torch.cuda.device(codec.device):
+                blob, ro = codec.pack_records(self.cont_d, self.seg_d)
+                ro_h = ro.cpu()                                      # (waits for the scan: the total decides the size of the copy)
+                total = int(ro_h[-1])
+                host = self._rec_stage(max(total, 1)) if self._rec_stage is not None else torch.empty((max(total, 1),), dtype=torch.uint8).pin_memory()
+                host[:total].copy_(blob[:total], non_blocking=True)
+                cur.synchronize()
+            if check:
+                codec.check()
+            self._records = (host[:total].numpy(), ro_h.numpy())
+        return self._records
 
     def lists(self, check=True):
         """Wait for the download (NOT for anything enqueued after it) and cut the containers into bytestream_lists (1 + L lists x 9 `bytes`).

@@ -6,7 +6,8 @@
 //
 // What it does: seeded pseudo-random weights of the reference's shapes (the round trip is lossless whatever the weights are) and
 // images, llicti_encode_images -> llicti_decode_images on a workspace overwritten in between, byte comparison of the decoded
-// pixels, the same through the reference-format container, and one deliberately corrupted container (the call must report
+// pixels, the containers packed into one blob of .llic records, unpacked at a tight stride and decoded from there
+// (llicti_pack_records / llicti_unpack_records), the same through the reference-format container, and one deliberately corrupted container (the call must report
 // LLICTI_EFORMAT for that image and decode the others).  Exit code 0 = all of it held.  Built and run by
 // tests/test_hip_parity.py::test_native_client_without_torch.
 #include <hip/hip_runtime.h>
@@ -80,6 +81,39 @@ int main(int argc, char **argv)
         const bool ok = std::memcmp(rec.data(), rgb.data(), npix) == 0;
         std::printf("mode 0x%03x: %d x %dx%d, %ld bytes (%.3f bpp), lossless: %s\n", mode, B, W, H, bytes, 8.0 * bytes / ((double)B * H * W), ok ? "yes" : "NO");
         failures += ok ? 0 : 1;
+        {
+            // records: the containers as ONE dense blob of .llic records (llicti_pack_records), cut back into containers of a tight stride
+            // (llicti_unpack_records) and decoded from there
+            const size_t cap = (size_t)B * (6 + 4 * 49 + stride);
+            uint8_t *d_blob = nullptr, *d_cont2 = nullptr;
+            int64_t *d_off = nullptr;
+            int32_t *d_seg2 = nullptr;
+            HIP_OK(hipMalloc(&d_blob, cap));
+            HIP_OK(hipMalloc(&d_off, (size_t)(B + 1) * sizeof(int64_t)));
+            HIP_OK(hipMalloc(&d_seg2, (size_t)B * 49 * sizeof(int32_t)));
+            LL_OK(llicti_pack_records(ctx, d_out, stride, d_seg, B, d_blob, cap, d_off, st));
+            std::vector<int64_t> off((size_t)B + 1);
+            HIP_OK(hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            LL_OK(llicti_check_status(ctx, st));                                      // (synchronises st)
+            size_t tight = 16;
+            bool sizes_ok = off[0] == 0;
+            for (int b = 0; b < B; ++b) {
+                sizes_ok = sizes_ok && (size_t)(off[b + 1] - off[b]) == llicti_record_bytes(ctx, seg.data() + (size_t)b * 49);
+                const size_t pay = (size_t)(off[b + 1] - off[b]) - (6 + 4 * 49);
+                if (pay > tight) tight = (pay + 15) / 16 * 16;
+            }
+            HIP_OK(hipMalloc(&d_cont2, (size_t)B * tight));
+            LL_OK(llicti_unpack_records(ctx, d_blob, (size_t)off[B], d_off, B, d_cont2, tight, d_seg2, st));
+            HIP_OK(hipMemsetAsync(d_ws, 0xA5, ws_bytes, st));
+            HIP_OK(hipMemsetAsync(d_rec, 0, npix, st));
+            LL_OK(llicti_decode_images(ctx, d_cont2, tight, d_seg2, B, H, W, mode, d_ws, ws_bytes, d_rec, st));
+            LL_OK(llicti_check_status(ctx, st));
+            HIP_OK(hipMemcpy(rec.data(), d_rec, npix, hipMemcpyDeviceToHost));
+            const bool rt = sizes_ok && std::memcmp(rec.data(), rgb.data(), npix) == 0;
+            std::printf("records: %lld bytes in one blob (strided: %zu), stride %zu -> %zu, round trip: %s\n", (long long)off[B], (size_t)B * stride, stride, tight, rt ? "ok" : "NO");
+            failures += rt ? 0 : 1;
+            (void)hipFree(d_blob); (void)hipFree(d_cont2); (void)hipFree(d_off); (void)hipFree(d_seg2);
+        }
         if (mode != 0 && B >= 2) {
             // one corrupted container: a byte of image 1's first stream flipped -> LLICTI_EFORMAT, image 1 named, the others intact
             const long off = seg[49 + 0] + seg[49 + 1] + seg[49 + 2] + seg[49 + 3] + 40;
