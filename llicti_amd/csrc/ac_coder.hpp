@@ -459,12 +459,12 @@ __global__ __launch_bounds__(64) void ac_decode_anchor_kernel(const uint8_t *__r
         const int i = 8 * L + e;
         const float pt = (i == 0) ? gr.p_first : div255_exact(fbase + (float)i);
         const float c_mu = __uint_as_float(cur_c.x), c_rs = __uint_as_float(cur_c.y), c_wn = __uint_as_float(cur_c.z);
-        const float t = c_wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - c_mu) * c_rs)));
+        const float t = mix_term(c_wn, c_mu, c_rs, pt);
         float acc = t + dpp_row_shl(t, 1);
         acc = acc + dpp_row_shl(t, 2);
         acc = acc + dpp_row_shl(t, 3);
         acc = acc + dpp_row_shl(t, 4);
-        const uint32_t c2 = (uint32_t)((int)__builtin_rintf(acc * gr.scale) + i) & 0xFFFFu;
+        const uint32_t c2 = entry_from_sum(acc, gr.scale, i);
         const uint32_t sc2 = __umul24(rh, c2) + ((__umul24(rl, c2) + c2) >> 16);
         const bool p2 = head && ((e == 0) || ((uint32_t)i <= max_symbol && sc2 <= T));
         const int es = __builtin_popcountll(ballot64(p2)) - 1;

@@ -79,6 +79,22 @@ __global__ __launch_bounds__(kPairsThreads) void cdf_pairs_bands_kernel(const in
 // x = -(p - mu) * rsig / sqrt2 is monotone in the sample index, |x| >= 7 saturates, and the interval is widened
 // by 2 entries against rounding.  A (block, component) pair outside the interval contributes the constant 0
 // or wn (bit-identical to evaluating erfc_spec there); only pairs that overlap it run the polynomial.
+// Component mi of a row's mixture in lane mi (lanes 0 .. 4 of the wavefront), with its normalised weight: the five bounded weights meet in lane 0
+// by row shifts and the denominator is broadcast from there.
+__device__ __forceinline__ Comp row_component(const ParRow &par, const int16_t *__restrict__ planes, long off, long plane, int clr, int mi, float &w)
+{
+    float a0 = 0.0f, a1 = 0.0f, y = 0.0f, co = 0.0f;
+    if (clr == 1) { a0 = par[48 + mi]; y = (float)planes[off] / 255.0f; }
+    else if (clr == 2) { a0 = par[48 + 5 + mi]; a1 = par[48 + 10 + mi]; y = (float)planes[off] / 255.0f; co = (float)planes[off + plane] / 255.0f; }
+    Comp c = mix_component(clr, par[5 * clr + mi], par[16 + 5 * clr + mi], par[32 + 5 * clr + mi], a0, a1, y, co, w);
+    float ssum = w + dpp_row_shl(w, 1);              // (((w0 + w1) + w2) + w3) + w4 in lane 0
+    ssum = ssum + dpp_row_shl(w, 2);
+    ssum = ssum + dpp_row_shl(w, 3);
+    ssum = ssum + dpp_row_shl(w, 4);
+    c.wn = w / mix_weight_den(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ssum))));
+    return c;
+}
+
 constexpr int kTabWaves = 4;
 
 __global__ __launch_bounds__(64 * kTabWaves) void cdf_table_kernel(const int16_t *__restrict__ planes, const float *__restrict__ params,
@@ -113,31 +129,12 @@ __global__ __launch_bounds__(64 * kTabWaves) void cdf_table_kernel(const int16_t
         const int i = n / s.wc, j = n - i * s.wc;
         const ParRow par = par_row(params, b, (long)s.h * s.w, (long)i * s.w + j);
         const long off = img + ((long)(2 * i + s.oi) << s.lvl) * s.W + ((long)(2 * j + s.oj) << s.lvl);
-        // component mi, prepared exactly as mix_prepare() does
-        const float sgm = par[5 * clr + mi];
-        float mu = par[16 + 5 * clr + mi];
-        const float wk = par[32 + 5 * clr + mi];
-        if (clr == 1) {
-            const float t = par[48 + mi] * ((float)planes[off] / 255.0f);
-            mu = mu + t;
-        } else if (clr == 2) {
-            const float t1 = par[48 + 5 + mi] * ((float)planes[off] / 255.0f);
-            const float t2 = par[48 + 10 + mi] * ((float)planes[off + s.plane] / 255.0f);
-            const float t = t1 + t2;
-            mu = mu + t;
-        }
-        const float sg = (sgm > kScaleBound) ? sgm : kScaleBound;
-        const float rsig = 1.0f / sg;
-        const float w = (wk > kWeightBound) ? wk : kWeightBound;
-        float ssum = w + dpp_row_shl(w, 1);              // (((w0 + w1) + w2) + w3) + w4 in lane 0
-        ssum = ssum + dpp_row_shl(w, 2);
-        ssum = ssum + dpp_row_shl(w, 3);
-        ssum = ssum + dpp_row_shl(w, 4);
-        ssum = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ssum)));
-        const float wn = w / (1e-9f + ssum);
+        float w;
+        const Comp cm = row_component(par, planes, off, s.plane, clr, mi, w);
+        const float mu = cm.mu, rsig = cm.rsig, wn = cm.wn;
         // saturation interval in entry coordinates: entry i samples (minv - 0.5 + i) / 255 (the two pushed-out
         // end points are further out on their own side, hence at least as saturated as this says)
-        const float c = mu * 255.0f - fmin + 0.5f, hw = 9.8994949f * 255.0f * sg + 2.0f;    // 7 * sqrt2
+        const float c = mu * 255.0f - fmin + 0.5f, hw = 9.8994949f * 255.0f * mix_sigma(par[5 * clr + mi]) + 2.0f;    // 7 * sqrt2
         int lo = -1, hi = 1 << 20;                       // entries <= lo: erfc = 0;  entries >= hi: erfc = 2
         if (c - hw > -1.0f && c - hw < 1e6f) lo = (int)(c - hw);
         if (c + hw > -1e6f && c + hw < 1e6f) hi = (int)(c + hw) + 1;
@@ -173,8 +170,7 @@ __global__ __launch_bounds__(64 * kTabWaves) void cdf_table_kernel(const int16_t
                     }
                     acc = (m == 0) ? t : acc + t;
                 }
-                const float q = __builtin_rintf(acc * gr.scale);
-                const uint32_t v = (uint32_t)((int)q + ec) & 0xFFFFu;
+                const uint32_t v = entry_from_sum(acc, gr.scale, ec);
                 if (e < row_stride) row[e] = (uint16_t)((e < gr.Lp) ? v : 0xFFFFu);
             }
         }
@@ -210,28 +206,9 @@ __global__ __launch_bounds__(64 * kTabWaves) void cdf_anchor_kernel(const int16_
         const int i = n / s.wc, j = n - i * s.wc;
         const ParRow par = par_row(params, b, (long)s.h * s.w, (long)i * s.w + j);
         const long off = img + ((long)(2 * i + s.oi) << s.lvl) * s.W + ((long)(2 * j + s.oj) << s.lvl);
-        // component mi, prepared exactly as mix_prepare() does
-        const float sgm = par[5 * clr + mi];
-        float mu = par[16 + 5 * clr + mi];
-        const float wk = par[32 + 5 * clr + mi];
-        if (clr == 1) {
-            const float t = par[48 + mi] * ((float)planes[off] / 255.0f);
-            mu = mu + t;
-        } else if (clr == 2) {
-            const float t1 = par[48 + 5 + mi] * ((float)planes[off] / 255.0f);
-            const float t2 = par[48 + 10 + mi] * ((float)planes[off + s.plane] / 255.0f);
-            const float t = t1 + t2;
-            mu = mu + t;
-        }
-        const float sg = (sgm > kScaleBound) ? sgm : kScaleBound;
-        const float rsig = 1.0f / sg;
-        const float w = (wk > kWeightBound) ? wk : kWeightBound;
-        float ssum = w + dpp_row_shl(w, 1);              // (((w0 + w1) + w2) + w3) + w4 in lane 0
-        ssum = ssum + dpp_row_shl(w, 2);
-        ssum = ssum + dpp_row_shl(w, 3);
-        ssum = ssum + dpp_row_shl(w, 4);
-        ssum = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ssum)));
-        const float wn = w / (1e-9f + ssum);
+        float w;
+        const Comp cm = row_component(par, planes, off, s.plane, clr, mi, w);
+        const float mu = cm.mu, rsig = cm.rsig, wn = cm.wn;
         float acc = 0.0f;
 #pragma unroll
         for (int m = 0; m < 5; ++m) {
@@ -242,8 +219,7 @@ __global__ __launch_bounds__(64 * kTabWaves) void cdf_anchor_kernel(const int16_
             const float t = wn_m * (0.5f * erfc_spec(kNegRsqrt2 * z));
             acc = (m == 0) ? t : acc + t;
         }
-        const float q = __builtin_rintf(acc * gr.scale);
-        const uint32_t v = (uint32_t)((int)q + ec) & 0xFFFFu;
+        const uint32_t v = entry_from_sum(acc, gr.scale, ec);
         uint8_t *row = rows + ((long)b * cap_rows + (n - n0)) * kAnchorRow;
         reinterpret_cast<uint16_t *>(row)[lane] = (uint16_t)v;
         if (lane < 5) reinterpret_cast<float4 *>(row + 128)[lane] = make_float4(mu, rsig, wn, 0.0f);

@@ -140,6 +140,51 @@ __device__ __forceinline__ ParRow32 par_row32(const float *params, int b, long n
     return ParRow32{ params + (long)b * 64 * npos, 4u * (uint32_t)npos, 4u * (uint32_t)pos };
 }
 
+// ---- the spec's mixture arithmetic, written once: every kernel that prepares a component or forms a table entry calls these
+struct Comp { float mu, rsig, wn; };             // one prepared component: mean after the cross-channel update, 1 / max(sigma, bound), normalised weight
+
+__device__ __forceinline__ float mix_sigma(float sg) { return (sg > kScaleBound) ? sg : kScaleBound; }
+// (sigma, mu, weight, cross-channel factors a0 / a1, prior channels y / co) of one component -> mu after the update and rsig; w = max(weight, bound).
+// clr 0: no update; 1: mu + a0 y; 2: mu + (a0 y + a1 co).  wn is the caller's: it gathers the five w its own way and divides by mix_weight_den().
+__device__ __forceinline__ Comp mix_component(int clr, float sg, float mu, float wk, float a0, float a1, float y, float co, float &w)
+{
+    if (clr == 1) {
+        const float t = a0 * y;
+        mu = mu + t;
+    } else if (clr == 2) {
+        const float t1 = a0 * y;
+        const float t2 = a1 * co;
+        const float t = t1 + t2;
+        mu = mu + t;
+    }
+    Comp c;
+    c.mu = mu;
+    c.rsig = 1.0f / mix_sigma(sg);
+    c.wn = 0.0f;
+    w = (wk > kWeightBound) ? wk : kWeightBound;
+    return c;
+}
+template <int clr>
+__device__ __forceinline__ Comp mix_component(float sg, float mu, float wk, float a0, float a1, float y, float co, float &w)
+{
+    return mix_component(clr, sg, mu, wk, a0, a1, y, co, w);
+}
+__device__ __forceinline__ float mix_weight_den(float sum) { return 1e-9f + sum; }      // sum: (((w0 + w1) + w2) + w3) + w4, however the caller formed it
+__device__ __forceinline__ float mix_weight_den(float w0, float w1, float w2, float w3, float w4)
+{
+    return mix_weight_den((((w0 + w1) + w2) + w3) + w4);
+}
+// one term of the mixture CDF at sample point pt (erfc_spec_nobranch: same bits as erfc_spec, and independent terms' chains interleave)
+__device__ __forceinline__ float mix_term(float wn, float mu, float rsig, float pt)
+{
+    return wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu) * rsig)));
+}
+// table entry i from the five terms' sum (((t0 + t1) + t2) + t3) + t4
+__device__ __forceinline__ uint32_t entry_from_sum(float acc, float scale, int i)
+{
+    return (uint32_t)((int)__builtin_rintf(acc * scale) + i) & 0xFFFFu;
+}
+
 // par: a ParRow, or a plain array of the position's 64 values (same indexing)
 template <class PAR>
 __device__ __forceinline__ void mix_prepare(const PAR &par, int clr, float yv, float cov, Mix &m)
@@ -148,23 +193,16 @@ __device__ __forceinline__ void mix_prepare(const PAR &par, int clr, float yv, f
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         const float sg = par[5 * clr + k];
-        float mu = par[16 + 5 * clr + k];
+        const float mu = par[16 + 5 * clr + k];
         const float wk = par[32 + 5 * clr + k];
-        if (clr == 1) {
-            const float t = par[48 + k] * yv;
-            mu = mu + t;
-        } else if (clr == 2) {
-            const float t1 = par[48 + 5 + k] * yv;
-            const float t2 = par[48 + 10 + k] * cov;
-            const float t = t1 + t2;
-            mu = mu + t;
-        }
-        m.rsig[k] = 1.0f / ((sg > kScaleBound) ? sg : kScaleBound);
-        m.mu[k] = mu;
-        w[k] = (wk > kWeightBound) ? wk : kWeightBound;
+        float a0 = 0.0f, a1 = 0.0f;
+        if (clr == 1) a0 = par[48 + k];
+        else if (clr == 2) { a0 = par[48 + 5 + k]; a1 = par[48 + 10 + k]; }
+        const Comp c = mix_component(clr, sg, mu, wk, a0, a1, yv, cov, w[k]);
+        m.rsig[k] = c.rsig;
+        m.mu[k] = c.mu;
     }
-    const float s = (((w[0] + w[1]) + w[2]) + w[3]) + w[4];
-    const float den = 1e-9f + s;
+    const float den = mix_weight_den(w[0], w[1], w[2], w[3], w[4]);
 #pragma unroll
     for (int k = 0; k < 5; ++k) m.wn[k] = w[k] / den;
 }
@@ -174,9 +212,7 @@ __device__ __forceinline__ float mix_cdf(const Mix &m, float pt)
     float acc = 0.0f;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const float z = (pt - m.mu[k]) * m.rsig[k];
-        const float c = 0.5f * erfc_spec_nobranch(kNegRsqrt2 * z);    // same bits as erfc_spec; the five chains interleave
-        const float t = m.wn[k] * c;
+        const float t = mix_term(m.wn[k], m.mu[k], m.rsig[k], pt);
         acc = (k == 0) ? t : acc + t;
     }
     return acc;
@@ -216,8 +252,7 @@ __device__ __forceinline__ float sample_pt(const Grid &g, int i)
 }
 __device__ __forceinline__ uint32_t cdf_entry(const Mix &m, const Grid &g, int i)
 {
-    const float q = __builtin_rintf(mix_cdf(m, sample_pt(g, i)) * g.scale);
-    return (uint32_t)((int)q + i) & 0xFFFFu;
+    return entry_from_sum(mix_cdf(m, sample_pt(g, i)), g.scale, i);
 }
 
 }  // namespace llicti

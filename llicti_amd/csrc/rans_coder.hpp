@@ -3,6 +3,8 @@
 #pragma once
 #include <type_traits>
 
+#include "prove_symbol.hpp"
+
 // ------------------------------------------------------------------------------------------------ rANS container
 // "LLICTI-rANS v3" (format of this build; BASELINE.json north_star: "torchac replaced by a HIP rANS coder"; spec and CPU
 // restatement: oracle/llicti_oracle.h / .c).  Same CDFs and symbols as the AC container; each image has M independent
@@ -629,18 +631,15 @@ __device__ __forceinline__ float quad_bcast(float v)     // broadcast lane (l & 
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), J * 0x55, 0xF, 0xF, true));   // quad_perm [J,J,J,J]
 }
 
-struct Comp { float mu, rsig, wn; };
-
 // exact table entry i (numerics spec); valid in the group's first lane.  erfc_spec_nobranch returns the same
 // bits as erfc_spec (the saturation test selects the result instead of skipping the polynomial), which lets
 // the two components' dependent chains interleave.
 __device__ __forceinline__ uint32_t group_cdf_entry(const Comp &A, const Comp &B, const Grid &g, int i)
 {
     const float pt = sample_pt(g, i);
-    const float tA = A.wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - A.mu) * A.rsig)));
-    const float tB = B.wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - B.mu) * B.rsig)));
-    const float q = __builtin_rintf(dpp_sum5(tA, tB) * g.scale);
-    return (uint32_t)((int)q + i) & 0xFFFFu;
+    const float tA = mix_term(A.wn, A.mu, A.rsig, pt);
+    const float tB = mix_term(B.wn, B.mu, B.rsig, pt);
+    return entry_from_sum(dpp_sum5(tA, tB), g.scale, i);
 }
 
 // Approximate table entry i, 0 < i < Lp - 1 (search hint only -- never used as a result): Abramowitz-Stegun
@@ -764,17 +763,6 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_kernel(cons
         r.on = (k < K) && (64 * (m + k * M) + gsym) < nc && (64 * k + gsym) < tail_from;
         return r;
     };
-    // component (sigma, mu, w) -> (mu with the cross-channel update, 1 / max(sigma, bound), max(w, bound)), as mix_prepare()
-    auto prep = [&](float sgm, float mu, float wk, float a0, float a1, float y, float co, float &w) -> Comp {
-        Comp cpt;
-        if constexpr (clr == 1) { const float t = a0 * y; mu = mu + t; }
-        else if constexpr (clr == 2) { const float t1 = a0 * y; const float t2 = a1 * co; const float t = t1 + t2; mu = mu + t; }
-        cpt.mu = mu;
-        cpt.rsig = 1.0f / ((sgm > kScaleBound) ? sgm : kScaleBound);
-        w = (wk > kWeightBound) ? wk : kWeightBound;
-        cpt.wn = 0.0f;
-        return cpt;
-    };
     Raw cur = fetch(0);
     for (int k = 0; k < K; ++k) {
         const int chunk0 = 64 * (m + k * M);
@@ -785,10 +773,9 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_kernel(cons
             if (cur.on) {                        // uniform within the group
                 const long off = cur.off;
                 float wA, wB;
-                Comp A = prep(cur.sgA, cur.muA, cur.wkA, cur.a0A, cur.a1A, cur.y, cur.co, wA);
-                Comp B = prep(cur.sgB, cur.muB, cur.wkB, cur.a0B, cur.a1B, cur.y, cur.co, wB);
-                const float ssum = quad_lane0(dpp_sum5(wA, wB));     // (((w0 + w1) + w2) + w3) + w4
-                const float den = 1e-9f + ssum;
+                Comp A = mix_component<clr>(cur.sgA, cur.muA, cur.wkA, cur.a0A, cur.a1A, cur.y, cur.co, wA);
+                Comp B = mix_component<clr>(cur.sgB, cur.muB, cur.wkB, cur.a0B, cur.a1B, cur.y, cur.co, wB);
+                const float den = mix_weight_den(quad_lane0(dpp_sum5(wA, wB)));
                 A.wn = wA / den;
                 B.wn = wB / den;
 
@@ -824,7 +811,7 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_kernel(cons
                     glo = nlo; ghi = nhi;
                 }
                 // 2. proof with the exact spec arithmetic: entries glo and glo + 1 in one round (independent chains);
-                //    if the hint is off, gallop away from it and bisect
+                //    if the hint is off, gallop away from it and bisect -- prove_symbol()'s search, in place (profiles/README.md, decoder_parts)
                 int lo = 0, hi = max_symbol + 1;
                 uint32_t vlo = 0, vhi = 0x10000u;                    // meaningful in the group's first lane only
                 bool have_lo = false, have_hi = false;
@@ -835,9 +822,9 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_kernel(cons
                     // evaluations per lane instead of four
                     const float p1 = sample_pt(gr, s1), p2 = sample_pt(gr, s2);
                     const float pX = (mA == 1) ? p2 : p1;
-                    const float t1 = A.wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((p1 - A.mu) * A.rsig)));
-                    const float t2 = A.wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((p2 - A.mu) * A.rsig)));
-                    const float tX = B.wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pX - B.mu) * B.rsig)));
+                    const float t1 = mix_term(A.wn, A.mu, A.rsig, p1);
+                    const float t2 = mix_term(A.wn, A.mu, A.rsig, p2);
+                    const float tX = mix_term(B.wn, B.mu, B.rsig, pX);
                     float a1 = t1 + dpp_row_shl(t1, 1);              // (((t0 + t1) + t2) + t3) + t4, in the group's lane 0
                     a1 = a1 + dpp_row_shl(t1, 2);
                     a1 = a1 + dpp_row_shl(t1, 3);
@@ -846,8 +833,8 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_kernel(cons
                     a2 = a2 + dpp_row_shl(t2, 2);
                     a2 = a2 + dpp_row_shl(t2, 3);
                     a2 = a2 + dpp_row_shl(tX, 1);
-                    const uint32_t eA = (uint32_t)((int)__builtin_rintf(a1 * gr.scale) + s1) & 0xFFFFu;
-                    const uint32_t eB = (uint32_t)((int)__builtin_rintf(a2 * gr.scale) + s2) & 0xFFFFu;
+                    const uint32_t eA = entry_from_sum(a1, gr.scale, s1);
+                    const uint32_t eB = entry_from_sum(a2, gr.scale, s2);
                     const bool bA = (ballot64(eA <= slot) >> gbit) & 1ull;
                     const bool bB = (ballot64(eB <= slot) >> gbit) & 1ull;
                     const bool leA = (s1 == 0) || bA;                // entry 0 is the floor of the search (torchac: left = 0)
@@ -927,7 +914,7 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_kernel(cons
 // symbol (a CU's issue saturates at two wavefronts per SIMD), and four lanes per symbol spend them on overhead: four 5-ary rounds
 // are 16 mixture evaluations per symbol where a pair's six ternary rounds are 12, and a wave's per-step fixed costs (fetch, the
 // state update of all 128 lanes) are shared by 32 symbols instead of 16.  A pair's lanes each own three mixture components
-// (0,1,2 / 2,3,4), prepare them as mix_prepare() does and swap the results (quad_perm [1,0,3,2]); both then hold all five in
+// (0,1,2 / 2,3,4), prepare them (mix_component) and swap the results (quad_perm [1,0,3,2]); both then hold all five in
 // canonical order.  Hint: ternary search on the approximate CDF, one probe per lane.  Proof: lane 0 evaluates the exact entry s,
 // lane 1 entry s + 1, each all five terms in the spec's order -- no cross-lane sum.  Bit-identical to the four-lane kernel.
 // One launch decodes a band's three stages (Y, Co, Cg passes).
@@ -1028,28 +1015,23 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_pair_kernel
         const uint32_t slot = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * (gsym & 63), (int)xs) & 0xFFFFu;
         if (cur.on) {                            // uniform within the pair
             const long off = cur.off;
-            // the lane's three components as mix_prepare() has them
-            float mu3[3], rs3[3], w3[3];
+            float mu3[3], rs3[3], w3[3];             // the lane's three components
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                float mu = cur.mu[t];
-                if constexpr (clr == 1) { const float tt = cur.a0[t] * cur.y; mu = mu + tt; }
-                else if constexpr (clr == 2) { const float t1 = cur.a0[t] * cur.y; const float t2 = cur.a1[t] * cur.co; const float tt = t1 + t2; mu = mu + tt; }
-                mu3[t] = mu;
-                rs3[t] = 1.0f / ((cur.sg[t] > kScaleBound) ? cur.sg[t] : kScaleBound);
-                w3[t] = (cur.wk[t] > kWeightBound) ? cur.wk[t] : kWeightBound;
+                const Comp c = mix_component<clr>(cur.sg[t], cur.mu[t], cur.wk[t], cur.a0[t], cur.a1[t], cur.y, cur.co, w3[t]);
+                mu3[t] = c.mu; rs3[t] = c.rsig;
             }
-            float w5[5], mu5[5], rs5[5], wn5[5];
+            float w5[5];
+            Mix mx;                                  // all five, in canonical order, in both lanes
             canon(w3, w5);
-            const float ssum = (((w5[0] + w5[1]) + w5[2]) + w5[3]) + w5[4];
-            const float den = 1e-9f + ssum;
+            const float den = mix_weight_den(w5[0], w5[1], w5[2], w5[3], w5[4]);
             float wn3[3];
 #pragma unroll
             for (int t = 0; t < 3; ++t) wn3[t] = w3[t] / den;
-            canon(mu3, mu5); canon(rs3, rs5); canon(wn3, wn5);
+            canon(mu3, mx.mu); canon(rs3, mx.rsig); canon(wn3, mx.wn);
             CompLut F[5];
 #pragma unroll
-            for (int c = 0; c < 5; ++c) { Comp cc; cc.mu = mu5[c]; cc.rsig = rs5[c]; cc.wn = wn5[c]; F[c] = comp_lut(cc); }
+            for (int c = 0; c < 5; ++c) { Comp cc; cc.mu = mx.mu[c]; cc.rsig = mx.rsig[c]; cc.wn = mx.wn[c]; F[c] = comp_lut(cc); }
 
             // 1. hint: ternary search on the approximate table, one probe per lane of the pair
             int glo = 0, ghi = max_symbol + 1;
@@ -1070,48 +1052,27 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_pair_kernel
                 const int nhi = (np == 0) ? q1 : (np == 1) ? q2 : ghi;
                 glo = nlo; ghi = nhi;
             }
-            // exact table entry i, all five terms in this lane, cdf_entry()'s operations in its order
-            auto entry_exact = [&](int i) -> uint32_t {
+            // exact table entry i in this lane: cdf_entry()'s operations, the terms formed before the first add (profiles/README.md, decoder_parts)
+            auto entry_exact = [&](int i) __attribute__((always_inline)) -> uint32_t {
                 const float pt = sample_pt(gr, i);
-                const float t0 = wn5[0] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[0]) * rs5[0])));
-                const float t1 = wn5[1] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[1]) * rs5[1])));
-                const float t2 = wn5[2] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[2]) * rs5[2])));
-                const float t3 = wn5[3] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[3]) * rs5[3])));
-                const float t4 = wn5[4] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[4]) * rs5[4])));
-                const float acc = (((t0 + t1) + t2) + t3) + t4;
-                return (uint32_t)((int)__builtin_rintf(acc * gr.scale) + i) & 0xFFFFu;
+                float t[5];
+#pragma unroll
+                for (int c = 0; c < 5; ++c) t[c] = mix_term(mx.wn[c], mx.mu[c], mx.rsig[c], pt);
+                return entry_from_sum((((t[0] + t[1]) + t[2]) + t[3]) + t[4], gr.scale, i);
             };
-            // 2. proof: lane 0 evaluates entry glo, lane 1 entry glo + 1; if the hint is off, gallop away from it and bisect
-            int lo = 0, hi = max_symbol + 1;
-            uint32_t vlo = 0, vhi = 0x10000u;
-            bool have_lo = false, have_hi = false;
-            {
-                const int s1 = glo, s2 = min(glo + 1, max_symbol);
-                const uint32_t eM = entry_exact(odd ? s2 : s1);
-                const uint32_t eO = pair_swap_u(eM);
-                const uint32_t eA = odd ? eO : eM, eB = odd ? eM : eO;
-                const bool leA = (s1 == 0) || (eA <= slot);              // entry 0 is the floor of the search (torchac: left = 0)
-                const bool leB = (s1 + 1 <= max_symbol) && (eB <= slot); // past the top symbol: c_high = 0x10000 by definition
-                if (leA) {
-                    lo = s1; vlo = eA; have_lo = true;
-                    if (leB) { lo = s2; vlo = eB; }
-                    else if (s1 + 1 <= max_symbol) { hi = s2; vhi = eB; have_hi = true; }
-                } else { hi = s1; vhi = eA; have_hi = true; }
-            }
-            int step = 2;
-            while (hi - lo > 1) {                                        // the same probe in both lanes (uniform in the pair)
-                int probe;
-                if (have_lo && have_hi) probe = (lo + hi) >> 1;
-                else if (have_lo) { probe = min(lo + step, hi - 1); step <<= 1; }
-                else { probe = max(hi - step, lo + 1); step <<= 1; }
-                const uint32_t e = entry_exact(probe);
-                if (e <= slot) { lo = probe; vlo = e; have_lo = true; } else { hi = probe; vhi = e; have_hi = true; }
-            }
-            if (!have_lo) vlo = entry_exact(0);
+            // 2. proof: lane 0 evaluates entry glo, lane 1 entry glo + 1; if the hint is off, gallop away from it and bisect with the same
+            //    probe in both lanes (uniform in the pair)
+            const Proved pr = prove_symbol(glo, max_symbol, 2,
+                [&](int s1, int s2, uint32_t &eA, uint32_t &eB) __attribute__((always_inline)) {
+                    const uint32_t eM = entry_exact(odd ? s2 : s1);
+                    const uint32_t eO = pair_swap_u(eM);
+                    eA = odd ? eO : eM; eB = odd ? eM : eO;
+                },
+                entry_exact, [&](uint32_t e) __attribute__((always_inline)) { return e <= slot; });
             if (head) {
-                sh_res[k & 1][gsym][0] = vlo;
-                sh_res[k & 1][gsym][1] = vhi;
-                const int v = lo - shift;
+                sh_res[k & 1][gsym][0] = pr.vlo;
+                sh_res[k & 1][gsym][1] = pr.vhi;
+                const int v = pr.lo - shift;
                 planes[off + (long)clr * sg.plane] = (int16_t)v;
                 fplanes[off + (long)clr * sg.plane] = div255_exact((float)v);
             }
@@ -1265,29 +1226,25 @@ __global__ __launch_bounds__(64 * Q) void rans_decode_stage_lane_kernel(const fl
     Raw cur = fetch(0);
     for (int k = 0; k < K; ++k) {
         const uint32_t slot = x & 0xFFFFu;
-        uint32_t vlo = 0, vhi = 0x10000u;
-        // the five components as mix_prepare() has them -- computed for every lane (a clamped position's values where the lane is off):
+        Proved pr{ 0, 0u, 0x10000u };
+        // the five prepared components -- computed for every lane (a clamped position's values where the lane is off):
         // that makes the raw CNN outputs dead right here, so the NEXT step's are loaded into the same registers now and have the whole
         // search to arrive (no second register set, no copies)
-        float mu5[5], rs5[5], wn5[5], w5[5];
+        Mix mx;
+        float w5[5];
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
-            float mu = cur.mu[t];
-            if constexpr (clr == 1) { const float tt = cur.a0[t] * cur.y; mu = mu + tt; }
-            else if constexpr (clr == 2) { const float t1 = cur.a0[t] * cur.y; const float t2 = cur.a1[t] * cur.co; const float tt = t1 + t2; mu = mu + tt; }
-            mu5[t] = mu;
-            rs5[t] = 1.0f / ((cur.sg[t] > kScaleBound) ? cur.sg[t] : kScaleBound);
-            w5[t] = (cur.wk[t] > kWeightBound) ? cur.wk[t] : kWeightBound;
+            const Comp c = mix_component<clr>(cur.sg[t], cur.mu[t], cur.wk[t], cur.a0[t], cur.a1[t], cur.y, cur.co, w5[t]);
+            mx.mu[t] = c.mu; mx.rsig[t] = c.rsig;
         }
         const long off_k = cur.off;
         const bool on_k = cur.on;
         cur = fetch(min(k + 1, K - 1));
         if (on_k) {
-            const float ssum = (((w5[0] + w5[1]) + w5[2]) + w5[3]) + w5[4];
-            const float den = 1e-9f + ssum;
+            const float den = mix_weight_den(w5[0], w5[1], w5[2], w5[3], w5[4]);
             float c1[5], c0[5];                  // table coordinate of component t at sample point pt: u = pt c1 + c0
 #pragma unroll
-            for (int t = 0; t < 5; ++t) { wn5[t] = w5[t] / den; c1[t] = rs5[t] * kLutS; c0[t] = __builtin_fmaf(-mu5[t], c1[t], kLutZ * kLutS); }
+            for (int t = 0; t < 5; ++t) { mx.wn[t] = w5[t] / den; c1[t] = mx.rsig[t] * kLutS; c0[t] = __builtin_fmaf(-mx.mu[t], c1[t], kLutZ * kLutS); }
 
             // 1. hint: binary search on the approximate table (probes 1 .. max_symbol: regular sample points only)
             int glo = 0, ghi = max_symbol + 1;
@@ -1301,50 +1258,27 @@ __global__ __launch_bounds__(64 * Q) void rans_decode_stage_lane_kernel(const fl
                     // (which truncates) turns a NaN into 0: the index stays inside the table whatever the CNN produced; v_fract_f32 is what is left
                     const float u = __builtin_amdgcn_fmed3f(__builtin_fmaf(pt, c1[t], c0[t]), 0.0f, (float)kLutN - 0.0009765625f);
                     const float2 e2 = sh_lut[(uint32_t)u];
-                    sum = __builtin_fmaf(wn5[t], __builtin_fmaf(e2.y, __builtin_amdgcn_fractf(u), e2.x), sum);
+                    sum = __builtin_fmaf(mx.wn[t], __builtin_fmaf(e2.y, __builtin_amdgcn_fractf(u), e2.x), sum);
                 }
                 const int e = (int)__builtin_rintf(sum * gr.scale) + pi;
                 const bool le = e <= (int)slot;
                 glo = le ? pi : glo;
                 ghi = le ? ghi : pi;
             }
-            // exact table entry i, cdf_entry()'s operations in its order
-            auto entry_exact = [&](int i) -> uint32_t {
+            // exact table entry i in this lane: cdf_entry()'s operations, the terms formed before the first add (profiles/README.md, decoder_parts)
+            auto entry_exact = [&](int i) __attribute__((always_inline)) -> uint32_t {
                 const float pt = sample_pt(gr, i);
-                const float t0 = wn5[0] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[0]) * rs5[0])));
-                const float t1 = wn5[1] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[1]) * rs5[1])));
-                const float t2 = wn5[2] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[2]) * rs5[2])));
-                const float t3 = wn5[3] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[3]) * rs5[3])));
-                const float t4 = wn5[4] * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu5[4]) * rs5[4])));
-                const float acc = (((t0 + t1) + t2) + t3) + t4;
-                return (uint32_t)((int)__builtin_rintf(acc * gr.scale) + i) & 0xFFFFu;
+                float t[5];
+#pragma unroll
+                for (int c = 0; c < 5; ++c) t[c] = mix_term(mx.wn[c], mx.mu[c], mx.rsig[c], pt);
+                return entry_from_sum((((t[0] + t[1]) + t[2]) + t[3]) + t[4], gr.scale, i);
             };
-            // 2. the two entries the state update needs anyway, entry[s] and entry[s + 1], are also the proof of the hint;
-            //    if it is off, gallop away from it and bisect with exact entries (bit-identical to an exact search whatever the hint was)
-            int lo = 0, hi = max_symbol + 1;
-            bool have_lo = false, have_hi = false;
-            {
-                const int s1 = glo, s2 = min(glo + 1, max_symbol);
-                const uint32_t eA = entry_exact(s1), eB = entry_exact(s2);
-                const bool leA = (s1 == 0) || (eA <= slot);              // entry 0 is the floor of the search (torchac: left = 0)
-                const bool leB = (s1 + 1 <= max_symbol) && (eB <= slot); // past the top symbol: c_high = 0x10000 by definition
-                if (leA) {
-                    lo = s1; vlo = eA; have_lo = true;
-                    if (leB) { lo = s2; vlo = eB; }
-                    else if (s1 + 1 <= max_symbol) { hi = s2; vhi = eB; have_hi = true; }
-                } else { hi = s1; vhi = eA; have_hi = true; }
-            }
-            int step = 1;                        // (a hint that is off is off by one: the first gallop probe is the neighbour)
-            while (hi - lo > 1) {
-                int probe;
-                if (have_lo && have_hi) probe = (lo + hi) >> 1;
-                else if (have_lo) { probe = min(lo + step, hi - 1); step <<= 1; }
-                else { probe = max(hi - step, lo + 1); step <<= 1; }
-                const uint32_t e = entry_exact(probe);
-                if (e <= slot) { lo = probe; vlo = e; have_lo = true; } else { hi = probe; vhi = e; have_hi = true; }
-            }
-            if (!have_lo) vlo = entry_exact(0);
-            const int v = lo - shift;
+            // 2. the two entries the state update needs anyway, entry[s] and entry[s + 1], are also the proof of the hint; if it is off, gallop
+            //    away from it and bisect with exact entries (a hint that is off is off by one: the first gallop probe is the neighbour)
+            pr = prove_symbol(glo, max_symbol, 1,
+                [&](int s1, int s2, uint32_t &eA, uint32_t &eB) __attribute__((always_inline)) { eA = entry_exact(s1); eB = entry_exact(s2); },
+                entry_exact, [&](uint32_t e) __attribute__((always_inline)) { return e <= slot; });
+            const int v = pr.lo - shift;
             planes[off_k + (long)clr * sg.plane] = (int16_t)v;
             fplanes[off_k + (long)clr * sg.plane] = div255_exact((float)v);
         }
@@ -1358,7 +1292,7 @@ __global__ __launch_bounds__(64 * Q) void rans_decode_stage_lane_kernel(const fl
         // state update of this lane, bit-granular renormalisation: lane l of the stream takes its clz(x) bits below those of lanes < l
         int nb = 0;
         if (on_k) {
-            x = (vhi - vlo) * (x >> 16) + slot - vlo;                          // in [freq << 15, freq << 16)
+            x = (pr.vhi - pr.vlo) * (x >> 16) + slot - pr.vlo;                 // in [freq << 15, freq << 16)
             const int lz = __clz((int)x);
             badx |= lz > 16;                                                   // only a corrupt stream: the oracle rejects it too
             nb = min(lz, 16);
@@ -1403,7 +1337,7 @@ __global__ __launch_bounds__(64 * Q) void rans_decode_stage_lane_kernel(const fl
 // of ONE coder state, serially; a lone wavefront issues one instruction every ~4 cycles whatever it does, so everything that does not
 // depend on the coder state is done by other wavefronts of the workgroup:
 //   * kTailAhead wavefronts per chain PREPARE symbols: the position's CNN outputs, the component's mean / 1 / sigma / normalised
-//     weight exactly as mix_prepare() has them, the approximate mixture at the 64 anchors 8 l (Lp <= 512) -- and, round 5, a
+//     weight with mix_component()'s operations, the approximate mixture at the 64 anchors 8 l (Lp <= 512) -- and, round 5, a
 //     SPECULATED WINDOW: the twelve exact table entries around the mixture's median (where the approximate table crosses 2^15).
 //     Round r + 1's symbols are prepared (into the other half of a ping-pong LDS buffer) while
 //   * wavefront 0 DECODES round r's: if the slot lies inside the speculated window the symbol is proved by one compare, a ballot and
@@ -1511,18 +1445,17 @@ __global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_t
             return r;
         };
         auto prepare = [&](const Row &row, int buf) {
-            // component mc, exactly as mix_prepare() does
+            // component mc: mix_component<2>'s operations, written out (profiles/README.md, section decoder_parts)
             const float t1 = row.bb * row.y;
             const float t2 = row.dd * row.co;
             const float tt = t1 + t2;
             const float mu = row.mu + tt;
-            const float rsig = 1.0f / ((row.sg > kScaleBound) ? row.sg : kScaleBound);
+            const float rsig = 1.0f / mix_sigma(row.sg);
             const float w = (row.wk > kWeightBound) ? row.wk : kWeightBound;
             float wk5[5], mu5[5], rs5[5];
 #pragma unroll
             for (int k = 0; k < 5; ++k) wk5[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), k));
-            const float ssum = (((wk5[0] + wk5[1]) + wk5[2]) + wk5[3]) + wk5[4];
-            const float wn = w / (1e-9f + ssum);
+            const float wn = w / mix_weight_den(wk5[0], wk5[1], wk5[2], wk5[3], wk5[4]);
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
                 mu5[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mu), k));
@@ -1556,7 +1489,7 @@ __global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_t
                 wbs = max(8 * lst + (int)__builtin_amdgcn_fmed3f(fr, 0.0f, 8.0f) - 5, 0);
                 const int idx = wbs + min(we, 11);
                 const float ptx = sample_pt(gr, min(idx, gr.Lp - 1));
-                const float term = wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((ptx - mu) * rsig)));
+                const float term = mix_term(wn, mu, rsig, ptx);
                 const int g0 = 4 * 5 * min(we, 11);
                 const float a0 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0, __float_as_int(term)));
                 const float a1 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 4, __float_as_int(term)));
@@ -1564,8 +1497,7 @@ __global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_t
                 const float a3 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 12, __float_as_int(term)));
                 const float a4 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 16, __float_as_int(term)));
                 const float acc = (((a0 + a1) + a2) + a3) + a4;
-                const float qf = __builtin_rintf(acc * gr.scale);
-                const uint32_t ent = (idx <= max_symbol) ? ((uint32_t)((int)qf + idx) & 0xFFFFu) : 0x10000u;
+                const uint32_t ent = (idx <= max_symbol) ? entry_from_sum(acc, gr.scale, idx) : 0x10000u;
                 if (mc == 0 && we < 12) sh_spec[buf][sl][we] = (int)ent;
             }
             if (lane == 0) sh_spec[buf][sl][12] = wbs;
@@ -1681,7 +1613,7 @@ __global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_t
                 // exact entry idx (uniform in the lane's group of five): valid in every lane of the group
                 auto entry_at = [&](int idx) -> uint32_t {
                     const float pt = sample_pt(gr, min(idx, gr.Lp - 1));
-                    const float term = wn * (0.5f * erfc_spec_nobranch(kNegRsqrt2 * ((pt - mu) * rsig)));
+                    const float term = mix_term(wn, mu, rsig, pt);
                     const int g0 = 4 * 5 * min(we, 11);
                     const float a0 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0, __float_as_int(term)));
                     const float a1 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 4, __float_as_int(term)));
@@ -1689,8 +1621,7 @@ __global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_t
                     const float a3 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 12, __float_as_int(term)));
                     const float a4 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 16, __float_as_int(term)));
                     const float acc = (((a0 + a1) + a2) + a3) + a4;
-                    const float qf = __builtin_rintf(acc * gr.scale);
-                    return (idx <= max_symbol) ? ((uint32_t)((int)qf + idx) & 0xFFFFu) : 0x10000u;      // past the top symbol: c_high = 2^16
+                    return (idx <= max_symbol) ? entry_from_sum(acc, gr.scale, idx) : 0x10000u;      // past the top symbol: c_high = 2^16
                 };
                 // 1. hint: the bucket of 8 entries the prepared anchors put the slot in
                 const uint64_t p1 = ballot64(lane == 0 || (8 * lane <= max_symbol && e1 <= (int)slot));

@@ -13,3 +13,7 @@ ASAN_OPTIONS=detect_leaks=1 "$OUT/sanitize_host"
 g++ -O1 -g -std=c++17 -Wall -Wextra -Wno-unused-function -Wno-unused-parameter -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
     -o "$OUT/host_queries" "$ROOT/tests/host_queries.cpp"
 ASAN_OPTIONS=detect_leaks=1 "$OUT/host_queries" | cmp - "$ROOT/tests/golden/host_queries.txt"
+# the stage decoders' exact search from every hint of small tables (llicti_amd/csrc/prove_symbol.hpp, tests/prove_symbol_host.cpp)
+g++ -O1 -g -std=c++17 -Wall -Wextra -Wno-unused-function -Wno-unused-parameter -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+    -o "$OUT/prove_symbol_host" "$ROOT/tests/prove_symbol_host.cpp"
+ASAN_OPTIONS=detect_leaks=1 "$OUT/prove_symbol_host"

@@ -1,5 +1,5 @@
 """All seven decoder paths on adversarial mixtures (run with -m gpu on an MI355X).  The mixture CDF entry is evaluated in nine places of the kernels
-(two on the encoder's side, seven on the decoders'); the encoder's two are held to the oracle at hand-made parameter rows
+(two on the encoder's side, seven on the decoders' -- nine callers of one statement, numerics.hpp's mix_term / entry_from_sum); the encoder's two are held to the oracle at hand-made parameter rows
 (test_hip_parity.py::test_cdf_*_kernel_adversarial_params), the decoders take theirs from the CNN inside the decode calls.  Here a model
 whose last layer emits chosen biases (tests/mixture_regimes.py) hands every decoder the same regimes from the INPUTS: nothing in the library
 is switched, forced or observed.  Per regime: four 67 x 93 images as one batch through the reference format with full tables and with

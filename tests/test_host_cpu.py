@@ -381,6 +381,22 @@ def test_host_queries_match_recorded_answers(tmp_path):
         assert False, (len(want_l), len(got_l), diff)
 
 
+def test_prove_symbol_finds_the_scan_s_answer_from_every_hint(tmp_path):
+    """llicti_amd/csrc/prove_symbol.hpp is the exact search of the rANS stage decoders (the proof of the approximate table's hint, the gallop away
+    from a wrong one, the bisection; the pair and lane kernels call it, the four-lane kernel holds the same text) and has no HIP dependency:
+    tests/prove_symbol_host.cpp (plain g++) runs it as a pure function on
+    tables of 1, 2, 3, 5, 8 and 17 entries -- strictly rising, with flat stretches, saturated at the top (entry 0 above most slots), flat at 0 and
+    then a step -- from EVERY hint, for the slots 0, 65535 and every entry's value and value +- 1, with a first gallop step of 1 and of 2.  Expected:
+    what a linear scan that ignores the hint returns (the last s with s == 0 or entry[s] <= slot, entry[s], entry[s + 1] or 0x10000 at the top
+    symbol), in at most 2 + 2 ceil(log2(max_symbol + 2)) single-entry evaluations, so a gallop that degenerates to a scan fails too."""
+    import subprocess
+    exe = tmp_path / "prove_symbol_host"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tests", "prove_symbol_host.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout[-500:], out.stderr[-2000:])
+    assert "clean" in out.stdout and " 0 failures" in out.stdout, out.stdout
+
+
 def test_no_scratch_in_mfma_and_stage_kernels():
     """no kernel of the library may spill a vector register or use a private segment -- the band CNN (18 instantiations: band x
     tile rows x equal / mixed sizes) and the stage decoders least of all.  Round 5's `band_params_kernel<2,16,true>` (the heaviest kernel of the
