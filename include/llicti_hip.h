@@ -264,7 +264,7 @@ int llicti_decode_images_v(llicti_ctx *ctx, const uint8_t *d_in, size_t in_strid
  * fine and a level never reads a finer one, so the call launches the stages of levels >= reduce only: 3 x (nlevels - reduce) band-CNN launches
  * (level 0 alone holds 3/4 of the symbols and CNN positions), none at reduce = nlevels, where the output is the header's raw DC band.
  * reduce = 0 is llicti_decode_images_vm / _v: same launches, bytes and status words.  0 <= reduce <= the model's levels (5 config A, 2 config B),
- * LLICTI_EINVAL otherwise; one value per call.
+ * LLICTI_EINVAL otherwise; one value for the call (llicti_decode_images_reduced_rv below takes one per image).
  *   Hs, Ws   the FULL sizes the headers describe; modes: one mode (n_modes = 1) or one per image (n_modes = B), as for llicti_decode_images_vm;
  *            every container the full decoder reads (the reference format: equal sizes per call)
  *   d_rgb    image b's uint8 [3][Hr][Wr] at d_rgb + rgb_off[b]; rgb_off = NULL: the reduced images tightly packed in call order
@@ -415,6 +415,45 @@ int llicti_decode_images_tensor_views(llicti_ctx *ctx, const uint8_t *d_in, size
                                       int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
                                       void *d_workspace, size_t workspace_bytes,
                                       const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream);
+/* PER-IMAGE REDUCE: the five decodes above with `int reduce` replaced by `const int *reduces`, a host array of B values, 0 <= reduces[b] <= the
+ * model's levels.  Image b is decoded EXACTLY as the scalar call at reduce = reduces[b] decodes it: its output size is
+ * llicti_reduced_dims(Hs[b], Ws[b], reduces[b]), its window / box / views are in the coordinates of ITS OWN decimated grid, its status word and
+ * the integrity rule are that call's (the end-of-stream check runs for exactly the images with reduces[b] == 0), and nothing of it depends on
+ * its neighbours' values.  So one tight crop no longer sends a whole batch through level 0 (three quarters of the CNN work).
+ *   schedule   level l runs for the images with reduces[b] <= l alone: the band CNN over the tile list of those images, the stage decoders with
+ *              one workgroup per stream of those images, the tail coder for the level-0 images; the loop ends at min(reduces)
+ *   placement  rgb_off / px_off NULL: the images tightly packed in call order, each at its own reduced size
+ *   views      a view is held against the reduce of the image it names; an image no view names is still decoded to its reduces[b] -- pass the
+ *              model's level count for it (its DC band only)
+ *   workspace  what the scalar sibling takes for the same batch and modes
+ *   plan       the batch's full-size plan (llicti_decode_images_vm's with tight placement): it does not depend on the values.  What does -- the
+ *              r table, the output table or windows, the levels' stream and tile lists -- is built per call on the host, uploaded with one
+ *              asynchronous copy on `stream` from a pooled block and never cached: calls with fresh values neither build a plan, allocate nor
+ *              synchronise once the pool is warm
+ *   all equal  the call IS its scalar sibling at that value (it delegates): same launches, plan key, counters, bytes
+ * LLICTI_EINVAL before anything is launched, naming the image: reduces NULL, a value out of range, differing values with a reference-format
+ * container in the call (its pipeline codes equal sizes and one schedule per call), and whatever the sibling refuses at that image's reduce. */
+int llicti_decode_images_reduced_rv(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                    int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                    void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream);
+int llicti_decode_images_px_rv(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                               int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                               void *d_workspace, size_t workspace_bytes,
+                               uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream);
+int llicti_decode_images_tensor_rv(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                   int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                   void *d_workspace, size_t workspace_bytes,
+                                   void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
+                                   const float *mean, const float *std, void *stream);
+int llicti_decode_images_tensor_resized_rv(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                           int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                           void *d_workspace, size_t workspace_bytes,
+                                           void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
+                                           const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream);
+int llicti_decode_images_tensor_views_rv(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                         int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                         void *d_workspace, size_t workspace_bytes,
+                                         const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream);
 /* llicti_encode_images_vm on planar float32: image b's [3][Hs[b]][Ws[b]] block at ELEMENT offset x_off[b] of d_x (NULL = the blocks back to back
  * in call order).  A sample x becomes the pixel value v = (int)rintf(x * 255.0f) -- one rounded fp32 product, rounded half to even
  * (torch.round) --, clamped to 0 .. 255, a NaN gives 0; containers and segment lengths are byte for byte those of the uint8 call on v, under

@@ -106,6 +106,12 @@ _SIGS = {
     "llicti_resize_axis": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_float), _i]),
     "llicti_decode_images_tensor_resized": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "llicti_decode_images_tensor_views": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(ViewGroup), _i, _vp, _vp, _vp]),
+    # per-image reduce: the siblings above with `int reduce` (argument 9) replaced by a host array of B ints
+    "llicti_decode_images_reduced_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "llicti_decode_images_px_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp]),
+    "llicti_decode_images_tensor_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "llicti_decode_images_tensor_resized_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "llicti_decode_images_tensor_views_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, C.POINTER(ViewGroup), _i, _vp, _vp, _vp]),
     "llicti_encode_images_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_transcode_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i]),

@@ -310,11 +310,13 @@ def _box_must_fit(H, W, box):
         raise ValueError(f"box (y0 {y0}, x0 {x0}, {h} x {w}) leaves its {H} x {W} image")
 
 
-def resized_crop_plan(sizes, boxes_full, size, nlevels=5):
+def resized_crop_plan(sizes, boxes_full, size, nlevels=5, per_image=False):
     """The `reduce` a batch of resized crops can be decoded at, and its boxes on that grid.  sizes: (H, W) per image; boxes_full: (y0, x0, h, w)
     per image in FULL-resolution pixels (torchvision's RandomResizedCrop.get_params order); size = (Ho, Wo) -> (reduce, boxes_reduced) for
-    decode_tensor_resized.  reduce is ONE value per call, as the decoder requires: the largest r in 0 .. nlevels at which EVERY image's box
-    still has at least Ho rows and Wo columns of decoded pixels (0 if none has: the boxes are then magnified).  A box maps to the pixels of the
+    decode_tensor_resized.  reduce is ONE value for the call: the largest r in 0 .. nlevels at which EVERY image's box
+    still has at least Ho rows and Wo columns of decoded pixels (0 if none has: the boxes are then magnified) -- one tight crop sends the whole
+    batch through level 0.  per_image=True -> ([r_b], boxes_reduced) for decode_tensor_resized(reduce=[...]): r_b is the largest r at which
+    image b's OWN box keeps Ho x Wo decoded pixels (0 if none does), and box b is mapped to its image's grid.  A box maps to the pixels of the
     decimated grid that lie inside it: y0r = ceil(y0 / 2^r), y1r = floor((y0 + h - 1) / 2^r) + 1, and the same for the columns.
     A REDUCED DECODE IS A DECIMATION -- every 2^r-th pixel of the image, taken without a low-pass filter -- so it ALIASES: fine detail of the
     source folds into the crop, where a full decode followed by an antialiased resize would have averaged it out.  What is gained is that the r
@@ -324,6 +326,9 @@ def resized_crop_plan(sizes, boxes_full, size, nlevels=5):
     assert len(sizes) == len(boxes_full) and Ho >= 1 and Wo >= 1
     for (H, W), box in zip(sizes, boxes_full):
         _box_must_fit(H, W, box)
+    if per_image:
+        rs = [max([0] + [r for r in range(1, int(nlevels) + 1) if _box_on_grid(b, r)[2] >= Ho and _box_on_grid(b, r)[3] >= Wo]) for b in boxes_full]
+        return rs, [_box_on_grid(b, r) for b, r in zip(boxes_full, rs)]
     reduce = 0
     for r in range(1, int(nlevels) + 1):
         if all(m[2] >= Ho and m[3] >= Wo for m in (_box_on_grid(b, r) for b in boxes_full)):
@@ -334,12 +339,14 @@ def resized_crop_plan(sizes, boxes_full, size, nlevels=5):
 VIEW_SLICE = 128               # views per launch of the views call's last kernel (kViewMax: a longer group takes several launches)
 
 
-def multi_crop_plan(sizes, groups_full, nlevels=5):
+def multi_crop_plan(sizes, groups_full, nlevels=5, per_image=False):
     """resized_crop_plan for views (decode_tensor_views): several crops per image, of several output sizes, from ONE decode.  sizes: (H, W) per
     image; groups_full: a list of (size, image_indices, boxes_full) -- size = (Ho, Wo) of the group, image_indices[v] the image view v is cut
     from (None: view v is image v), boxes_full[v] = (y0, x0, h, w) in FULL-resolution pixels of that image -> (reduce, [boxes_reduced per
-    group]).  reduce is ONE value per call: the largest r in 0 .. nlevels at which EVERY view of EVERY group still has at least Ho x Wo decoded
-    pixels of its group's size in its box (0 if none has) -- the small crops of a multi-crop set decide it.  The box mapping is
+    group]).  reduce is ONE value for the call: the largest r in 0 .. nlevels at which EVERY view of EVERY group still has at least Ho x Wo decoded
+    pixels of its group's size in its box (0 if none has) -- the small crops of a multi-crop set decide it.  per_image=True -> ([r_b], the
+    same) for decode_tensor_views(reduce=[...]): r_b is the smallest such r over the views that name image b, nlevels for an image no view
+    names (its DC band only), and every view's box is mapped to its image's grid.  The box mapping is
     resized_crop_plan's, and so is what it says about a reduced decode: a DECIMATION, which aliases.  For one group with image_indices None it
     returns what resized_crop_plan returns.  Pure Python, no device."""
     sizes = list(sizes)
@@ -353,12 +360,36 @@ def multi_crop_plan(sizes, groups_full, nlevels=5):
             if not 0 <= b < len(sizes):
                 raise ValueError(f"a view names image {b}: the batch has images 0 .. {len(sizes) - 1}")
             _box_must_fit(sizes[b][0], sizes[b][1], box)
-        groups.append((Ho, Wo, boxes))
+        groups.append((Ho, Wo, boxes, image))
+    if per_image:
+        rs = [int(nlevels)] * len(sizes)
+        for Ho, Wo, boxes, image in groups:
+            for b, box in zip(image, boxes):
+                rs[b] = min(rs[b], max([0] + [r for r in range(1, int(nlevels) + 1) if _box_on_grid(box, r)[2] >= Ho and _box_on_grid(box, r)[3] >= Wo]))
+        return rs, [[_box_on_grid(box, rs[b]) for b, box in zip(image, boxes)] for _, _, boxes, image in groups]
+    groups = [g[:3] for g in groups]
     reduce = 0
     for r in range(1, int(nlevels) + 1):
         if all(m[2] >= Ho and m[3] >= Wo for Ho, Wo, boxes in groups for m in (_box_on_grid(b, r) for b in boxes)):
             reduce = r
     return reduce, [[_box_on_grid(b, reduce) for b in boxes] for _, _, boxes in groups]
+
+
+def _reduce_arg(reduce, B):
+    """`reduce=` of the decode calls: one int for the call -> (r, None); a sequence of B ints, image b stopping at its own level
+    (the llicti_decode_images_*_rv calls) -> (None, int32 array)."""
+    if isinstance(reduce, (int, np.integer)):
+        return int(reduce), None
+    rv = np.ascontiguousarray(list(reduce), dtype=np.int32)
+    if rv.shape != (B,):
+        raise ValueError(f"reduce: {rv.size} values for a batch of {B} images (one int, or one per image)")
+    return None, rv
+
+
+def _reduced_sizes(Hs, Ws, r, rv):
+    """every image's decoded size at the call's reduce r, or at its own rv[b] (a value the library will refuse counts as 0 here: the call says so)"""
+    rs = [r] * len(Hs) if rv is None else [int(v) for v in rv]
+    return [reduced_dims(h, w, k) if 0 <= k <= 5 else (int(h), int(w)) for h, w, k in zip(Hs, Ws, rs)]
 
 
 def _ptr(t):
@@ -643,13 +674,15 @@ class HipCodec:
         """llicti_decode_images_reduced: device containers of B images of FULL sizes Hs[b] x Ws[b] (mode: one, or one per image) -> flat uint8
         device tensor holding image b's [3][Hr][Wr] block (reduced_dims) at byte rgb_off[b], or back to back (rgb_off None), async.  Only the
         stages of levels >= reduce are launched; a rANS container's end-of-stream check (the last stage's tail coder) is therefore not run for
-        reduce >= 1: check() / image_status() report what the launched kernels flag.  reduce = 0 is decode_v."""
+        reduce >= 1: check() / image_status() report what the launched kernels flag.  reduce = 0 is decode_v.
+        reduce may be a sequence of B ints (llicti_decode_images_reduced_rv): image b stops at its own level reduce[b] and is exactly what the
+        call at that one value gives for it -- size, bytes, status word; level l runs for the images with reduce[b] <= l alone."""
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
         assert containers.shape[0] == B
         ws = self.workspace_v(Hs, Ws, mode)          # (the full decode's: a reduced call uses the same layout)
-        r = int(reduce)
-        dims = [reduced_dims(h, w, r) if 0 <= r <= 5 else (int(h), int(w)) for h, w in zip(Hs, Ws)]      # (a bad r: the library says so)
+        r, rv = _reduce_arg(reduce, B)
+        dims = _reduced_sizes(Hs, Ws, r, rv)      # (a bad r: the library says so)
         sizes = [3 * h * w for h, w in dims]
         if rgb_off is None:
             offs, total = None, sum(sizes)
@@ -662,9 +695,10 @@ class HipCodec:
         assert out.numel() >= total
         one, per = self._modes_arg(mode, B)
         modes = np.array([one], dtype=np.int32) if per is None else per
-        _lib.check(self.L.llicti_decode_images_reduced(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                                                       _ptr(modes), len(modes), r, _ptr(ws), ws.numel(), _ptr(out), _ptr(offs),
-                                                       _stream_ptr(self.device)))
+        fn = self.L.llicti_decode_images_reduced if rv is None else self.L.llicti_decode_images_reduced_rv
+        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), _ptr(offs),
+                      _stream_ptr(self.device)))
         return out
 
     # ---- interleaved, pitched pixels (llicti_encode_images_px / llicti_decode_images_px): the layout image sources deliver
@@ -706,12 +740,13 @@ class HipCodec:
     def decode_px(self, containers, seg_len, Hs, Ws, mode, fmt=PIX_RGB8, reduce=0, out=None, px_off=None, pitch=None):
         """device containers of B images of FULL sizes Hs[b] x Ws[b] -> flat uint8 device tensor of interleaved pixels: image b's window (of
         reduced_dims(Hs[b], Ws[b], reduce)) at byte px_off[b] with rows pitch[b] bytes apart (None: back to back / tight).  Only the bytes of
-        the windows' rows are written -- `out` may be a canvas whose other bytes must stay; alpha is written as 255.  reduce as decode_reduced.  Async."""
+        the windows' rows are written -- `out` may be a canvas whose other bytes must stay; alpha is written as 255.  reduce as decode_reduced
+        (an int, or one per image: image b's window then has reduced_dims(Hs[b], Ws[b], reduce[b])).  Async."""
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
         assert containers.shape[0] == B
-        r = int(reduce)
-        dims = [reduced_dims(h, w, r) if 0 <= r <= 5 else (int(h), int(w)) for h, w in zip(Hs, Ws)]      # (a bad r: the library says so)
+        r, rv = _reduce_arg(reduce, B)
+        dims = _reduced_sizes(Hs, Ws, r, rv)      # (a bad r: the library says so)
         fmt, offs, pt, total = self._px_layout(fmt, dims, px_off, pitch)
         ws = self.workspace_v(Hs, Ws, mode)
         if out is None:
@@ -719,15 +754,16 @@ class HipCodec:
         assert out.dtype == torch.uint8 and out.dim() == 1 and out.numel() >= total
         one, per = self._modes_arg(mode, B)
         modes = np.array([one], dtype=np.int32) if per is None else per
-        _lib.check(self.L.llicti_decode_images_px(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                                                  _ptr(modes), len(modes), r, _ptr(ws), ws.numel(), _ptr(out), fmt, _ptr(offs), _ptr(pt),
-                                                  _stream_ptr(self.device)))
+        fn = self.L.llicti_decode_images_px if rv is None else self.L.llicti_decode_images_px_rv
+        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), fmt, _ptr(offs), _ptr(pt),
+                      _stream_ptr(self.device)))
         return out
 
     def decode_v(self, containers, seg_len, Hs, Ws, mode, out=None, reduce=0):
         """device containers of B images of sizes Hs[b] x Ws[b] -> flat uint8 device tensor (the images back to back), async.
-        reduce = r: the images at reduced_dims(Hs[b], Ws[b], r), back to back (decode_reduced)."""
-        if reduce:
+        reduce = r: the images at reduced_dims(Hs[b], Ws[b], r), back to back (decode_reduced); one r per image: each at its own size."""
+        if not isinstance(reduce, (int, np.integer)) or reduce:
             return self.decode_reduced(containers, seg_len, Hs, Ws, mode, reduce, out=out)
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
@@ -754,7 +790,8 @@ class HipCodec:
         flip: B flags, a set one mirrors that window left to right; mean, std: 3 floats each (both or neither).  The values are those of
         torchvision's ToTensor + Normalize on the CPU, bit for bit: v / 255 (one fp32 division), then (x - mean[c]) / std[c], then dtype's
         round-to-nearest-even.  Origins and flips are per-call data: calls that differ only in them share one cached plan.  `out`: a contiguous
-        [B, 3, Ho, Wo] tensor of that dtype to write into (nothing outside it is touched).  reduce as decode_reduced."""
+        [B, 3, Ho, Wo] tensor of that dtype to write into (nothing outside it is touched).  reduce as decode_reduced (an int, or one per image:
+        image b's origin is then in the coordinates of its own decimated grid)."""
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
         assert containers.shape[0] == B
@@ -776,9 +813,11 @@ class HipCodec:
         assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
         one, per = self._modes_arg(mode, B)
         modes = np.array([one], dtype=np.int32) if per is None else per
-        _lib.check(self.L.llicti_decode_images_tensor(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                                                      _ptr(modes), len(modes), int(reduce), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
-                                                      _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
+        r, rv = _reduce_arg(reduce, B)
+        fn = self.L.llicti_decode_images_tensor if rv is None else self.L.llicti_decode_images_tensor_rv
+        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
+                      _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
         return out
 
     def decode_tensor_resized(self, containers, seg_len, Hs, Ws, mode, size, boxes, dtype=torch.float32, flip=None, mean=None, std=None, antialias=True,
@@ -789,7 +828,9 @@ class HipCodec:
         RandomResizedCrop + flip + ToTensor + Normalize on a batch of mixed sizes.  The filter is F.interpolate's bilinear one
         (align_corners=False); antialias=True widens it by the scale when a box shrinks, up to a scale of 4 per axis -- beyond that raise
         `reduce` (resized_crop_plan picks it).  A box of Ho x Wo gives decode_tensor's bytes.  Boxes, flips, size and flag are per-call data:
-        calls that differ only in them share decode_reduced's cached plan and neither allocate nor synchronise."""
+        calls that differ only in them share decode_reduced's cached plan and neither allocate nor synchronise.  reduce: an int, or one per image
+        (resized_crop_plan(..., per_image=True)): box b is then in the coordinates of image b's own decimated grid, and a tight crop no longer
+        sends its neighbours through the finest levels."""
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
         assert containers.shape[0] == B
@@ -813,10 +854,12 @@ class HipCodec:
         one, per = self._modes_arg(mode, B)
         modes = np.array([one], dtype=np.int32) if per is None else per
         aa = int(antialias) if isinstance(antialias, (bool, int, np.integer)) else -1
-        _lib.check(self.L.llicti_decode_images_tensor_resized(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                                                              _ptr(modes), len(modes), int(reduce), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
-                                                              _ptr(y0), _ptr(x0), _ptr(bh), _ptr(bw), _ptr(fl), _ptr(mn), _ptr(sd), aa,
-                                                              _stream_ptr(self.device)))
+        r, rv = _reduce_arg(reduce, B)
+        fn = self.L.llicti_decode_images_tensor_resized if rv is None else self.L.llicti_decode_images_tensor_resized_rv
+        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
+                      _ptr(y0), _ptr(x0), _ptr(bh), _ptr(bw), _ptr(fl), _ptr(mn), _ptr(sd), aa,
+                      _stream_ptr(self.device)))
         return out
 
     def decode_tensor_views(self, containers, seg_len, Hs, Ws, mode, groups, mean=None, std=None, reduce=0):
@@ -826,7 +869,9 @@ class HipCodec:
         image v) with box boxes[v] (decoded coordinates, the reduced ones for reduce >= 1; None: the whole image), to the bit.  -> a list
         of one device tensor [n, 3, Ho, Wo] per group, async.  Outputs of different groups must not overlap.  The batch is decoded once;
         every view costs one more pass of the last kernel.  Image indices, boxes and flips are per-call data: calls that differ only in
-        them share decode_reduced's cached plan and neither allocate nor synchronise.  multi_crop_plan picks reduce."""
+        them share decode_reduced's cached plan and neither allocate nor synchronise.  multi_crop_plan picks reduce: an int, or one per image
+        (per_image=True) -- a view's box is then in the coordinates of ITS image's decimated grid, and an image no view names may be passed at
+        the model's level count."""
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
         assert containers.shape[0] == B
@@ -868,9 +913,11 @@ class HipCodec:
         assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
         one, per = self._modes_arg(mode, B)
         modes = np.array([one], dtype=np.int32) if per is None else per
-        _lib.check(self.L.llicti_decode_images_tensor_views(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                                                            _ptr(modes), len(modes), int(reduce), _ptr(ws), ws.numel(), arr, len(groups),
-                                                            _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
+        r, rv = _reduce_arg(reduce, B)
+        fn = self.L.llicti_decode_images_tensor_views if rv is None else self.L.llicti_decode_images_tensor_views_rv
+        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
+                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), arr, len(groups),
+                      _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
         return outs
 
     def encode_f32(self, x_flat, Hs, Ws, mode, x_off=None, out=None, seg_len=None):

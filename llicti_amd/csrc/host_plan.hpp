@@ -497,7 +497,9 @@ static void plan_add_pixels(Plan &p, const std::vector<PixGeo> &pix)
 struct TensorArgs { int dtype, Ho, Wo; const int *y0, *x0; const uint8_t *flip; const float *mean, *std; };
 // ... and validated against the call's images (FULL sizes Hs, Ws, decoded at `reduce`): every image's packed window word (tensor_win_pack) and
 // the normalisation constants.  These are the call's kernel arguments -- nothing of them enters the plan or its key.
-static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, int reduce, const TensorArgs &t, std::vector<uint32_t> &wins, TensorNorm &nm)
+// rv != nullptr (the _rv calls): image b is held against its own reduce rv[b], and `reduce` is not read.
+static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, int reduce, const TensorArgs &t, std::vector<uint32_t> &wins, TensorNorm &nm,
+                          const int *rv = nullptr)
 {
     if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
     if (t.Ho < 1 || t.Wo < 1) return fail(LLICTI_EINVAL, "%s: output size %dx%d (need Ho, Wo >= 1)", who, t.Wo, t.Ho);
@@ -513,6 +515,7 @@ static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, 
     wins.assign(B, 0u);
     for (int b = 0; b < B; ++b) {
         const int y0 = t.y0 ? t.y0[b] : 0, x0 = t.x0 ? t.x0[b] : 0;
+        if (rv) reduce = rv[b];
         if (!tensor_window_ok(Hs[b], Ws[b], reduce, y0, x0, t.Ho, t.Wo))
             return fail(LLICTI_EINVAL, "%s: the %dx%d window at (y %d, x %d) leaves image %d (%dx%d at reduce %d)", who, t.Wo, t.Ho, y0, x0, b,
                         reduced_dim(Ws[b], reduce), reduced_dim(Hs[b], reduce), reduce);
@@ -560,14 +563,15 @@ static int resolve_resize_box(const char *who, const char *whose, int H, int W, 
     words[1] = resize_ext_pack(hs, ws);
     return 0;
 }
-static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ResizeArgs &t, std::vector<uint32_t> &boxes, TensorNorm &nm)
+static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ResizeArgs &t, std::vector<uint32_t> &boxes, TensorNorm &nm,
+                          const int *rv = nullptr)
 {
-    if (int rc = resolve_resize_head(who, reduce, t, nm)) return rc;
+    if (int rc = resolve_resize_head(who, rv ? 0 : reduce, t, nm)) return rc;
     boxes.assign(2 * (size_t)B, 0u);
     for (int b = 0; b < B; ++b) {
         char whose[32];
         snprintf(whose, sizeof whose, "image %d", b);
-        if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], reduce, t, b, &boxes[2 * (size_t)b])) return rc;
+        if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], rv ? rv[b] : reduce, t, b, &boxes[2 * (size_t)b])) return rc;
     }
     return 0;
 }
@@ -577,8 +581,9 @@ struct ViewArgs { const llicti_view_group *groups; int G; const float *mean, *st
 // ... and one validated group: three packed words per view (ViewSlice), kernel arguments of the group's launches like the boxes above
 struct ViewGroupOut { void *d_out; int dtype, Ho, Wo, antialias, n; std::vector<uint32_t> words; };
 // Every view is held to resolve_resize's rules against the image it names (resolve_resize_head, resolve_resize_box: the same functions, the
-// same words); a refusal names the group and the view.
-static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ViewArgs &a, std::vector<ViewGroupOut> &out, TensorNorm &nm)
+// same words); a refusal names the group and the view.  rv != nullptr (the _rv call): a view is held against the reduce of the image it names.
+static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ViewArgs &a, std::vector<ViewGroupOut> &out, TensorNorm &nm,
+                         const int *rv = nullptr)
 {
     if (a.G < 1 || a.G > LLICTI_VIEW_GROUPS_MAX) return fail(LLICTI_EINVAL, "%s: %d groups (need 1 .. %d)", who, a.G, LLICTI_VIEW_GROUPS_MAX);
     if (!a.groups) return fail(LLICTI_EINVAL, "%s: null groups", who);
@@ -591,7 +596,7 @@ static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, i
         if (vg.n < 1 || vg.n > kViewCountMax) return fail(LLICTI_EINVAL, "%s: n = %d views (need 1 .. %d)", whose, vg.n, kViewCountMax);
         if (!vg.image && vg.n != B) return fail(LLICTI_EINVAL, "%s: image = NULL means view v is image v: n = %d, the batch has %d images", whose, vg.n, B);
         const ResizeArgs t{ vg.dtype, vg.Ho, vg.Wo, vg.y0, vg.x0, vg.hs, vg.ws, vg.flip, a.mean, a.std, vg.antialias };
-        if (int rc = resolve_resize_head(whose, reduce, t, nm)) return rc;
+        if (int rc = resolve_resize_head(whose, rv ? 0 : reduce, t, nm)) return rc;
         ViewGroupOut &o = out[(size_t)g];
         o.d_out = vg.d_out; o.dtype = vg.dtype; o.Ho = vg.Ho; o.Wo = vg.Wo; o.antialias = vg.antialias; o.n = vg.n;
         o.words.assign(3 * (size_t)vg.n, 0u);
@@ -599,7 +604,7 @@ static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, i
             const int b = vg.image ? vg.image[v] : v;
             if (b < 0 || b >= B) return fail(LLICTI_EINVAL, "%s: view %d of group %d names image %d (the batch has images 0 .. %d)", who, v, g, b, B - 1);
             snprintf(whose, sizeof whose, "view %d of group %d (image %d)", v, g, b);
-            if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], reduce, t, v, &o.words[3 * (size_t)v])) return rc;
+            if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], rv ? rv[b] : reduce, t, v, &o.words[3 * (size_t)v])) return rc;
             o.words[3 * (size_t)v + 2] = (uint32_t)b;
         }
     }
@@ -790,6 +795,118 @@ static int admit_transcode(int nlev, bool ragged, int B, const int *Hs, const in
     if (int rc = check_stream_bits("transcode_images (target)", nlev, B, Hs, Ws, *MEd, Msd)) return rc;
     if (int rc = check_transcode_sizes("transcode_images", B, Hs, Ws, *MEs, *MEd, ragged)) return rc;
     return check_header_grid("transcode_images", nlev, B, Hs, Ws);
+}
+
+// ------------------------------------------------------------------------------------------------ per-image reduce
+// The _rv calls (llicti_decode_images_reduced_rv and its four kin): image b stops at its OWN level reduces[b].  The cached plan is the batch's
+// full-size one with tight placement -- it does not depend on the values -- and everything that does is PER CALL data, built here: the r table,
+// the reduced output table (or the pixel windows), for each level the streams of the images that take part in it (r_b <= lvl), and for each
+// (level, band) the band CNN's tile list over those images with its TileRun (form chosen over the ACTIVE images: choose_tile_form).  The call
+// copies the tables into one pooled block, uploads it with one asynchronous copy and hands the block back behind its last kernel; none of it
+// enters the plan cache.
+//
+// What the calls refuse on the values alone: a null array, a value outside 0 .. nlev (naming the image), and differing values with a
+// reference-format container (ME's count is 0), whose pipeline codes equal sizes and one schedule per call.
+static int admit_reduces(const char *who, int B, const int *reduces, int nlev, int ME)
+{
+    if (!reduces) return fail(LLICTI_EINVAL, "%s: null reduces (one value per image)", who);
+    for (int b = 0; b < B; ++b)
+        if (reduces[b] < 0 || reduces[b] > nlev)
+            return fail(LLICTI_EINVAL, "%s: reduces[%d] = %d of image %d (a %d-level model decodes at reduce 0 .. %d)", who, b, reduces[b], b, nlev, nlev);
+    if ((ME & 0xFF) == 0)
+        for (int b = 1; b < B; ++b)
+            if (reduces[b] != reduces[0])
+                return fail(LLICTI_EINVAL, "%s: image %d has reduce %d, image 0 reduce %d -- a reference-format container codes one schedule per call "
+                            "(per-image reduces need rANS containers)", who, b, reduces[b], reduces[0]);
+    return 0;
+}
+static bool reduces_equal(int B, const int *reduces)
+{
+    for (int b = 1; b < B; ++b) if (reduces[b] != reduces[0]) return false;
+    return true;
+}
+struct ReduceSchedule {
+    int B = 0, nlev = 0, rmin = 0;
+    std::vector<int> r;                   // [B]
+    std::vector<RedGeo> red;              // [B]: every image's reduced size (its full one at r = 0) and where its planar output goes
+    long max_rplane = 0;                  // largest Hr * Wr
+    std::vector<int> streams;             // the levels' lists of active streams (indices into the plan's stream table, ascending), back to back
+    size_t s_off[LLICTI_NLEVELS] = {};
+    int s_n[LLICTI_NLEVELS] = {};
+    std::vector<TileRef> tiles;           // the (level, band) tile lists, back to back; image-major, rows, columns -- build_plan's order
+    TileRun run[LLICTI_NLEVELS * 3];      // n_tiles = 0: no image takes part in the level, nothing is launched
+    std::vector<PixGeo> pix;              // the pixel call's windows (empty otherwise)
+    long pix_units = 0;
+    // the device block
+    size_t d_r = 0, d_red = 0, d_streams = 0, d_tiles = 0, d_pix = 0, d_total = 0;
+};
+// p: the batch's plan (build_plan; its host tile list may be gone).  out_off: the planar outputs' byte offsets (nullptr: tight in call order, each
+// image at its own reduced size).  pix: the pixel call's validated windows (resolve_pixels on the reduced sizes), or nullptr.
+static void build_reduce_schedule(ReduceSchedule &q, const Plan &p, const int *reduces, const size_t *out_off, int n_cu, int tile_rows,
+                                  const std::vector<PixGeo> *pix = nullptr)
+{
+    const int B = p.B, nlev = p.nlev;
+    q.B = B; q.nlev = nlev;
+    q.r.assign(reduces, reduces + B);
+    q.rmin = nlev;
+    for (int b = 0; b < B; ++b) q.rmin = std::min(q.rmin, q.r[b]);
+    q.red.assign(B, RedGeo{});
+    q.max_rplane = 0; q.pix_units = 0;
+    long pos = 0;
+    for (int b = 0; b < B; ++b) {
+        RedGeo &rg = q.red[b];
+        rg.Hr = reduced_dim(p.img[b].H, q.r[b]); rg.Wr = reduced_dim(p.img[b].W, q.r[b]);
+        rg.off = out_off ? (long)out_off[b] : pos;
+        pos += 3L * rg.Hr * rg.Wr;
+        q.max_rplane = std::max(q.max_rplane, (long)rg.Hr * rg.Wr);
+        q.pix_units = std::max(q.pix_units, (long)rg.Hr * ((rg.Wr + 3) / 4));
+    }
+    q.pix.clear();
+    if (pix) q.pix = *pix;
+    q.streams.clear(); q.tiles.clear();
+    for (int k = 0; k < LLICTI_NLEVELS * 3; ++k) q.run[k] = TileRun{};
+    for (int l = 0; l < LLICTI_NLEVELS; ++l) { q.s_off[l] = 0; q.s_n[l] = 0; }
+    for (int lvl = nlev - 1; lvl >= q.rmin; --lvl) {
+        q.s_off[lvl] = q.streams.size();
+        for (int i = 0; i < p.nstreams; ++i) if (q.r[p.sref[(size_t)i].b] <= lvl) q.streams.push_back(i);
+        q.s_n[lvl] = (int)(q.streams.size() - q.s_off[lvl]);
+        const Geom *gl = &p.geo[(size_t)lvl * B];
+        auto count = [&](int th) -> long {
+            long t = 0;
+            for (int b = 0; b < B; ++b) if (q.r[b] <= lvl) t += (long)((gl[b].w + kTileW - 1) / kTileW) * ((gl[b].h + th - 1) / th);
+            return t;
+        };
+        if (count(kTileHMax) == 0) continue;
+        for (int band = 0; band < 3; ++band) {
+            const TileForm f = choose_tile_form(n_cu, tile_rows, band, count);
+            TileRun &r = q.run[lvl * 3 + band];
+            r.off = q.tiles.size(); r.n_tiles = (int)std::min<long>(f.n_tiles, 0x7FFFFFFFL); r.TH = f.TH; r.gx = f.gx;
+            for (int b = 0; b < B; ++b) {
+                if (q.r[b] > lvl) continue;
+                const int tx_n = (gl[b].w + kTileW - 1) / kTileW, ty_n = (gl[b].h + f.TH - 1) / f.TH;
+                for (int ty = 0; ty < ty_n; ++ty)
+                    for (int tx = 0; tx < tx_n; ++tx) q.tiles.push_back(TileRef{ b, (ty << 16) | tx });
+            }
+        }
+    }
+    size_t d = 0;
+    auto dtake = [&](size_t bytes) { size_t r = d; d = align_up(d + bytes, 256); return r; };
+    q.d_r = dtake(q.r.size() * sizeof(int));
+    q.d_red = dtake(q.red.size() * sizeof(RedGeo));
+    q.d_streams = dtake(q.streams.size() * sizeof(int));
+    q.d_tiles = dtake(q.tiles.size() * sizeof(TileRef));
+    q.d_pix = dtake(q.pix.size() * sizeof(PixGeo));
+    q.d_total = std::max<size_t>(d, 256);
+}
+// the tables into the block's host side, at their offsets
+static void write_reduce_schedule(const ReduceSchedule &q, uint8_t *h)
+{
+    auto put = [&](size_t off, const void *src, size_t n) { if (n) memcpy(h + off, src, n); };
+    put(q.d_r, q.r.data(), q.r.size() * sizeof(int));
+    put(q.d_red, q.red.data(), q.red.size() * sizeof(RedGeo));
+    put(q.d_streams, q.streams.data(), q.streams.size() * sizeof(int));
+    put(q.d_tiles, q.tiles.data(), q.tiles.size() * sizeof(TileRef));
+    put(q.d_pix, q.pix.data(), q.pix.size() * sizeof(PixGeo));
 }
 
 // ------------------------------------------------------------------------------------------------ size queries

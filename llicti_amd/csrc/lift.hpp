@@ -224,13 +224,16 @@ __global__ __launch_bounds__(256) void unlift_kernel(const int16_t *__restrict__
 // (i << r, j << r) -- final once level r has been decoded; the finer levels' pixels are never written and never read here -- through the same
 // inverse YCoCg-R, written as compact planar uint8 [3][Hr][Wr] at rv[b].off.  One thread per output pixel; image b's sizes and offsets are
 // scalar loads from the call's tables.  Latches the call's status words like unlift_kernel.
+// rtab != nullptr (llicti_decode_images_reduced_rv): image b stops at ITS OWN level, r = rtab[b] (0: its full size) -- one more scalar load
+// beside iv[b]'s; rv[b] holds the sizes that go with it.
 __global__ __launch_bounds__(256) void unlift_reduced_kernel(const int16_t *__restrict__ planes, uint8_t *__restrict__ rgb, int r,
                                                              const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
                                                              int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
-                                                             const RedGeo *__restrict__ rv)
+                                                             const RedGeo *__restrict__ rv, const int *__restrict__ rtab = nullptr)
 {
     const int b = blockIdx.y;
     latch_status(status, status_head, latched, img_latched, b);
+    if (rtab) r = rtab[b];
     const int W = iv[b].W, Hr = rv[b].Hr, Wr = rv[b].Wr;
     const long plane = iv[b].plane, rplane = (long)Hr * Wr;
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -363,10 +366,12 @@ __device__ __forceinline__ void unlift_px_rows(const int16_t *__restrict__ src, 
 __global__ __launch_bounds__(256) void unlift_px_kernel(const int16_t *__restrict__ planes, uint8_t *__restrict__ pix, int r,
                                                         const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
                                                         int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
-                                                        const RedGeo *__restrict__ rv, const PixGeo *__restrict__ pv)
+                                                        const RedGeo *__restrict__ rv, const PixGeo *__restrict__ pv,
+                                                        const int *__restrict__ rtab = nullptr)
 {
     const int b = blockIdx.y;
     latch_status(status, status_head, latched, img_latched, b);
+    if (rtab) r = rtab[b];      // (the _rv call: the image's own level, wave-uniform; an image at 0 takes the full-size vector path below)
     const int W = iv[b].W, Ho = rv ? rv[b].Hr : iv[b].H, Wo = rv ? rv[b].Wr : W, pitch = pv[b].pitch, fmt = pv[b].fmt;
     const long plane = iv[b].plane;
     const int16_t *src = planes + iv[b].pix_off;
@@ -424,10 +429,12 @@ template <typename T>
 __global__ __launch_bounds__(256) void unlift_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
                                                             const TensorWins wins, const TensorNorm nm,
                                                             const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
-                                                            int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv)
+                                                            int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
+                                                            const int *__restrict__ rtab = nullptr)
 {
     const int b = b0 + blockIdx.y;
     latch_status(status, status_head, latched, img_latched, b);
+    if (rtab) r = rtab[b];      // (the _rv call: the image's own level, wave-uniform)
     const uint32_t wd = wins.w[blockIdx.y];
     const int y0 = (int)(wd & 0x1FFFu), x0 = (int)((wd >> 13) & 0x1FFFu);
     const bool flip = ((wd >> 26) & 1u) != 0;
@@ -536,10 +543,12 @@ template <typename T>
 __global__ __launch_bounds__(256) void unlift_resize_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
                                                                    int tiles_x, int antialias, const ResizeBoxes boxes, const TensorNorm nm,
                                                                    const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
-                                                                   int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv)
+                                                                   int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
+                                                                   const int *__restrict__ rtab = nullptr)
 {
     const int b = b0 + blockIdx.y;
     latch_status(status, status_head, latched, img_latched, b);
+    if (rtab) r = rtab[b];      // (the _rv call: the image's own level, wave-uniform)
     resize_tile<T>(planes, out, (long)b, r, Ho, Wo, tiles_x, antialias, boxes.w[2 * blockIdx.y], boxes.w[2 * blockIdx.y + 1], nm, iv, b);
 }
 
@@ -551,9 +560,11 @@ template <typename T>
 __global__ __launch_bounds__(256) void unlift_views_tensor_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int v0,
                                                                   int tiles_x, int antialias, const ViewSlice views, const TensorNorm nm,
                                                                   const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
-                                                                  int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv, int latch_n)
+                                                                  int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv, int latch_n,
+                                                                  const int *__restrict__ rtab = nullptr)
 {
     if (blockIdx.x == 0 && blockIdx.y == 0 && latch_n > 0) latch_status_all(status, status_head, latched, img_latched, latch_n);
-    resize_tile<T>(planes, out, (long)v0 + blockIdx.y, r, Ho, Wo, tiles_x, antialias, views.w[3 * blockIdx.y], views.w[3 * blockIdx.y + 1], nm, iv,
-                   (int)views.w[3 * blockIdx.y + 2]);
+    const int b = (int)views.w[3 * blockIdx.y + 2];
+    if (rtab) r = rtab[b];      // (the _rv call: the level of the view's IMAGE, wave-uniform)
+    resize_tile<T>(planes, out, (long)v0 + blockIdx.y, r, Ho, Wo, tiles_x, antialias, views.w[3 * blockIdx.y], views.w[3 * blockIdx.y + 1], nm, iv, b);
 }

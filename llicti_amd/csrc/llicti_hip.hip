@@ -781,6 +781,38 @@ struct PlanUse {
     ~PlanUse() { if (pd && hipEventRecord(pd->blk.done, s) == hipSuccess) { pd->blk.used = true; pd->blk.done_stream = s; } }
 };
 
+// The per-call tables of an _rv decode (host_plan.hpp: ReduceSchedule) in a block of the plans' pool: taken for the call, uploaded with ONE
+// asynchronous copy on the call's stream, handed back to the pool behind the call's last kernel (`done`, as PlanUse records it) -- so a steady
+// stream of calls with fresh reduces neither allocates nor synchronises, and nothing of it enters the plan cache or its LRU.
+struct RvCall {
+    llicti_ctx *c = nullptr;
+    hipStream_t s = nullptr;
+    ReduceSchedule q;
+    PlanBlock blk;
+    bool have = false;
+    template <class T> const T *dev(size_t off) const { return reinterpret_cast<const T *>(blk.dev + off); }
+    const int *d_r() const { return dev<int>(q.d_r); }
+    const RedGeo *d_red() const { return dev<RedGeo>(q.d_red); }
+    const PixGeo *d_pix() const { return dev<PixGeo>(q.d_pix); }
+    int upload()
+    {
+        if (int rc = acquire_block(c, q.d_total, &blk)) return rc;
+        have = true;
+        write_reduce_schedule(q, blk.host);
+        if (hipMemcpyAsync(blk.dev, blk.host, q.d_total, hipMemcpyHostToDevice, s) != hipSuccess) return fail(LLICTI_EHIP, "per-image reduce tables: upload failed");
+        return 0;
+    }
+    ~RvCall()
+    {
+        if (!have) return;
+        if (hipEventRecord(blk.done, s) == hipSuccess) { blk.used = true; blk.done_stream = s; }
+        c->pool.push_back(blk);
+    }
+    RvCall() = default;
+    RvCall(const RvCall &) = delete;
+    RvCall &operator=(const RvCall &) = delete;
+};
+
 // the pixel arguments of llicti_encode_images_px / llicti_decode_images_px as the caller gave them (host_plan.hpp: resolve_pixels)
 struct PixArgs { int fmt; const size_t *off, *pitch; };
 
@@ -997,20 +1029,21 @@ struct DecodeSink {
     uint8_t *target_ws = nullptr;
 };
 
-static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, int reduce)
+// rv: the _rv calls' per-image reduces (nullptr: `reduce` for every image)
+static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, int reduce, const int *rv = nullptr)
 {
     switch (k.kind) {
     case DecodeSink::Interleaved: {
         std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes
-        for (int b = 0; b < B; ++b) { Hw[b] = reduced_dim(Hs[b], reduce); Ww[b] = reduced_dim(Ws[b], reduce); }
+        for (int b = 0; b < B; ++b) { const int r = rv ? rv[b] : reduce; Hw[b] = reduced_dim(Hs[b], r); Ww[b] = reduced_dim(Ws[b], r); }
         return resolve_pixels("decode_images_px", B, Hw.data(), Ww.data(), k.px.fmt, k.px.off, k.px.pitch, k.pix);
     }
     case DecodeSink::Tensor:
-        return resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, k.tensor, k.wins, k.nm);
+        return resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, k.tensor, k.wins, k.nm, rv);
     case DecodeSink::Resized:
-        return resolve_resize("decode_images_tensor_resized", B, Hs, Ws, reduce, k.resize, k.wins, k.nm);
+        return resolve_resize("decode_images_tensor_resized", B, Hs, Ws, reduce, k.resize, k.wins, k.nm, rv);
     case DecodeSink::Views:
-        return resolve_views("decode_images_tensor_views", B, Hs, Ws, reduce, k.views, k.groups, k.nm);
+        return resolve_views("decode_images_tensor_views", B, Hs, Ws, reduce, k.views, k.groups, k.nm, rv);
     default:
         return 0;
     }
@@ -1035,8 +1068,10 @@ template <typename S> static S arg_slice(const std::vector<uint32_t> &words, int
 // The last kernel(s) of a decode, one block per kind.  Each latches the call's status words into the context's (the workspace is the caller's:
 // it may be gone or reused by the time the words are read); every side stream of the reference-format pipeline was joined back onto `s` at the
 // end of its band, so nothing is pending here.
-static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t *ws, hipStream_t s, int reduce)
+// rv (an _rv call): every image's own r comes from the call's table, and so do the reduced output table and the pixel windows.
+static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t *ws, hipStream_t s, int reduce, const RvCall *rv = nullptr)
 {
+    const int *rtab = rv ? rv->d_r() : nullptr;
     const Plan &p = pd->p;
     const int B = p.B;
     const int16_t *planes = (const int16_t *)(ws + p.off_planes);
@@ -1056,7 +1091,7 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
             with_tensor_type(t.dtype, [&](auto e) {
                 using T = decltype(e);
                 unlift_tensor_kernel<T><<<dim3(gx, nb), 256, 0, s>>>(planes, (T *)k.d_out, reduce, t.Ho, t.Wo, b0, tw, k.nm, status, kStatusHead, c->d_status,
-                                                                    c->d_img_status, d_img);
+                                                                    c->d_img_status, d_img, rtab);
             });
         }
         break;
@@ -1072,7 +1107,7 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
             with_tensor_type(t.dtype, [&](auto e) {
                 using T = decltype(e);
                 unlift_resize_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(planes, (T *)k.d_out, reduce, t.Ho, t.Wo, b0, tiles_x, t.antialias, bx, k.nm,
-                                                                                          status, kStatusHead, c->d_status, c->d_img_status, d_img);
+                                                                                          status, kStatusHead, c->d_status, c->d_img_status, d_img, rtab);
             });
         }
         break;
@@ -1089,7 +1124,7 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
                 with_tensor_type(g.dtype, [&](auto e) {
                     using T = decltype(e);
                     unlift_views_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(planes, (T *)g.d_out, reduce, g.Ho, g.Wo, v0, tiles_x, g.antialias, vs, k.nm,
-                                                                                             status, kStatusHead, c->d_status, c->d_img_status, d_img, latch_n);
+                                                                                             status, kStatusHead, c->d_status, c->d_img_status, d_img, latch_n, rtab);
                 });
                 latch_n = 0;
             }
@@ -1098,13 +1133,17 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
     }
     case DecodeSink::Interleaved: {
         // full size or reduced: one kernel, the window table behind the plan's others
-        const int gx = (int)std::min<long>((p.pix_units + 255) / 256, 1024);
-        unlift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, k.d_out, reduce, status, kStatusHead, c->d_status, c->d_img_status, d_img,
-                                                     reduce > 0 ? pd->dev<RedGeo>(p.d_red) : nullptr, pd->dev<PixGeo>(p.d_pix));
+        const int gx = (int)std::min<long>(((rv ? rv->q.pix_units : p.pix_units) + 255) / 256, 1024);
+        if (rv) unlift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, k.d_out, 0, status, kStatusHead, c->d_status, c->d_img_status, d_img, rv->d_red(), rv->d_pix(), rtab);
+        else unlift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, k.d_out, reduce, status, kStatusHead, c->d_status, c->d_img_status, d_img,
+                                                          reduce > 0 ? pd->dev<RedGeo>(p.d_red) : nullptr, pd->dev<PixGeo>(p.d_pix));
         break;
     }
     default:                                            // Planar (Transcode has returned above)
-        if (reduce > 0) {
+        if (rv) {
+            unlift_reduced_kernel<<<dim3((unsigned)((rv->q.max_rplane + 255) / 256), B), 256, 0, s>>>(planes, k.d_out, 0, status, kStatusHead, c->d_status,
+                                                                                                      c->d_img_status, d_img, rv->d_red(), rtab);
+        } else if (reduce > 0) {
             long max_rplane = 0;
             for (const RedGeo &rg : p.red) max_rplane = std::max(max_rplane, (long)rg.Hr * rg.Wr);
             unlift_reduced_kernel<<<dim3((unsigned)((max_rplane + 255) / 256), B), 256, 0, s>>>(planes, k.d_out, reduce, status, kStatusHead, c->d_status,
@@ -1118,8 +1157,11 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
     return 0;
 }
 
+// rv (an _rv call, rANS containers only; reduce = the smallest of its values): level lvl runs for the images with r_b <= lvl alone -- the band
+// CNN in its tile-list form over the call's list of that level (on an equal-size plan too: its Geom table is on the device), the stage kernels
+// and the tail with one workgroup per ACTIVE stream, which they find through the level's list.
 static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, uint8_t *ws, hipStream_t s, int reduce,
-                         const DecodeSink &sink)
+                         const DecodeSink &sink, const RvCall *rv = nullptr)
 {
     const Plan &p = pd->p;
     const int B = p.B, M = p.M, Q = p.Q;
@@ -1163,29 +1205,35 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
     // A reduced decode (reduce = r >= 1) stops after level r: every pixel whose row and column are multiples of 2^r is final then, and nothing that
     // ran reads a finer one.  The whole container has been unpacked above; the rANS bit region is read downwards from the stream's end and the coarse
     // stages come first, so stopping is sound -- but the tail coder (the last stage's) never runs, and with it the end-of-stream check.
+    if (rv && M == 0) return fail(LLICTI_EINVAL, "decode_images: per-image reduces need rANS containers");
     for (int lvl = p.nlev - 1; lvl >= reduce; --lvl) {
         const Geom &g = p.geo[(size_t)lvl * B];                         // image 0's (equal sizes: every image's)
-        const Geom *gv = p.uniform ? nullptr : d_geo + (size_t)lvl * B;
+        const Geom *gv = (p.uniform && !rv) ? nullptr : d_geo + (size_t)lvl * B;
+        const int NS = rv ? rv->q.s_n[lvl] : p.nstreams;               // (shadows the call's: the level's active streams)
+        const int *act = rv ? rv->dev<int>(rv->q.d_streams) + rv->q.s_off[lvl] : nullptr;
+        if (NS == 0 && M > 0) continue;                                 // (no image takes part in the level)
         for (int band = 0; band < 3; ++band) {
-            if (int rc = launch_band_params(c, fplanes, g, band, params, s, gv, d_tiles ? d_tiles + p.run[lvl * 3 + band].off : nullptr, &p.run[lvl * 3 + band])) return rc;
+            const TileRun *run = rv ? &rv->q.run[lvl * 3 + band] : &p.run[lvl * 3 + band];
+            const TileRef *tl = rv ? rv->dev<TileRef>(rv->q.d_tiles) + run->off : d_tiles ? d_tiles + run->off : nullptr;
+            if (int rc = launch_band_params(c, fplanes, g, band, params, s, gv, tl, run)) return rc;
             const StageGeom *sgv = d_sg + (size_t)(lvl * 3 + band) * B;
             if (M > 0) {
                 const int last = (lvl == 0 && band == 2) ? 1 : 0;      // the last stage's tail symbols are decoded by rans_tail_kernel
                 {
                 ProfSpan span(c, PROF_RANS_STAGE, s);
                 if (Q == 4) {
-                    rans_decode_stage_lane_kernel<4><<<NS, 256, 0, s>>>(params, sgv, d_sref, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status, c->d_phi_lut);
+                    rans_decode_stage_lane_kernel<4><<<NS, 256, 0, s>>>(params, sgv, d_sref, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status, c->d_phi_lut, act);
                 } else if (Q == 2) {
-                    rans_decode_stage_pair_kernel<<<NS, 64 * kRansWaves, 0, s>>>(params, sgv, d_sref, c->d_phi_lut, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status);
+                    rans_decode_stage_pair_kernel<<<NS, 64 * kRansWaves, 0, s>>>(params, sgv, d_sref, c->d_phi_lut, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status, act);
                 } else {
-                    rans_decode_stage_kernel<<<NS, 64 * kRansWaves, 0, s>>>(params, sgv, d_sref, c->d_phi_lut, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status);
+                    rans_decode_stage_kernel<<<NS, 64 * kRansWaves, 0, s>>>(params, sgv, d_sref, c->d_phi_lut, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status, act);
                 }
                 }
                 if (last) {
                     ProfSpan span(c, PROF_RANS_TAIL, s);
-                    if (Q == 4) rans_tail_kernel<4><<<NS, 64 * (1 + kTailAhead) * kTailChains<4>, 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off);
-                    else if (Q == 2) rans_tail_kernel<2><<<NS, 64 * (1 + kTailAhead), 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off);
-                    else rans_tail_kernel<1><<<NS, 64 * (1 + kTailAhead), 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off);
+                    if (Q == 4) rans_tail_kernel<4><<<NS, 64 * (1 + kTailAhead) * kTailChains<4>, 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off, act);
+                    else if (Q == 2) rans_tail_kernel<2><<<NS, 64 * (1 + kTailAhead), 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off, act);
+                    else rans_tail_kernel<1><<<NS, 64 * (1 + kTailAhead), 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off, act);
                 }
             }
             if (M == 0) {
@@ -1247,7 +1295,7 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t
             }
         }
     }
-    return launch_sink(c, pd, sink, ws, s, reduce);
+    return launch_sink(c, pd, sink, ws, s, reduce, rv);
 }
 
 // Room for the per-image status words of a call on B images in the context's own copy (llicti_image_status); none are valid until the call has run
@@ -1267,8 +1315,10 @@ static int reserve_img_status(llicti_ctx *c, int B)
 
 // rgb_off: the images' placement in a Planar sink's buffer (NULL: tight, and for every other kind)
 static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
-                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, const size_t *rgb_off, void *stream, int reduce, DecodeSink sink)
+                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, const size_t *rgb_off, void *stream, int reduce, DecodeSink sink,
+                        const int *reduces = nullptr)
 {
+    // reduces (the _rv calls, values that differ): B per-image values in the place of `reduce`; rgb_off then places the images at their own reduced sizes
     const bool own_out = sink.kind == DecodeSink::Views;      // (every group has its own output)
     if (!c || !d_in || !d_seg_len || !d_workspace || (!sink.d_out && !own_out)) return fail(LLICTI_EINVAL, "decode_images: null pointer");
     if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
@@ -1278,13 +1328,16 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
     if (int rc = resolve_modes("decode_images", modes, n_modes, B, &ME, Ms)) return rc;
     if (int rc = check_model(c->nlev, "decode_images", ME, Ms)) return rc;
     if (int rc = check_stream_bits("decode_images", c->nlev, B, Hs, Ws, ME, Ms)) return rc;
-    if (int rc = resolve_sink(sink, B, Hs, Ws, reduce)) return rc;
+    if (reduces) if (int rc = admit_reduces("decode_images", B, reduces, c->nlev, ME)) return rc;
+    if (int rc = resolve_sink(sink, B, Hs, Ws, reduce, reduces)) return rc;
     if (int rc = check_source_modes("decode_images", "container", ME)) return rc;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)stream;
     PlanDev *pd = nullptr;
-    if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, modes_ptr(Ms), s, &pd, reduce, sink.kind == DecodeSink::Interleaved ? &sink.pix : nullptr)) return rc;
+    // (an _rv call: the batch's full-size plan with tight placement, whatever the values and the sink -- outputs and windows are per-call tables)
+    if (reduces) { if (int rc = get_plan(c, B, Hs, Ws, nullptr, ME, modes_ptr(Ms), s, &pd)) return rc; }
+    else if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, modes_ptr(Ms), s, &pd, reduce, sink.kind == DecodeSink::Interleaved ? &sink.pix : nullptr)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     if (!p.uniform && p.M == 0) return fail(LLICTI_EINVAL, "decode_images: a batch of mixed sizes needs a rANS container (the reference-format container codes equal sizes per call)");
@@ -1293,8 +1346,16 @@ static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, co
         return fail(LLICTI_ENOSPACE, "decode_images: workspace %zu < %zu", workspace_bytes, p.total);
 
     if (int rc = reserve_img_status(c, B)) return rc;
+    RvCall rv;
+    if (reduces) {
+        rv.c = c; rv.s = s;
+        build_reduce_schedule(rv.q, p, reduces, sink.kind == DecodeSink::Planar ? rgb_off : nullptr, c->n_cu, c->cnn_tile_rows,
+                              sink.kind == DecodeSink::Interleaved ? &sink.pix : nullptr);
+        if (int rc = rv.upload()) return rc;
+        reduce = rv.q.rmin;
+    }
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, (uint8_t *)d_workspace, s, reduce, sink)) return rc;
+    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, (uint8_t *)d_workspace, s, reduce, sink, reduces ? &rv : nullptr)) return rc;
     c->img_status_n = B;
     return LLICTI_OK;
 }
@@ -1399,6 +1460,86 @@ extern "C" int llicti_decode_images_tensor_views(llicti_ctx *c, const uint8_t *d
     DecodeSink sink;
     sink.kind = DecodeSink::Views; sink.views = { groups, G, mean, std };
     return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
+}
+
+// ------------------------------------------------------------------------------------------------ per-image reduce
+// The five _rv calls: the scalar sibling with `int reduce` replaced by B host values.  All equal: the call IS the sibling (it delegates: same
+// launches, plan key and counters).  Otherwise decode_batch runs the per-call schedule (host_plan.hpp: ReduceSchedule).
+// -> 0 and *equal, or the refusal of a null array / a value out of range
+static int rv_head(llicti_ctx *c, const char *who, int B, const int *reduces, bool *equal)
+{
+    if (!c) return fail(LLICTI_EINVAL, "%s: null ctx", who);
+    if (B < 1) return fail(LLICTI_EINVAL, "%s: bad batch: B=%d", who, B);
+    if (int rc = admit_reduces(who, B, reduces, c->nlev, 1)) return rc;      // (the container kind is held against the modes in decode_batch)
+    *equal = reduces_equal(B, reduces);
+    return 0;
+}
+
+extern "C" int llicti_decode_images_reduced_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                               int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                               void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream)
+{
+    bool equal = false;
+    if (int rc = rv_head(c, "decode_images_reduced_rv", B, reduces, &equal)) return rc;
+    if (equal) return llicti_decode_images_reduced(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_rgb, rgb_off, stream);
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, rgb_off, stream, 0, planar_sink(d_rgb), reduces);
+}
+
+extern "C" int llicti_decode_images_px_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                          int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                          void *d_workspace, size_t workspace_bytes,
+                                          uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream)
+{
+    bool equal = false;
+    if (int rc = rv_head(c, "decode_images_px_rv", B, reduces, &equal)) return rc;
+    if (equal) return llicti_decode_images_px(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_pix, format, px_off, pitch, stream);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Interleaved; sink.d_out = d_pix; sink.px = { format, px_off, pitch };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
+}
+
+extern "C" int llicti_decode_images_tensor_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                              int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                              void *d_workspace, size_t workspace_bytes,
+                                              void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
+                                              const float *mean, const float *std, void *stream)
+{
+    bool equal = false;
+    if (int rc = rv_head(c, "decode_images_tensor_rv", B, reduces, &equal)) return rc;
+    if (equal) return llicti_decode_images_tensor(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_out, dtype, Ho, Wo,
+                                                  y0, x0, flip, mean, std, stream);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Tensor; sink.d_out = (uint8_t *)d_out; sink.tensor = { dtype, Ho, Wo, y0, x0, flip, mean, std };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
+}
+
+extern "C" int llicti_decode_images_tensor_resized_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                                      int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                                      void *d_workspace, size_t workspace_bytes,
+                                                      void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
+                                                      const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream)
+{
+    bool equal = false;
+    if (int rc = rv_head(c, "decode_images_tensor_resized_rv", B, reduces, &equal)) return rc;
+    if (equal) return llicti_decode_images_tensor_resized(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_out, dtype,
+                                                          Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias, stream);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Resized; sink.d_out = (uint8_t *)d_out; sink.resize = { dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
+}
+
+extern "C" int llicti_decode_images_tensor_views_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                                    int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                                    void *d_workspace, size_t workspace_bytes,
+                                                    const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream)
+{
+    bool equal = false;
+    if (int rc = rv_head(c, "decode_images_tensor_views_rv", B, reduces, &equal)) return rc;
+    if (equal) return llicti_decode_images_tensor_views(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, groups, G,
+                                                        mean, std, stream);
+    DecodeSink sink;
+    sink.kind = DecodeSink::Views; sink.views = { groups, G, mean, std };
+    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
 }
 
 extern "C" int llicti_encode_images_f32(llicti_ctx *c, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,

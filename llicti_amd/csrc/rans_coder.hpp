@@ -701,11 +701,12 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_kernel(cons
                                                                int rslot_cap, uint32_t *__restrict__ rstate, uint32_t *__restrict__ rpos,
                                                                const uint32_t *__restrict__ rtail,
                                                                int16_t *__restrict__ planes, float *__restrict__ fplanes,
-                                                               const int32_t *__restrict__ minmax, int last_stage, int32_t *status)
+                                                               const int32_t *__restrict__ minmax, int last_stage, int32_t *status,
+                                                               const int *__restrict__ act = nullptr)
 {
     __shared__ uint32_t sh_res[2][64][2];        // ping-pong by step parity: [0] = c_low, [1] = c_high
     __shared__ float2 sh_lut[kPhiLutN];          // the hint's normal CDF (term_lut)
-    const int sidx = blockIdx.x;
+    const int sidx = act ? act[blockIdx.x] : (int)blockIdx.x;      // (act: a per-image-reduce call's list of the level's streams, llicti_decode_images_*_rv)
     const StreamRef sr_ = sref[sidx];               // the stream's image, its index among the image's streams, the image's stream count (images of a call may differ)
     const int b = sr_.b, m = sr_.m, M = sr_.M;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -933,12 +934,13 @@ __global__ __launch_bounds__(64 * kRansWaves) void rans_decode_stage_pair_kernel
                                                                int rslot_cap, uint32_t *__restrict__ rstate, uint32_t *__restrict__ rpos,
                                                                const uint32_t *__restrict__ rtail,
                                                                int16_t *__restrict__ planes, float *__restrict__ fplanes,
-                                                               const int32_t *__restrict__ minmax, int last_stage, int32_t *status)
+                                                               const int32_t *__restrict__ minmax, int last_stage, int32_t *status,
+                                                               const int *__restrict__ act = nullptr)
 {
     constexpr int Q = 2, L = 64 * Q;
     __shared__ uint32_t sh_res[2][L][2];         // ping-pong by step parity: [0] = c_low, [1] = c_high
     __shared__ float2 sh_lut[kPhiLutN];          // the hint's normal CDF (term_lut)
-    const int sidx = blockIdx.x;
+    const int sidx = act ? act[blockIdx.x] : (int)blockIdx.x;      // (act: a per-image-reduce call's list of the level's streams, llicti_decode_images_*_rv)
     const StreamRef sr_ = sref[sidx];               // the stream's image, its index among the image's streams, the image's stream count (images of a call may differ)
     const int b = sr_.b, m = sr_.m, M = sr_.M;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1153,7 +1155,7 @@ __global__ __launch_bounds__(64 * Q) void rans_decode_stage_lane_kernel(const fl
                                                                const uint32_t *__restrict__ rtail,
                                                                int16_t *__restrict__ planes, float *__restrict__ fplanes,
                                                                const int32_t *__restrict__ minmax, int last_stage, int32_t *status,
-                                                               const float2 *__restrict__ phi_lut)
+                                                               const float2 *__restrict__ phi_lut, const int *__restrict__ act = nullptr)
 {
     constexpr int L = 64 * Q;
     constexpr int kRing = 512, kRefill = 128;    // dwords; a step consumes at most 16 L bits = L / 2 dwords
@@ -1169,7 +1171,7 @@ __global__ __launch_bounds__(64 * Q) void rans_decode_stage_lane_kernel(const fl
     constexpr int kLutN = kPhiLutN;
     constexpr float kLutZ = (float)kPhiLutZ, kLutS = kLutN / (2.0f * kLutZ);
     __shared__ float2 sh_lut[kLutN];
-    const int sidx = blockIdx.x;
+    const int sidx = act ? act[blockIdx.x] : (int)blockIdx.x;      // (act: a per-image-reduce call's list of the level's streams, llicti_decode_images_*_rv)
     const StreamRef sr_ = sref[sidx];               // the stream's image, its index among the image's streams, the image's stream count (images of a call may differ)
     const int b = sr_.b, m = sr_.m, M = sr_.M;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;      // tid = lane of the stream
@@ -1372,7 +1374,8 @@ __global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_t
                                                        const uint32_t *__restrict__ rtail,
                                                        int16_t *__restrict__ planes, float *__restrict__ fplanes,
                                                        const int32_t *__restrict__ minmax, int32_t *status,
-                                                       const uint8_t *__restrict__ slots, const long *__restrict__ rslot_off)
+                                                       const uint8_t *__restrict__ slots, const long *__restrict__ rslot_off,
+                                                       const int *__restrict__ act = nullptr)
 {
     using GEO = RansGeo<Q>;
     constexpr int L = 64 * Q, NCH = kTailChains<Q>;
@@ -1384,7 +1387,7 @@ __global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_t
     __shared__ long sh_off[2][NSL];                     // the symbol's pixel
     __shared__ int sh_spec[2][NSL][16];                 // [0..11] the exact entries of the speculated window, [12] its first index (-1: none)
     __shared__ int sh_cur[2];                           // xwide: where the two chains stopped reading
-    const int sidx = blockIdx.x;
+    const int sidx = act ? act[blockIdx.x] : (int)blockIdx.x;      // (act: a per-image-reduce call's list of the level's streams, llicti_decode_images_*_rv)
     const StreamRef sr_ = sref[sidx];               // the stream's image, its index among the image's streams, the image's stream count (images of a call may differ)
     const int b = sr_.b, m = sr_.m, M = sr_.M;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (scalar: roles, chains and symbol counts are wave-uniform, their branches scalar)

@@ -374,7 +374,8 @@ class LLICTI(nn.Module):
     @torch.no_grad()
     def decompres_batch(self, lists, devc=None, reduce=0):
         """bytestream_lists of B images -> float32 [B,3,H,W] (equal sizes), or -- images of different sizes, rANS containers -- a LIST of B tensors
-        [1,3,H_b,W_b], each what decompres() returns for that image.  reduce: as for decompres(), one value for the call."""
+        [1,3,H_b,W_b], each what decompres() returns for that image.  reduce: as for decompres() -- one value for the call, or one per image
+        (rANS containers): then always the list, image b at its own reduced size."""
         res = self.decode_batch_async(lists, devc, reduce=reduce)
         self.codec().check()
         if isinstance(res, tuple):
@@ -503,7 +504,10 @@ class LLICTI(nn.Module):
         """bytestream_lists of B images -> uint8 [B,3,H,W] on the device, enqueued (upload from a pinned buffer + decode); device-side
         failures are reported by codec().check() / image_status().  The images of a call share a container kind; in a rANS container their
         SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each.
-        reduce = r: every image at 1 / 2^r (decompres()); H, W, Hs, Ws of the result are the REDUCED sizes.  (The pinned staging buffers hold the
+        reduce = r: every image at 1 / 2^r (decompres()); H, W, Hs, Ws of the result are the REDUCED sizes.  reduce = [r_0, ...], one per image
+        (rANS containers): image b stops at its own level -- exactly what the call at r_b gives for it -- and the finer levels run for the images
+        that need them alone; the result is the flat form, Hs, Ws each image's own reduced size; with tensor= the origins, boxes and views are
+        in the coordinates of each image's own decimated grid (codec.resized_crop_plan / multi_crop_plan with per_image=True).  (The pinned staging buffers hold the
         call's INPUT -- containers and segment lengths, sized by the full image -- so a reduced and a full decode share them safely.)
         pixels = "rgb" | "bgr" | "rgba" | "bgra": the result is a LIST of B uint8 device tensors [H_b, W_b, 3 | 4], interleaved (alpha 255), written
         in that layout by the decode's last kernel (HipCodec.decode_px) -- views of one flat buffer, the images back to back; with flat=True
@@ -526,6 +530,13 @@ class LLICTI(nn.Module):
             codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_batch(lists, devc)
         else:
             codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
+        per_image = not isinstance(reduce, (int, np.integer))
+        if per_image:
+            reduce = [int(r) for r in reduce]
+            if len(reduce) != len(Hs):
+                raise ValueError(f"reduce: {len(reduce)} values for a batch of {len(Hs)} images (one int, or one per image)")
+        # the images' decoded sizes (a value the library refuses: it says so in the decode call)
+        red_sizes = lambda: (list(v) for v in zip(*(reduced_dims(h, w, r) for h, w, r in zip(Hs, Ws, reduce if per_image else [reduce] * len(Hs)))))
         if tensor is not None and "views" in tensor:
             if any(k in tensor for k in ("boxes", "origin", "size")):
                 raise ValueError("tensor=dict(views=...): every group has its own size and boxes; boxes=, origin= and size= do not go beside it")
@@ -538,16 +549,16 @@ class LLICTI(nn.Module):
         if pixels is not None:
             bpp = pixel_bytes(pixels)
             out = codec.decode_px(cont_d, seg_d, Hs, Ws, mode, pixels, reduce=reduce)
-            if reduce:
-                Hs, Ws = (list(v) for v in zip(*(reduced_dims(h, w, reduce) for h, w in zip(Hs, Ws))))
+            if per_image or reduce:
+                Hs, Ws = red_sizes()
             if flat:
                 return out, Hs, Ws
             offs = np.concatenate(([0], np.cumsum([h * w * bpp for h, w in zip(Hs, Ws)])))
             return [out[int(o):int(o) + h * w * bpp].view(h, w, bpp) for o, h, w in zip(offs, Hs, Ws)]
-        if mixed or flat:
+        if mixed or flat or per_image:
             out = codec.decode_v(cont_d, seg_d, Hs, Ws, mode, reduce=reduce)
-            if reduce:
-                Hs, Ws = (list(v) for v in zip(*(reduced_dims(h, w, reduce) for h, w in zip(Hs, Ws))))
+            if per_image or reduce:
+                Hs, Ws = red_sizes()
             return out, Hs, Ws
         return codec.decode(cont_d, seg_d, Hs[0], Ws[0], mode=mode, reduce=reduce)
 
