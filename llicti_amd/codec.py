@@ -392,6 +392,28 @@ def _reduced_sizes(Hs, Ws, r, rv):
     return [reduced_dims(h, w, k) if 0 <= k <= 5 else (int(h), int(w)) for h, w, k in zip(Hs, Ws, rs)]
 
 
+def _flip_arg(flip, n):
+    fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+    assert fl is None or fl.shape == (n,)
+    return fl
+
+
+def _norm_args(mean, std):
+    mn = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
+    sd = None if std is None else np.ascontiguousarray(std, dtype=np.float32)
+    assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
+    return mn, sd
+
+
+def _box_columns(boxes, n):
+    """n boxes (y0, x0, hs, ws), or None -> the four int32 columns the library takes (None each)"""
+    if boxes is None:
+        return [None] * 4
+    bx = np.ascontiguousarray(boxes, dtype=np.int32)
+    assert bx.shape == (n, 4)
+    return [np.ascontiguousarray(bx[:, k]) for k in range(4)]
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -670,6 +692,34 @@ class HipCodec:
                                                       _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
         return out, seg_len
 
+    def _decode_prologue(self, name, containers, seg_len, Hs, Ws, mode, reduce):
+        """The front of the decode calls that take `reduce`: sizes as int32 arrays, the workspace, the modes array and the reduce argument
+        -> (B, every image's decoded size, call), where call(*tail) runs llicti_<name> (reduce an int) or llicti_<name>_rv (one per image) on
+        the leading arguments, `tail` and this device's stream."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.shape[0] == B
+        ws = self.workspace_v(Hs, Ws, mode)          # (the full decode's: a reduced call uses the same layout)
+        one, per = self._modes_arg(mode, B)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        r, rv = _reduce_arg(reduce, B)
+        fn = getattr(self.L, "llicti_" + name if rv is None else "llicti_" + name + "_rv")
+
+        def call(*tail):
+            _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws), _ptr(modes), len(modes),
+                          r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), *tail, _stream_ptr(self.device)))
+        return B, _reduced_sizes(Hs, Ws, r, rv), call      # (a bad r: the library says so)
+
+    def _tensor_out(self, out, n, size, dtype):
+        """the [n, 3, Ho, Wo] output of a tensor decode, the caller's (checked) or a new one -> (out, the library's dtype code, Ho, Wo)"""
+        Ho, Wo = int(size[0]), int(size[1])
+        dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
+        tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
+        if out is None:
+            out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= n * 3 * Ho * Wo
+        return out, int(dt), Ho, Wo
+
     def decode_reduced(self, containers, seg_len, Hs, Ws, mode, reduce, out=None, rgb_off=None):
         """llicti_decode_images_reduced: device containers of B images of FULL sizes Hs[b] x Ws[b] (mode: one, or one per image) -> flat uint8
         device tensor holding image b's [3][Hr][Wr] block (reduced_dims) at byte rgb_off[b], or back to back (rgb_off None), async.  Only the
@@ -677,12 +727,7 @@ class HipCodec:
         reduce >= 1: check() / image_status() report what the launched kernels flag.  reduce = 0 is decode_v.
         reduce may be a sequence of B ints (llicti_decode_images_reduced_rv): image b stops at its own level reduce[b] and is exactly what the
         call at that one value gives for it -- size, bytes, status word; level l runs for the images with reduce[b] <= l alone."""
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
-        assert containers.shape[0] == B
-        ws = self.workspace_v(Hs, Ws, mode)          # (the full decode's: a reduced call uses the same layout)
-        r, rv = _reduce_arg(reduce, B)
-        dims = _reduced_sizes(Hs, Ws, r, rv)      # (a bad r: the library says so)
+        B, dims, call = self._decode_prologue("decode_images_reduced", containers, seg_len, Hs, Ws, mode, reduce)
         sizes = [3 * h * w for h, w in dims]
         if rgb_off is None:
             offs, total = None, sum(sizes)
@@ -693,12 +738,7 @@ class HipCodec:
         if out is None:
             out = torch.empty((total,), dtype=torch.uint8, device=self.device)
         assert out.numel() >= total
-        one, per = self._modes_arg(mode, B)
-        modes = np.array([one], dtype=np.int32) if per is None else per
-        fn = self.L.llicti_decode_images_reduced if rv is None else self.L.llicti_decode_images_reduced_rv
-        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), _ptr(offs),
-                      _stream_ptr(self.device)))
+        call(_ptr(out), _ptr(offs))
         return out
 
     # ---- interleaved, pitched pixels (llicti_encode_images_px / llicti_decode_images_px): the layout image sources deliver
@@ -742,22 +782,12 @@ class HipCodec:
         reduced_dims(Hs[b], Ws[b], reduce)) at byte px_off[b] with rows pitch[b] bytes apart (None: back to back / tight).  Only the bytes of
         the windows' rows are written -- `out` may be a canvas whose other bytes must stay; alpha is written as 255.  reduce as decode_reduced
         (an int, or one per image: image b's window then has reduced_dims(Hs[b], Ws[b], reduce[b])).  Async."""
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
-        assert containers.shape[0] == B
-        r, rv = _reduce_arg(reduce, B)
-        dims = _reduced_sizes(Hs, Ws, r, rv)      # (a bad r: the library says so)
+        B, dims, call = self._decode_prologue("decode_images_px", containers, seg_len, Hs, Ws, mode, reduce)
         fmt, offs, pt, total = self._px_layout(fmt, dims, px_off, pitch)
-        ws = self.workspace_v(Hs, Ws, mode)
         if out is None:
             out = torch.empty((total,), dtype=torch.uint8, device=self.device)
         assert out.dtype == torch.uint8 and out.dim() == 1 and out.numel() >= total
-        one, per = self._modes_arg(mode, B)
-        modes = np.array([one], dtype=np.int32) if per is None else per
-        fn = self.L.llicti_decode_images_px if rv is None else self.L.llicti_decode_images_px_rv
-        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), fmt, _ptr(offs), _ptr(pt),
-                      _stream_ptr(self.device)))
+        call(_ptr(out), fmt, _ptr(offs), _ptr(pt))
         return out
 
     def decode_v(self, containers, seg_len, Hs, Ws, mode, out=None, reduce=0):
@@ -792,32 +822,15 @@ class HipCodec:
         round-to-nearest-even.  Origins and flips are per-call data: calls that differ only in them share one cached plan.  `out`: a contiguous
         [B, 3, Ho, Wo] tensor of that dtype to write into (nothing outside it is touched).  reduce as decode_reduced (an int, or one per image:
         image b's origin is then in the coordinates of its own decimated grid)."""
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
-        assert containers.shape[0] == B
-        Ho, Wo = int(size[0]), int(size[1])
-        dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
-        tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
-        ws = self.workspace_v(Hs, Ws, mode)
-        if out is None:
-            out = torch.empty((B, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= B * 3 * Ho * Wo
+        B, _, call = self._decode_prologue("decode_images_tensor", containers, seg_len, Hs, Ws, mode, reduce)
+        out, dt, Ho, Wo = self._tensor_out(out, B, size, dtype)
         y0 = x0 = None
         if origin is not None:
             y0, x0 = (np.ascontiguousarray(v, dtype=np.int32) for v in origin)
             assert y0.shape == (B,) and x0.shape == (B,)
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
-        assert fl is None or fl.shape == (B,)
-        mn = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
-        sd = None if std is None else np.ascontiguousarray(std, dtype=np.float32)
-        assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
-        one, per = self._modes_arg(mode, B)
-        modes = np.array([one], dtype=np.int32) if per is None else per
-        r, rv = _reduce_arg(reduce, B)
-        fn = self.L.llicti_decode_images_tensor if rv is None else self.L.llicti_decode_images_tensor_rv
-        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
-                      _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
+        fl = _flip_arg(flip, B)
+        mn, sd = _norm_args(mean, std)
+        call(_ptr(out), dt, Ho, Wo, _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd))
         return out
 
     def decode_tensor_resized(self, containers, seg_len, Hs, Ws, mode, size, boxes, dtype=torch.float32, flip=None, mean=None, std=None, antialias=True,
@@ -831,35 +844,13 @@ class HipCodec:
         calls that differ only in them share decode_reduced's cached plan and neither allocate nor synchronise.  reduce: an int, or one per image
         (resized_crop_plan(..., per_image=True)): box b is then in the coordinates of image b's own decimated grid, and a tight crop no longer
         sends its neighbours through the finest levels."""
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
-        assert containers.shape[0] == B
-        Ho, Wo = int(size[0]), int(size[1])
-        dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
-        tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
-        ws = self.workspace_v(Hs, Ws, mode)
-        if out is None:
-            out = torch.empty((B, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= B * 3 * Ho * Wo
-        y0 = x0 = bh = bw = None
-        if boxes is not None:
-            bx = np.ascontiguousarray(boxes, dtype=np.int32)
-            assert bx.shape == (B, 4)
-            y0, x0, bh, bw = (np.ascontiguousarray(bx[:, k]) for k in range(4))
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
-        assert fl is None or fl.shape == (B,)
-        mn = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
-        sd = None if std is None else np.ascontiguousarray(std, dtype=np.float32)
-        assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
-        one, per = self._modes_arg(mode, B)
-        modes = np.array([one], dtype=np.int32) if per is None else per
+        B, _, call = self._decode_prologue("decode_images_tensor_resized", containers, seg_len, Hs, Ws, mode, reduce)
+        out, dt, Ho, Wo = self._tensor_out(out, B, size, dtype)
+        cols = _box_columns(boxes, B)
+        fl = _flip_arg(flip, B)
+        mn, sd = _norm_args(mean, std)
         aa = int(antialias) if isinstance(antialias, (bool, int, np.integer)) else -1
-        r, rv = _reduce_arg(reduce, B)
-        fn = self.L.llicti_decode_images_tensor_resized if rv is None else self.L.llicti_decode_images_tensor_resized_rv
-        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), _ptr(out), int(dt), Ho, Wo,
-                      _ptr(y0), _ptr(x0), _ptr(bh), _ptr(bw), _ptr(fl), _ptr(mn), _ptr(sd), aa,
-                      _stream_ptr(self.device)))
+        call(_ptr(out), dt, Ho, Wo, *(_ptr(c) for c in cols), _ptr(fl), _ptr(mn), _ptr(sd), aa)
         return out
 
     def decode_tensor_views(self, containers, seg_len, Hs, Ws, mode, groups, mean=None, std=None, reduce=0):
@@ -872,11 +863,8 @@ class HipCodec:
         them share decode_reduced's cached plan and neither allocate nor synchronise.  multi_crop_plan picks reduce: an int, or one per image
         (per_image=True) -- a view's box is then in the coordinates of ITS image's decimated grid, and an image no view names may be passed at
         the model's level count."""
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
-        assert containers.shape[0] == B
+        B, _, call = self._decode_prologue("decode_images_tensor_views", containers, seg_len, Hs, Ws, mode, reduce)
         groups = list(groups)
-        ws = self.workspace_v(Hs, Ws, mode)
         arr = (_lib.ViewGroup * max(len(groups), 1))()
         outs, keep = [], []
         for g, spec in enumerate(groups):
@@ -886,38 +874,21 @@ class HipCodec:
             dtype, antialias = spec.pop("dtype", torch.float32), spec.pop("antialias", True)
             if spec:
                 raise TypeError(f"group {g}: unknown keys {sorted(spec)}")
-            dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
-            tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
             img = None if image is None else np.ascontiguousarray(image, dtype=np.int32)
             assert img is None or img.ndim == 1
             n = B if img is None else len(img)
-            if out is None:
-                out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
-            assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= n * 3 * Ho * Wo
-            cols = [None] * 4
-            if boxes is not None:
-                bx = np.ascontiguousarray(boxes, dtype=np.int32)
-                assert bx.shape == (n, 4)
-                cols = [np.ascontiguousarray(bx[:, k]) for k in range(4)]
-            fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
-            assert fl is None or fl.shape == (n,)
+            out, dt, Ho, Wo = self._tensor_out(out, n, (Ho, Wo), dtype)
+            cols = _box_columns(boxes, n)
+            fl = _flip_arg(flip, n)
             aa = int(antialias) if isinstance(antialias, (bool, int, np.integer)) else -1
             keep.append((img, cols, fl))                  # (the host arrays live until the call returns)
             vg = arr[g]
-            vg.d_out, vg.dtype, vg.Ho, vg.Wo, vg.antialias, vg.n = out.data_ptr(), int(dt), Ho, Wo, aa, n
+            vg.d_out, vg.dtype, vg.Ho, vg.Wo, vg.antialias, vg.n = out.data_ptr(), dt, Ho, Wo, aa, n
             vg.image, vg.flip = _ptr(img), _ptr(fl)
             vg.y0, vg.x0, vg.hs, vg.ws = (_ptr(c) for c in cols)
             outs.append(out)
-        mn = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
-        sd = None if std is None else np.ascontiguousarray(std, dtype=np.float32)
-        assert (mn is None or mn.shape == (3,)) and (sd is None or sd.shape == (3,))
-        one, per = self._modes_arg(mode, B)
-        modes = np.array([one], dtype=np.int32) if per is None else per
-        r, rv = _reduce_arg(reduce, B)
-        fn = self.L.llicti_decode_images_tensor_views if rv is None else self.L.llicti_decode_images_tensor_views_rv
-        _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
-                      _ptr(modes), len(modes), r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), arr, len(groups),
-                      _ptr(mn), _ptr(sd), _stream_ptr(self.device)))
+        mn, sd = _norm_args(mean, std)
+        call(arr, len(groups), _ptr(mn), _ptr(sd))
         return outs
 
     def encode_f32(self, x_flat, Hs, Ws, mode, x_off=None, out=None, seg_len=None):

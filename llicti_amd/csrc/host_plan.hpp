@@ -49,6 +49,7 @@ struct Plan {
     // reduced-resolution decodes (plan_add_reduced): the levels the call skips and where every image's reduced output goes
     int reduce = 0;
     std::vector<RedGeo> red;            // [B], empty for reduce = 0
+    long max_rplane = 0;                // the largest Hr * Wr: sizes the grid of unlift_reduced_kernel
     size_t d_red = 0;
     // interleaved pixel buffers (plan_add_pixels): every image's window in the caller's buffer
     std::vector<PixGeo> pix;            // [B], empty for the planar calls
@@ -151,6 +152,36 @@ static TileForm choose_tile_form(int n_cu, int tile_rows, int band, COUNT &&coun
         }
     }
     return f;
+}
+
+// The band CNN's tile lists of levels lvl_first, lvl_first +- 1, ... up to but not including lvl_end, in that order, behind what `tiles` holds: one
+// list per (level, band) over the images with active(b, lvl) -- image-major, rows, columns: the order the division form walks -- and its TileRun in
+// run[lvl * 3 + band] (form chosen over those images; n_tiles clamped to 2^31 - 1).  No active image at a level: no list, its runs stay as they are.
+// geo: a plan's [level][B] table.
+template <class ACTIVE>
+static void build_tile_lists(const std::vector<Geom> &geo, int B, int lvl_first, int lvl_end, ACTIVE &&active, int n_cu, int tile_rows,
+                             std::vector<TileRef> &tiles, TileRun *run)
+{
+    for (int lvl = lvl_first; lvl != lvl_end; lvl += lvl_end > lvl_first ? 1 : -1) {
+        const Geom *gl = &geo[(size_t)lvl * B];
+        auto count = [&](int th) -> long {
+            long t = 0;
+            for (int b = 0; b < B; ++b) if (active(b, lvl)) t += (long)((gl[b].w + kTileW - 1) / kTileW) * ((gl[b].h + th - 1) / th);
+            return t;
+        };
+        if (count(kTileHMax) == 0) continue;
+        for (int band = 0; band < 3; ++band) {
+            const TileForm f = choose_tile_form(n_cu, tile_rows, band, count);
+            TileRun &r = run[lvl * 3 + band];
+            r.off = tiles.size(); r.n_tiles = (int)std::min<long>(f.n_tiles, 0x7FFFFFFFL); r.TH = f.TH; r.gx = f.gx;
+            for (int b = 0; b < B; ++b) {
+                if (!active(b, lvl)) continue;
+                const int tx_n = (gl[b].w + kTileW - 1) / kTileW, ty_n = (gl[b].h + f.TH - 1) / f.TH;
+                for (int ty = 0; ty < ty_n; ++ty)
+                    for (int tx = 0; tx < tx_n; ++tx) tiles.push_back(TileRef{ b, (ty << 16) | tx });
+            }
+        }
+    }
 }
 
 static int rans_byte0(int M, int Q, int nlev = LLICTI_NLEVELS);
@@ -369,26 +400,7 @@ static void build_plan(Plan &p, const PlanSpec &sp)
     // mixed sizes: the band CNN's tile lists (image-major, rows, columns: the order the division form walks)
     p.tiles.clear();
     for (int k = 0; k < LLICTI_NLEVELS * 3; ++k) p.run[k] = TileRun{};
-    if (!p.uniform) {
-        for (int lvl = 0; lvl < nlev; ++lvl) {
-            const Geom *gl = &p.geo[(size_t)lvl * B];
-            auto count = [&](int th) -> long {
-                long t = 0;
-                for (int b = 0; b < B; ++b) t += (long)((gl[b].w + kTileW - 1) / kTileW) * ((gl[b].h + th - 1) / th);
-                return t;
-            };
-            for (int band = 0; band < 3; ++band) {
-                const TileForm f = choose_tile_form(n_cu, tile_rows, band, count);
-                TileRun &r = p.run[lvl * 3 + band];
-                r.off = p.tiles.size(); r.n_tiles = (int)std::min<long>(f.n_tiles, 0x7FFFFFFFL); r.TH = f.TH; r.gx = f.gx;
-                for (int b = 0; b < B; ++b) {
-                    const int tx_n = (gl[b].w + kTileW - 1) / kTileW, ty_n = (gl[b].h + f.TH - 1) / f.TH;
-                    for (int ty = 0; ty < ty_n; ++ty)
-                        for (int tx = 0; tx < tx_n; ++tx) p.tiles.push_back(TileRef{ b, (ty << 16) | tx });
-                }
-            }
-        }
-    }
+    if (!p.uniform) build_tile_lists(p.geo, B, 0, nlev, [](int, int) { return true; }, n_cu, tile_rows, p.tiles, p.run);
     // the device block: every table at a 256-byte boundary
     size_t d = 0;
     auto dtake = [&](size_t bytes) { size_t r = d; d = align_up(d + bytes, 256); return r; };
@@ -404,36 +416,66 @@ static void build_plan(Plan &p, const PlanSpec &sp)
     p.d_total = d;
 }
 
-// The extra words a reduced-resolution decode adds to the cache key of its batch's plan: a marker that no full-size key holds at that place
-// (-reduce: sizes are >= 32), then the byte offset of every image's reduced output (out_off, or nullptr = tightly packed in call order).
-// A full-size key has 3 + 4 B words, a reduced one 4 + 5 B: the two never compare equal, so a reduced call never finds, changes or
-// replaces the full-size plan of the same batch.
-static void reduced_key_tail(std::vector<long> &key, int B, const int *Hs, const int *Ws, int reduce, const size_t *out_off)
+// The reduce of a decode: one level r for every image, or (the _rv calls) image b's own rv[b].
+struct Reduces {
+    int r = 0;
+    const int *rv = nullptr;            // B values; r is not read then
+    Reduces(int r_ = 0) : r(r_) {}
+    static Reduces each(const int *rv) { Reduces d; d.rv = rv; return d; }
+    bool per_image() const { return rv != nullptr; }
+    int of(int b) const { return rv ? rv[b] : r; }
+    int min(int B) const { int m = of(0); for (int b = 1; b < B; ++b) m = std::min(m, of(b)); return m; }
+};
+// Where a reduced decode's output goes: every image's size at its reduce and its byte offset (out_off, or nullptr = tightly packed in call order,
+// each image at its own reduced size), the largest Hr * Wr (the grid of unlift_reduced_kernel) and the largest image in 4-pixel row pieces,
+// Hr * ceil(Wr / 4) (the grid of unlift_px_kernel).  At reduce 0 the sizes are the full ones.
+struct ReducedOut { std::vector<RedGeo> red; long max_rplane = 0, pix_units = 0; };
+static ReducedOut reduced_out(int B, const int *Hs, const int *Ws, const Reduces &rd, const size_t *out_off)
 {
-    key.push_back(-(long)reduce);
+    ReducedOut o;
+    o.red.assign(B, RedGeo{});
     long pos = 0;
     for (int b = 0; b < B; ++b) {
-        key.push_back(out_off ? (long)out_off[b] : pos);
-        pos += 3L * reduced_dim(Hs[b], reduce) * reduced_dim(Ws[b], reduce);
+        RedGeo &rg = o.red[b];
+        rg.Hr = reduced_dim(Hs[b], rd.of(b)); rg.Wr = reduced_dim(Ws[b], rd.of(b));
+        rg.off = out_off ? (long)out_off[b] : pos;
+        pos += 3L * rg.Hr * rg.Wr;
+        o.max_rplane = std::max(o.max_rplane, (long)rg.Hr * rg.Wr);
+        o.pix_units = std::max(o.pix_units, (long)rg.Hr * ((rg.Wr + 3) / 4));
     }
+    return o;
+}
+static ReducedOut reduced_out(const std::vector<ImgGeo> &img, const Reduces &rd, const size_t *out_off)      // (a plan's image table)
+{
+    std::vector<int> Hs, Ws;
+    for (const ImgGeo &ig : img) { Hs.push_back(ig.H); Ws.push_back(ig.W); }
+    return reduced_out((int)img.size(), Hs.data(), Ws.data(), rd, out_off);
+}
+
+// The extra words a reduced-resolution decode adds to the cache key of its batch's plan: a marker that no full-size key holds at that place
+// (-reduce: sizes are >= 32), then the byte offset of every image's reduced output (reduced_out's).
+// A full-size key has 3 + 4 B words, a reduced one 4 + 5 B: the two never compare equal, so a reduced call never finds, changes or
+// replaces the full-size plan of the same batch.
+static void reduced_key_tail(std::vector<long> &key, int reduce, const std::vector<RedGeo> &red)
+{
+    key.push_back(-(long)reduce);
+    for (const RedGeo &rg : red) key.push_back(rg.off);
+}
+static void reduced_key_tail(std::vector<long> &key, int B, const int *Hs, const int *Ws, int reduce, const size_t *out_off)
+{
+    reduced_key_tail(key, reduce, reduced_out(B, Hs, Ws, reduce, out_off).red);
 }
 // Turns the plan build_plan made for a batch -- with FULL-size tight RGB placement: `uniform`, `vec_ok`, ImgGeo::rgb_off and rgb_bytes keep
 // their full-size meaning and nothing of the decode's stages changes -- into the plan of a decode that stops after level `reduce`
 // (1 .. nlev): the output table of unlift_reduced_kernel goes behind the other tables of the device block, the key gets its tail.
 static void plan_add_reduced(Plan &p, int reduce, const size_t *out_off)
 {
+    ReducedOut o = reduced_out(p.img, reduce, out_off);
     p.reduce = reduce;
-    p.red.assign(p.B, RedGeo{});
-    std::vector<int> Hs(p.B), Ws(p.B);
-    long pos = 0;
-    for (int b = 0; b < p.B; ++b) {
-        RedGeo &rg = p.red[b];
-        Hs[b] = p.img[b].H; Ws[b] = p.img[b].W;
-        rg.Hr = reduced_dim(Hs[b], reduce); rg.Wr = reduced_dim(Ws[b], reduce);
-        rg.off = out_off ? (long)out_off[b] : pos;
-        pos += 3L * rg.Hr * rg.Wr;
-    }
-    reduced_key_tail(p.key, p.B, Hs.data(), Ws.data(), reduce, out_off);
+    p.red.swap(o.red);
+    p.max_rplane = o.max_rplane;
+    p.pix_units = o.pix_units;          // (of a pixel call: plan_add_pixels)
+    reduced_key_tail(p.key, reduce, p.red);
     p.d_red = p.d_total;
     p.d_total = align_up(p.d_total + p.red.size() * sizeof(RedGeo), 256);
 }
@@ -483,39 +525,40 @@ static void pixel_key_tail(std::vector<long> &key, const std::vector<PixGeo> &pi
 static void plan_add_pixels(Plan &p, const std::vector<PixGeo> &pix)
 {
     p.pix = pix;
-    p.pix_units = 0;
-    for (int b = 0; b < p.B; ++b) {
-        const long Hw = p.reduce ? p.red[b].Hr : p.img[b].H, Ww = p.reduce ? p.red[b].Wr : p.img[b].W;
-        p.pix_units = std::max(p.pix_units, Hw * ((Ww + 3) / 4));
-    }
+    if (!p.reduce) p.pix_units = reduced_out(p.img, 0, nullptr).pix_units;      // (a reduced plan has its own from plan_add_reduced)
     pixel_key_tail(p.key, pix);
     p.d_pix = p.d_total;
     p.d_total = align_up(p.d_total + p.pix.size() * sizeof(PixGeo), 256);
 }
 
-// Float tensor output (llicti_decode_images_tensor): the output description as the caller gave it ...
-struct TensorArgs { int dtype, Ho, Wo; const int *y0, *x0; const uint8_t *flip; const float *mean, *std; };
-// ... and validated against the call's images (FULL sizes Hs, Ws, decoded at `reduce`): every image's packed window word (tensor_win_pack) and
-// the normalisation constants.  These are the call's kernel arguments -- nothing of them enters the plan or its key.
-// rv != nullptr (the _rv calls): image b is held against its own reduce rv[b], and `reduce` is not read.
-static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, int reduce, const TensorArgs &t, std::vector<uint32_t> &wins, TensorNorm &nm,
-                          const int *rv = nullptr)
+// The normalisation constants of a float tensor output, validated: both or neither, every std finite and above zero
+static int resolve_norm(const char *who, const float *mean, const float *std, TensorNorm &nm)
 {
-    if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
-    if (t.Ho < 1 || t.Wo < 1) return fail(LLICTI_EINVAL, "%s: output size %dx%d (need Ho, Wo >= 1)", who, t.Wo, t.Ho);
-    if ((t.mean == nullptr) != (t.std == nullptr)) return fail(LLICTI_EINVAL, "%s: mean and std go together (both, or both NULL)", who);
+    if ((mean == nullptr) != (std == nullptr)) return fail(LLICTI_EINVAL, "%s: mean and std go together (both, or both NULL)", who);
     memset(&nm, 0, sizeof nm);
-    if (t.mean) {
+    if (mean) {
         for (int k = 0; k < 3; ++k) {
-            if (!(t.std[k] > 0.0f) || !std::isfinite(t.std[k])) return fail(LLICTI_EINVAL, "%s: std[%d] = %g (need a finite value above zero)", who, k, (double)t.std[k]);
-            nm.mean[k] = t.mean[k]; nm.std[k] = t.std[k];
+            if (!(std[k] > 0.0f) || !std::isfinite(std[k])) return fail(LLICTI_EINVAL, "%s: std[%d] = %g (need a finite value above zero)", who, k, (double)std[k]);
+            nm.mean[k] = mean[k]; nm.std[k] = std[k];
         }
         nm.on = 1;
     }
+    return 0;
+}
+
+// Float tensor output (llicti_decode_images_tensor): the output description as the caller gave it ...
+struct TensorArgs { int dtype, Ho, Wo; const int *y0, *x0; const uint8_t *flip; const float *mean, *std; };
+// ... and validated against the call's images (FULL sizes Hs, Ws, image b decoded at rd.of(b)): every image's packed window word (tensor_win_pack)
+// and the normalisation constants.  These are the call's kernel arguments -- nothing of them enters the plan or its key.
+static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, const Reduces &rd, const TensorArgs &t, std::vector<uint32_t> &wins, TensorNorm &nm)
+{
+    if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
+    if (t.Ho < 1 || t.Wo < 1) return fail(LLICTI_EINVAL, "%s: output size %dx%d (need Ho, Wo >= 1)", who, t.Wo, t.Ho);
+    if (int rc = resolve_norm(who, t.mean, t.std, nm)) return rc;
     wins.assign(B, 0u);
     for (int b = 0; b < B; ++b) {
         const int y0 = t.y0 ? t.y0[b] : 0, x0 = t.x0 ? t.x0[b] : 0;
-        if (rv) reduce = rv[b];
+        const int reduce = rd.of(b);
         if (!tensor_window_ok(Hs[b], Ws[b], reduce, y0, x0, t.Ho, t.Wo))
             return fail(LLICTI_EINVAL, "%s: the %dx%d window at (y %d, x %d) leaves image %d (%dx%d at reduce %d)", who, t.Wo, t.Ho, y0, x0, b,
                         reduced_dim(Ws[b], reduce), reduced_dim(Hs[b], reduce), reduce);
@@ -528,22 +571,14 @@ static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, 
 // the origin -- ...
 struct ResizeArgs { int dtype, Ho, Wo; const int *y0, *x0, *hs, *ws; const uint8_t *flip; const float *mean, *std; int antialias; };
 // ... and validated like resolve_tensor's: two packed words per image (ResizeBoxes) and the normalisation constants, kernel arguments all.
-// (what does not depend on the image: dtype, output size, flag, reduce, mean and std)
-static int resolve_resize_head(const char *who, int reduce, const ResizeArgs &t, TensorNorm &nm)
+// (what does not depend on the image: dtype, output size, flag, a call-wide reduce -- per-image values are admit_reduces' to check -- mean and std)
+static int resolve_resize_head(const char *who, const Reduces &rd, const ResizeArgs &t, TensorNorm &nm)
 {
     if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
     if (t.Ho < 1 || t.Wo < 1 || t.Ho > 8160 || t.Wo > 8160) return fail(LLICTI_EINVAL, "%s: output size %dx%d (need 1 <= Ho, Wo <= 8160)", who, t.Wo, t.Ho);
     if (t.antialias != 0 && t.antialias != 1) return fail(LLICTI_EINVAL, "%s: antialias = %d (0: two taps per axis, 1: the triangle filter widened by the scale)", who, t.antialias);
-    if (reduce < 0 || reduce > LLICTI_NLEVELS) return fail(LLICTI_EINVAL, "%s: reduce = %d", who, reduce);
-    if ((t.mean == nullptr) != (t.std == nullptr)) return fail(LLICTI_EINVAL, "%s: mean and std go together (both, or both NULL)", who);
-    memset(&nm, 0, sizeof nm);
-    if (t.mean) {
-        for (int k = 0; k < 3; ++k) {
-            if (!(t.std[k] > 0.0f) || !std::isfinite(t.std[k])) return fail(LLICTI_EINVAL, "%s: std[%d] = %g (need a finite value above zero)", who, k, (double)t.std[k]);
-            nm.mean[k] = t.mean[k]; nm.std[k] = t.std[k];
-        }
-        nm.on = 1;
-    }
+    if (!rd.per_image() && (rd.r < 0 || rd.r > LLICTI_NLEVELS)) return fail(LLICTI_EINVAL, "%s: reduce = %d", who, rd.r);
+    if (int rc = resolve_norm(who, t.mean, t.std, nm)) return rc;
     return 0;
 }
 // (one box, entry k of the call's arrays, against its H x W image: `whose` is how a message names it; -> the two packed words)
@@ -563,15 +598,14 @@ static int resolve_resize_box(const char *who, const char *whose, int H, int W, 
     words[1] = resize_ext_pack(hs, ws);
     return 0;
 }
-static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ResizeArgs &t, std::vector<uint32_t> &boxes, TensorNorm &nm,
-                          const int *rv = nullptr)
+static int resolve_resize(const char *who, int B, const int *Hs, const int *Ws, const Reduces &rd, const ResizeArgs &t, std::vector<uint32_t> &boxes, TensorNorm &nm)
 {
-    if (int rc = resolve_resize_head(who, rv ? 0 : reduce, t, nm)) return rc;
+    if (int rc = resolve_resize_head(who, rd, t, nm)) return rc;
     boxes.assign(2 * (size_t)B, 0u);
     for (int b = 0; b < B; ++b) {
         char whose[32];
         snprintf(whose, sizeof whose, "image %d", b);
-        if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], rv ? rv[b] : reduce, t, b, &boxes[2 * (size_t)b])) return rc;
+        if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], rd.of(b), t, b, &boxes[2 * (size_t)b])) return rc;
     }
     return 0;
 }
@@ -581,9 +615,8 @@ struct ViewArgs { const llicti_view_group *groups; int G; const float *mean, *st
 // ... and one validated group: three packed words per view (ViewSlice), kernel arguments of the group's launches like the boxes above
 struct ViewGroupOut { void *d_out; int dtype, Ho, Wo, antialias, n; std::vector<uint32_t> words; };
 // Every view is held to resolve_resize's rules against the image it names (resolve_resize_head, resolve_resize_box: the same functions, the
-// same words); a refusal names the group and the view.  rv != nullptr (the _rv call): a view is held against the reduce of the image it names.
-static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, int reduce, const ViewArgs &a, std::vector<ViewGroupOut> &out, TensorNorm &nm,
-                         const int *rv = nullptr)
+// same words); a refusal names the group and the view.  A view is held against the reduce of the image it names.
+static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, const Reduces &rd, const ViewArgs &a, std::vector<ViewGroupOut> &out, TensorNorm &nm)
 {
     if (a.G < 1 || a.G > LLICTI_VIEW_GROUPS_MAX) return fail(LLICTI_EINVAL, "%s: %d groups (need 1 .. %d)", who, a.G, LLICTI_VIEW_GROUPS_MAX);
     if (!a.groups) return fail(LLICTI_EINVAL, "%s: null groups", who);
@@ -596,7 +629,7 @@ static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, i
         if (vg.n < 1 || vg.n > kViewCountMax) return fail(LLICTI_EINVAL, "%s: n = %d views (need 1 .. %d)", whose, vg.n, kViewCountMax);
         if (!vg.image && vg.n != B) return fail(LLICTI_EINVAL, "%s: image = NULL means view v is image v: n = %d, the batch has %d images", whose, vg.n, B);
         const ResizeArgs t{ vg.dtype, vg.Ho, vg.Wo, vg.y0, vg.x0, vg.hs, vg.ws, vg.flip, a.mean, a.std, vg.antialias };
-        if (int rc = resolve_resize_head(whose, rv ? 0 : reduce, t, nm)) return rc;
+        if (int rc = resolve_resize_head(whose, rd, t, nm)) return rc;
         ViewGroupOut &o = out[(size_t)g];
         o.d_out = vg.d_out; o.dtype = vg.dtype; o.Ho = vg.Ho; o.Wo = vg.Wo; o.antialias = vg.antialias; o.n = vg.n;
         o.words.assign(3 * (size_t)vg.n, 0u);
@@ -604,7 +637,7 @@ static int resolve_views(const char *who, int B, const int *Hs, const int *Ws, i
             const int b = vg.image ? vg.image[v] : v;
             if (b < 0 || b >= B) return fail(LLICTI_EINVAL, "%s: view %d of group %d names image %d (the batch has images 0 .. %d)", who, v, g, b, B - 1);
             snprintf(whose, sizeof whose, "view %d of group %d (image %d)", v, g, b);
-            if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], rv ? rv[b] : reduce, t, v, &o.words[3 * (size_t)v])) return rc;
+            if (int rc = resolve_resize_box(who, whose, Hs[b], Ws[b], rd.of(b), t, v, &o.words[3 * (size_t)v])) return rc;
             o.words[3 * (size_t)v + 2] = (uint32_t)b;
         }
     }
@@ -820,11 +853,7 @@ static int admit_reduces(const char *who, int B, const int *reduces, int nlev, i
                             "(per-image reduces need rANS containers)", who, b, reduces[b], reduces[0]);
     return 0;
 }
-static bool reduces_equal(int B, const int *reduces)
-{
-    for (int b = 1; b < B; ++b) if (reduces[b] != reduces[0]) return false;
-    return true;
-}
+static bool reduces_equal(int B, const int *reduces) { return std::all_of(reduces, reduces + B, [&](int v) { return v == reduces[0]; }); }
 struct ReduceSchedule {
     int B = 0, nlev = 0, rmin = 0;
     std::vector<int> r;                   // [B]
@@ -846,49 +875,20 @@ static void build_reduce_schedule(ReduceSchedule &q, const Plan &p, const int *r
                                   const std::vector<PixGeo> *pix = nullptr)
 {
     const int B = p.B, nlev = p.nlev;
+    q = ReduceSchedule{};
     q.B = B; q.nlev = nlev;
     q.r.assign(reduces, reduces + B);
-    q.rmin = nlev;
-    for (int b = 0; b < B; ++b) q.rmin = std::min(q.rmin, q.r[b]);
-    q.red.assign(B, RedGeo{});
-    q.max_rplane = 0; q.pix_units = 0;
-    long pos = 0;
-    for (int b = 0; b < B; ++b) {
-        RedGeo &rg = q.red[b];
-        rg.Hr = reduced_dim(p.img[b].H, q.r[b]); rg.Wr = reduced_dim(p.img[b].W, q.r[b]);
-        rg.off = out_off ? (long)out_off[b] : pos;
-        pos += 3L * rg.Hr * rg.Wr;
-        q.max_rplane = std::max(q.max_rplane, (long)rg.Hr * rg.Wr);
-        q.pix_units = std::max(q.pix_units, (long)rg.Hr * ((rg.Wr + 3) / 4));
-    }
-    q.pix.clear();
+    q.rmin = Reduces::each(reduces).min(B);
+    ReducedOut o = reduced_out(p.img, Reduces::each(reduces), out_off);
+    q.red.swap(o.red);
+    q.max_rplane = o.max_rplane; q.pix_units = o.pix_units;
     if (pix) q.pix = *pix;
-    q.streams.clear(); q.tiles.clear();
-    for (int k = 0; k < LLICTI_NLEVELS * 3; ++k) q.run[k] = TileRun{};
-    for (int l = 0; l < LLICTI_NLEVELS; ++l) { q.s_off[l] = 0; q.s_n[l] = 0; }
     for (int lvl = nlev - 1; lvl >= q.rmin; --lvl) {
         q.s_off[lvl] = q.streams.size();
         for (int i = 0; i < p.nstreams; ++i) if (q.r[p.sref[(size_t)i].b] <= lvl) q.streams.push_back(i);
         q.s_n[lvl] = (int)(q.streams.size() - q.s_off[lvl]);
-        const Geom *gl = &p.geo[(size_t)lvl * B];
-        auto count = [&](int th) -> long {
-            long t = 0;
-            for (int b = 0; b < B; ++b) if (q.r[b] <= lvl) t += (long)((gl[b].w + kTileW - 1) / kTileW) * ((gl[b].h + th - 1) / th);
-            return t;
-        };
-        if (count(kTileHMax) == 0) continue;
-        for (int band = 0; band < 3; ++band) {
-            const TileForm f = choose_tile_form(n_cu, tile_rows, band, count);
-            TileRun &r = q.run[lvl * 3 + band];
-            r.off = q.tiles.size(); r.n_tiles = (int)std::min<long>(f.n_tiles, 0x7FFFFFFFL); r.TH = f.TH; r.gx = f.gx;
-            for (int b = 0; b < B; ++b) {
-                if (q.r[b] > lvl) continue;
-                const int tx_n = (gl[b].w + kTileW - 1) / kTileW, ty_n = (gl[b].h + f.TH - 1) / f.TH;
-                for (int ty = 0; ty < ty_n; ++ty)
-                    for (int tx = 0; tx < tx_n; ++tx) q.tiles.push_back(TileRef{ b, (ty << 16) | tx });
-            }
-        }
     }
+    build_tile_lists(p.geo, B, nlev - 1, q.rmin - 1, [&](int b, int lvl) { return q.r[b] <= lvl; }, n_cu, tile_rows, q.tiles, q.run);
     size_t d = 0;
     auto dtake = [&](size_t bytes) { size_t r = d; d = align_up(d + bytes, 256); return r; };
     q.d_r = dtake(q.r.size() * sizeof(int));

@@ -791,9 +791,6 @@ struct RvCall {
     PlanBlock blk;
     bool have = false;
     template <class T> const T *dev(size_t off) const { return reinterpret_cast<const T *>(blk.dev + off); }
-    const int *d_r() const { return dev<int>(q.d_r); }
-    const RedGeo *d_red() const { return dev<RedGeo>(q.d_red); }
-    const PixGeo *d_pix() const { return dev<PixGeo>(q.d_pix); }
     int upload()
     {
         if (int rc = acquire_block(c, q.d_total, &blk)) return rc;
@@ -945,7 +942,7 @@ static int encode_batch(llicti_ctx *c, const EncodeSrc &src, const size_t *rgb_o
     for (int lvl = p.nlev - 1; lvl >= 0; --lvl) {
         const Geom &g = p.geo[(size_t)lvl * B];                         // image 0's (equal sizes: every image's)
         const Geom *gv = p.uniform ? nullptr : d_geo + (size_t)lvl * B;
-        hipStream_t s = (lvl >= 1) ? s2 : (hipStream_t)stream;          // (shadows the call's stream inside the loop)
+        hipStream_t ls = (lvl >= 1) ? s2 : s;                           // the level's queue
         float *params = (lvl >= 1 && side) ? (float *)(ws + p.off_params2) : (float *)(ws + p.off_params);
         const unsigned pairs_gx = (unsigned)((p.lev_maxpos[lvl] + kPairsThreads - 1) / kPairsThreads);
         if (lvl >= 1 && !side) {
@@ -954,23 +951,23 @@ static int encode_batch(llicti_ctx *c, const EncodeSrc &src, const size_t *rgb_o
             PairsBands pb;
             for (int band = 0; band < 3; ++band) {
                 float *pband = params + band * p.lev_floats[lvl];
-                if (int rc = launch_band_params(c, fplanes, g, band, pband, s, gv, d_tiles ? d_tiles + p.run[lvl * 3 + band].off : nullptr, &p.run[lvl * 3 + band])) return rc;
+                if (int rc = launch_band_params(c, fplanes, g, band, pband, ls, gv, d_tiles ? d_tiles + p.run[lvl * 3 + band].off : nullptr, &p.run[lvl * 3 + band])) return rc;
                 pb.sv[band] = d_sg + (size_t)(lvl * 3 + band) * B;
                 pb.params[band] = pband;
                 pb.pairs[band] = pairs + p.pair_base[lvl * 3 + band];
             }
-            ProfSpan span(c, PROF_PAIRS, s);
-            cdf_pairs_bands_kernel<<<dim3(pairs_gx, B, 3), kPairsThreads, 0, s>>>(planes, pb, mm);
+            ProfSpan span(c, PROF_PAIRS, ls);
+            cdf_pairs_bands_kernel<<<dim3(pairs_gx, B, 3), kPairsThreads, 0, ls>>>(planes, pb, mm);
             HIPCHK(hipGetLastError());
             continue;
         }
         for (int band = 0; band < 3; ++band) {
             // (a launch's CNN outputs are read once, by the pairs kernel right behind it; cutting level 0 into sub-batches whose outputs stay in
             // the memory-side cache was measured and bought nothing: profiles/r4/tried_encoder_subbatch.json)
-            if (int rc = launch_band_params(c, fplanes, g, band, params, s, gv, d_tiles ? d_tiles + p.run[lvl * 3 + band].off : nullptr, &p.run[lvl * 3 + band])) return rc;
-            ProfSpan span(c, PROF_PAIRS, s);
+            if (int rc = launch_band_params(c, fplanes, g, band, params, ls, gv, d_tiles ? d_tiles + p.run[lvl * 3 + band].off : nullptr, &p.run[lvl * 3 + band])) return rc;
+            ProfSpan span(c, PROF_PAIRS, ls);
             const StageGeom *sv = d_sg + (size_t)(lvl * 3 + band) * B;
-            cdf_pairs_kernel<<<dim3(pairs_gx, B), kPairsThreads, 0, s>>>(planes, params, mm, p.sg[(size_t)(lvl * 3 + band) * B], sv, pairs + p.pair_base[lvl * 3 + band]);
+            cdf_pairs_kernel<<<dim3(pairs_gx, B), kPairsThreads, 0, ls>>>(planes, params, mm, p.sg[(size_t)(lvl * 3 + band) * B], sv, pairs + p.pair_base[lvl * 3 + band]);
             HIPCHK(hipGetLastError());
         }
     }
@@ -1008,8 +1005,20 @@ extern "C" int llicti_encode_images(llicti_ctx *c, const uint8_t *d_rgb, int B, 
 }
 
 // ------------------------------------------------------------------------------------------------ decode
-// What a whole-batch decode ends in: ONE value of one kind.  An entry point fills in what its caller gave; decode_batch validates that against
-// the call's images (resolve_sink: the kind's payload, which is all launch_sink reads) -- reduced planar output is Planar at reduce > 0.
+// One whole-batch decode as its entry point received it: containers, images, container modes, workspace, where a Planar sink's images go
+// (rgb_off; NULL: tight, and for every other kind), the caller's stream, and the level(s) the images stop at.
+struct DecodeCall {
+    const uint8_t *d_in; size_t in_stride; const int32_t *d_seg_len;
+    int B; const int *Hs, *Ws, *modes; int n_modes;
+    void *d_workspace; size_t workspace_bytes;
+    const size_t *rgb_off;
+    void *stream;
+    Reduces rd;
+};
+
+// What a whole-batch decode ends in: ONE value of one kind.  An entry point fills in what its caller gave (one builder per kind, below);
+// decode_batch validates that against the call's images (resolve_sink: the kind's payload, which is all launch_sink reads) -- reduced planar
+// output is Planar at reduce > 0.
 struct DecodeSink {
     enum Kind { Planar, Interleaved, Tensor, Resized, Views, Transcode } kind = Planar;
     uint8_t *d_out = nullptr;               // the caller's buffer (Views: none, every group has its own)
@@ -1028,25 +1037,60 @@ struct DecodeSink {
     PlanDev *target = nullptr;
     uint8_t *target_ws = nullptr;
 };
+static DecodeSink planar_sink(uint8_t *d_rgb) { DecodeSink k; k.d_out = d_rgb; return k; }
+static DecodeSink px_sink(uint8_t *d_pix, const PixArgs &px) { DecodeSink k; k.kind = DecodeSink::Interleaved; k.d_out = d_pix; k.px = px; return k; }
+static DecodeSink tensor_sink(void *d_out, const TensorArgs &t) { DecodeSink k; k.kind = DecodeSink::Tensor; k.d_out = (uint8_t *)d_out; k.tensor = t; return k; }
+static DecodeSink resized_sink(void *d_out, const ResizeArgs &t) { DecodeSink k; k.kind = DecodeSink::Resized; k.d_out = (uint8_t *)d_out; k.resize = t; return k; }
+static DecodeSink views_sink(const ViewArgs &a) { DecodeSink k; k.kind = DecodeSink::Views; k.views = a; return k; }
 
-// rv: the _rv calls' per-image reduces (nullptr: `reduce` for every image)
-static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, int reduce, const int *rv = nullptr)
+static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, const Reduces &rd)
 {
     switch (k.kind) {
     case DecodeSink::Interleaved: {
         std::vector<int> Hw(B), Ww(B);      // the windows: the reduced sizes
-        for (int b = 0; b < B; ++b) { const int r = rv ? rv[b] : reduce; Hw[b] = reduced_dim(Hs[b], r); Ww[b] = reduced_dim(Ws[b], r); }
+        for (int b = 0; b < B; ++b) { Hw[b] = reduced_dim(Hs[b], rd.of(b)); Ww[b] = reduced_dim(Ws[b], rd.of(b)); }
         return resolve_pixels("decode_images_px", B, Hw.data(), Ww.data(), k.px.fmt, k.px.off, k.px.pitch, k.pix);
     }
     case DecodeSink::Tensor:
-        return resolve_tensor("decode_images_tensor", B, Hs, Ws, reduce, k.tensor, k.wins, k.nm, rv);
+        return resolve_tensor("decode_images_tensor", B, Hs, Ws, rd, k.tensor, k.wins, k.nm);
     case DecodeSink::Resized:
-        return resolve_resize("decode_images_tensor_resized", B, Hs, Ws, reduce, k.resize, k.wins, k.nm, rv);
+        return resolve_resize("decode_images_tensor_resized", B, Hs, Ws, rd, k.resize, k.wins, k.nm);
     case DecodeSink::Views:
-        return resolve_views("decode_images_tensor_views", B, Hs, Ws, reduce, k.views, k.groups, k.nm, rv);
+        return resolve_views("decode_images_tensor_views", B, Hs, Ws, rd, k.views, k.groups, k.nm);
     default:
         return 0;
     }
+}
+
+// What differs between a plan-driven decode and an _rv one, resolved ONCE per call (plan_run / rv_run) so that no launch asks which it is.
+// A level: the streams that take part in it (act: their indices in the plan's stream table, nullptr = all NS of them), the band CNN's Geom table
+// (nullptr: the division form of an equal-size plan), its three TileRuns and the tile table their offsets count in (nullptr: none).
+struct LevelRun { int NS; const int *act; const Geom *gv; const TileRun *run; const TileRef *tiles; };
+struct DecodeRun {
+    int stop;                               // levels nlev - 1 .. stop run
+    LevelRun lev[LLICTI_NLEVELS];
+    // the sink: the reduce every image stops at, or rtab with each image's own (r is 0 then: the kernels read the table); the reduced output
+    // table and the pixel windows (nullptr: none), and what sizes the grids of unlift_reduced_kernel / unlift_px_kernel
+    int r; const int *rtab; const RedGeo *d_red; const PixGeo *d_pix; long max_rplane, pix_units;
+};
+static DecodeRun plan_run(PlanDev *pd, int reduce)
+{
+    const Plan &p = pd->p;
+    DecodeRun r{ reduce, {}, reduce, nullptr, reduce > 0 ? pd->dev<RedGeo>(p.d_red) : nullptr, p.pix.empty() ? nullptr : pd->dev<PixGeo>(p.d_pix), p.max_rplane, p.pix_units };
+    for (int lvl = 0; lvl < LLICTI_NLEVELS; ++lvl)
+        r.lev[lvl] = { p.nstreams, nullptr, p.uniform ? nullptr : pd->dev<Geom>(p.d_geo) + (size_t)lvl * p.B, &p.run[lvl * 3], p.uniform ? nullptr : pd->dev<TileRef>(p.d_tiles) };
+    return r;
+}
+// (rANS containers only: level lvl runs for the images with r_b <= lvl alone -- the band CNN in its tile-list form over the call's list of that
+// level, on an equal-size plan too: its Geom table is on the device; the stage kernels and the tail with one workgroup per ACTIVE stream)
+static DecodeRun rv_run(PlanDev *pd, const RvCall &rv)
+{
+    const Plan &p = pd->p;
+    const ReduceSchedule &q = rv.q;
+    DecodeRun r{ q.rmin, {}, 0, rv.dev<int>(q.d_r), rv.dev<RedGeo>(q.d_red), q.pix.empty() ? nullptr : rv.dev<PixGeo>(q.d_pix), q.max_rplane, q.pix_units };
+    for (int lvl = 0; lvl < LLICTI_NLEVELS; ++lvl)
+        r.lev[lvl] = { q.s_n[lvl], rv.dev<int>(q.d_streams) + q.s_off[lvl], pd->dev<Geom>(p.d_geo) + (size_t)lvl * p.B, &q.run[lvl * 3], rv.dev<TileRef>(q.d_tiles) };
+    return r;
 }
 
 // calls f with a value of the element type an output tensor's (validated) dtype names
@@ -1065,18 +1109,28 @@ template <typename S> static S arg_slice(const std::vector<uint32_t> &words, int
     return a;
 }
 
+// Where the kernels of a decode find their data: the workspace as pd's plan carves it, and the plan's device tables
+struct DecodeBufs {
+    int16_t *planes; float *fplanes; int32_t *mm, *status; float *params; uint8_t *slots, *tables; uint32_t *acstate; int32_t *slot_len;
+    uint32_t *rstate, *rpos, *rtail;
+    const ImgGeo *d_img; const StageGeom *d_sg; const long *d_rslot_off; const StreamRef *d_sref;
+    DecodeBufs(const PlanDev *pd, uint8_t *ws)
+    {
+        const Plan &p = pd->p;
+        planes = (int16_t *)(ws + p.off_planes); fplanes = (float *)(ws + p.off_fplanes); mm = (int32_t *)(ws + p.off_minmax);
+        status = (int32_t *)(ws + p.off_status); params = (float *)(ws + p.off_params); slots = ws + p.off_slots; tables = ws + p.off_tables;
+        acstate = (uint32_t *)(ws + p.off_acstate); slot_len = (int32_t *)(ws + p.off_slot_len);
+        rstate = (uint32_t *)(ws + p.off_rstate); rpos = (uint32_t *)(ws + p.off_rpos); rtail = (uint32_t *)(ws + p.off_rtail);
+        d_img = pd->dev<ImgGeo>(p.d_img); d_sg = pd->dev<StageGeom>(p.d_sg); d_rslot_off = pd->dev<long>(p.d_rslot_off); d_sref = pd->dev<StreamRef>(p.d_sref);
+    }
+};
+
 // The last kernel(s) of a decode, one block per kind.  Each latches the call's status words into the context's (the workspace is the caller's:
 // it may be gone or reused by the time the words are read); every side stream of the reference-format pipeline was joined back onto `s` at the
 // end of its band, so nothing is pending here.
-// rv (an _rv call): every image's own r comes from the call's table, and so do the reduced output table and the pixel windows.
-static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t *ws, hipStream_t s, int reduce, const RvCall *rv = nullptr)
+static int launch_sink(llicti_ctx *c, const Plan &p, const DecodeBufs &w, const DecodeSink &k, hipStream_t s, const DecodeRun &o)
 {
-    const int *rtab = rv ? rv->d_r() : nullptr;
-    const Plan &p = pd->p;
     const int B = p.B;
-    const int16_t *planes = (const int16_t *)(ws + p.off_planes);
-    const int32_t *status = (const int32_t *)(ws + p.off_status);
-    const ImgGeo *d_img = pd->dev<ImgGeo>(p.d_img);
     if (k.kind == DecodeSink::Transcode) return 0;      // (no pixels: the caller goes on with the target's header and coder, and latches the status words itself)
     ProfSpan span(c, PROF_MISC, s);
     switch (k.kind) {
@@ -1090,8 +1144,8 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
             const TensorWins tw = arg_slice<TensorWins>(k.wins, 1, b0, nb);
             with_tensor_type(t.dtype, [&](auto e) {
                 using T = decltype(e);
-                unlift_tensor_kernel<T><<<dim3(gx, nb), 256, 0, s>>>(planes, (T *)k.d_out, reduce, t.Ho, t.Wo, b0, tw, k.nm, status, kStatusHead, c->d_status,
-                                                                    c->d_img_status, d_img, rtab);
+                unlift_tensor_kernel<T><<<dim3(gx, nb), 256, 0, s>>>(w.planes, (T *)k.d_out, o.r, t.Ho, t.Wo, b0, tw, k.nm, w.status, kStatusHead, c->d_status,
+                                                                    c->d_img_status, w.d_img, o.rtab);
             });
         }
         break;
@@ -1106,8 +1160,8 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
             const ResizeBoxes bx = arg_slice<ResizeBoxes>(k.wins, 2, b0, nb);
             with_tensor_type(t.dtype, [&](auto e) {
                 using T = decltype(e);
-                unlift_resize_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(planes, (T *)k.d_out, reduce, t.Ho, t.Wo, b0, tiles_x, t.antialias, bx, k.nm,
-                                                                                          status, kStatusHead, c->d_status, c->d_img_status, d_img, rtab);
+                unlift_resize_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(w.planes, (T *)k.d_out, o.r, t.Ho, t.Wo, b0, tiles_x, t.antialias, bx, k.nm,
+                                                                                          w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img, o.rtab);
             });
         }
         break;
@@ -1123,8 +1177,8 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
                 const ViewSlice vs = arg_slice<ViewSlice>(g.words, 3, v0, nv);
                 with_tensor_type(g.dtype, [&](auto e) {
                     using T = decltype(e);
-                    unlift_views_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(planes, (T *)g.d_out, reduce, g.Ho, g.Wo, v0, tiles_x, g.antialias, vs, k.nm,
-                                                                                             status, kStatusHead, c->d_status, c->d_img_status, d_img, latch_n, rtab);
+                    unlift_views_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(w.planes, (T *)g.d_out, o.r, g.Ho, g.Wo, v0, tiles_x, g.antialias, vs, k.nm,
+                                                                                             w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img, latch_n, o.rtab);
                 });
                 latch_n = 0;
             }
@@ -1132,170 +1186,159 @@ static int launch_sink(llicti_ctx *c, PlanDev *pd, const DecodeSink &k, uint8_t 
         break;
     }
     case DecodeSink::Interleaved: {
-        // full size or reduced: one kernel, the window table behind the plan's others
-        const int gx = (int)std::min<long>(((rv ? rv->q.pix_units : p.pix_units) + 255) / 256, 1024);
-        if (rv) unlift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, k.d_out, 0, status, kStatusHead, c->d_status, c->d_img_status, d_img, rv->d_red(), rv->d_pix(), rtab);
-        else unlift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, k.d_out, reduce, status, kStatusHead, c->d_status, c->d_img_status, d_img,
-                                                          reduce > 0 ? pd->dev<RedGeo>(p.d_red) : nullptr, pd->dev<PixGeo>(p.d_pix));
+        // full size or reduced: one kernel, the window table behind the call's others
+        const int gx = (int)std::min<long>((o.pix_units + 255) / 256, 1024);
+        unlift_px_kernel<<<dim3(gx, B), 256, 0, s>>>(w.planes, k.d_out, o.r, w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img, o.d_red, o.d_pix, o.rtab);
         break;
     }
     default:                                            // Planar (Transcode has returned above)
-        if (rv) {
-            unlift_reduced_kernel<<<dim3((unsigned)((rv->q.max_rplane + 255) / 256), B), 256, 0, s>>>(planes, k.d_out, 0, status, kStatusHead, c->d_status,
-                                                                                                      c->d_img_status, d_img, rv->d_red(), rtab);
-        } else if (reduce > 0) {
-            long max_rplane = 0;
-            for (const RedGeo &rg : p.red) max_rplane = std::max(max_rplane, (long)rg.Hr * rg.Wr);
-            unlift_reduced_kernel<<<dim3((unsigned)((max_rplane + 255) / 256), B), 256, 0, s>>>(planes, k.d_out, reduce, status, kStatusHead, c->d_status,
-                                                                                                c->d_img_status, d_img, pd->dev<RedGeo>(p.d_red));
+        if (o.d_red) {
+            unlift_reduced_kernel<<<dim3((unsigned)((o.max_rplane + 255) / 256), B), 256, 0, s>>>(w.planes, k.d_out, o.r, w.status, kStatusHead, c->d_status,
+                                                                                                  c->d_img_status, w.d_img, o.d_red, o.rtab);
         } else {
             const int gx = (int)std::min<long>((p.max_plane + 255) / 256, 1024);
-            unlift_kernel<<<dim3(gx, B), 256, 0, s>>>(planes, p.max_plane, k.d_out, status, kStatusHead, c->d_status, c->d_img_status, d_img);
+            unlift_kernel<<<dim3(gx, B), 256, 0, s>>>(w.planes, p.max_plane, k.d_out, w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img);
         }
     }
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// rv (an _rv call, rANS containers only; reduce = the smallest of its values): level lvl runs for the images with r_b <= lvl alone -- the band
-// CNN in its tile-list form over the call's list of that level (on an equal-size plan too: its Geom table is on the device), the stage kernels
-// and the tail with one workgroup per ACTIVE stream, which they find through the level's list.
-static int decode_stages(llicti_ctx *c, PlanDev *pd, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, uint8_t *ws, hipStream_t s, int reduce,
-                         const DecodeSink &sink, const RvCall *rv = nullptr)
+// The front of a decode: the call's status words cleared, the headers read, the containers unpacked into the slots, the rANS states set up
+static int decode_prologue(llicti_ctx *c, PlanDev *pd, const DecodeBufs &w, const DecodeCall &a, hipStream_t s)
 {
     const Plan &p = pd->p;
-    const int B = p.B, M = p.M, Q = p.Q;
-    int16_t *planes = (int16_t *)(ws + p.off_planes);
-    float *fplanes = (float *)(ws + p.off_fplanes);
-    int32_t *mm = (int32_t *)(ws + p.off_minmax);
-    int32_t *status = (int32_t *)(ws + p.off_status);
-    float *params = (float *)(ws + p.off_params);
-    uint8_t *slots = ws + p.off_slots;
-    uint8_t *tables = ws + p.off_tables;
-    uint32_t *acstate = (uint32_t *)(ws + p.off_acstate);
-    int32_t *slot_len = (int32_t *)(ws + p.off_slot_len);
-    const ImgGeo *d_img = pd->dev<ImgGeo>(p.d_img);
-    const Geom *d_geo = pd->dev<Geom>(p.d_geo);
-    const StageGeom *d_sg = pd->dev<StageGeom>(p.d_sg);
-    const long *d_rslot_off = pd->dev<long>(p.d_rslot_off);
-    const StreamRef *d_sref = pd->dev<StreamRef>(p.d_sref);
-    const int NS = p.nstreams;
-    const TileRef *d_tiles = p.uniform ? nullptr : pd->dev<TileRef>(p.d_tiles);
+    const int B = p.B, Q = p.Q, NS = p.nstreams;
+    zero_words_kernel<<<(kStatusHead + B + 255) / 256, 256, 0, s>>>(w.status, kStatusHead + B);
+    ProfSpan span(c, PROF_MISC, s);
+    header_read_kernel<<<B, 256, 0, s>>>(a.d_in, (long)a.in_stride, a.d_seg_len, w.d_img, w.planes, w.fplanes, w.mm, w.status);
+    if (p.M == 0) {
+        const int st0 = first_stage(p.nlev);
+        unpack_kernel<<<dim3(LLICTI_NSTREAMS - st0, B), 256, 0, s>>>(a.d_in, (long)a.in_stride, a.d_seg_len, B, w.slots, pd->dev<long>(p.d_slot_off), pd->dev<int32_t>(p.d_slot_cap), w.slot_len, w.status, st0);
+    } else {
+        const StageGeom *sglv = w.d_sg + (size_t)(0 * 3 + 2) * B;      // the last stage: an xwide v4 tail is at most the stream's share of it
+        rans_unpack_kernel<<<NS, 256, 0, s>>>(a.d_in, (long)a.in_stride, a.d_seg_len, w.d_sref, 2 + Q * RansGeo<1>::kPayBytes,
+                                              w.slots, w.d_rslot_off, p.rslot_cap, w.rpos, w.status, Q == 4 ? 4 : 2);
+        if (Q == 4) rans_init_kernel<4><<<NS, 64, 0, s>>>(w.slots, w.d_rslot_off, w.d_sref, w.rstate, w.rpos, w.rtail, w.status, sglv);
+        else if (Q == 2) rans_init_kernel<2><<<NS, 64, 0, s>>>(w.slots, w.d_rslot_off, w.d_sref, w.rstate, w.rpos, w.rtail, w.status, sglv);
+        else rans_init_kernel<1><<<NS, 64, 0, s>>>(w.slots, w.d_rslot_off, w.d_sref, w.rstate, w.rpos, w.rtail, w.status, sglv);
+    }
+    return 0;
+}
 
-    zero_words_kernel<<<(kStatusHead + B + 255) / 256, 256, 0, s>>>(status, kStatusHead + B);
-    uint32_t *rstate = (uint32_t *)(ws + p.off_rstate);
-    uint32_t *rpos = (uint32_t *)(ws + p.off_rpos);
-    uint32_t *rtail = (uint32_t *)(ws + p.off_rtail);
+// One (level, band) of the rANS containers: the three colours' stage in one launch of a workgroup per stream of the level, and behind the last
+// stage the tail coder
+static void rans_stage(llicti_ctx *c, const Plan &p, const DecodeBufs &w, int lvl, int band, const LevelRun &lr, hipStream_t s)
+{
+    const int Q = p.Q, NS = lr.NS;
+    const StageGeom *sgv = w.d_sg + (size_t)(lvl * 3 + band) * p.B;
+    const int last = (lvl == 0 && band == 2) ? 1 : 0;      // the last stage's tail symbols are decoded by rans_tail_kernel
     {
-        ProfSpan span(c, PROF_MISC, s);
-        header_read_kernel<<<B, 256, 0, s>>>(d_in, (long)in_stride, d_seg_len, d_img, planes, fplanes, mm, status);
-        if (M == 0) {
-            const int st0 = first_stage(p.nlev);
-            unpack_kernel<<<dim3(LLICTI_NSTREAMS - st0, B), 256, 0, s>>>(d_in, (long)in_stride, d_seg_len, B, slots, pd->dev<long>(p.d_slot_off), pd->dev<int32_t>(p.d_slot_cap), slot_len, status, st0);
+        ProfSpan span(c, PROF_RANS_STAGE, s);
+        if (Q == 4) {
+            rans_decode_stage_lane_kernel<4><<<NS, 256, 0, s>>>(w.params, sgv, w.d_sref, w.slots, w.d_rslot_off, p.rslot_cap, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, last, w.status, c->d_phi_lut, lr.act);
+        } else if (Q == 2) {
+            rans_decode_stage_pair_kernel<<<NS, 64 * kRansWaves, 0, s>>>(w.params, sgv, w.d_sref, c->d_phi_lut, w.slots, w.d_rslot_off, p.rslot_cap, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, last, w.status, lr.act);
         } else {
-            const StageGeom *sglv = d_sg + (size_t)(0 * 3 + 2) * B;      // the last stage: an xwide v4 tail is at most the stream's share of it
-            rans_unpack_kernel<<<NS, 256, 0, s>>>(d_in, (long)in_stride, d_seg_len, d_sref, 2 + Q * RansGeo<1>::kPayBytes,
-                                                  slots, d_rslot_off, p.rslot_cap, rpos, status, Q == 4 ? 4 : 2);
-            if (Q == 4) rans_init_kernel<4><<<NS, 64, 0, s>>>(slots, d_rslot_off, d_sref, rstate, rpos, rtail, status, sglv);
-            else if (Q == 2) rans_init_kernel<2><<<NS, 64, 0, s>>>(slots, d_rslot_off, d_sref, rstate, rpos, rtail, status, sglv);
-            else rans_init_kernel<1><<<NS, 64, 0, s>>>(slots, d_rslot_off, d_sref, rstate, rpos, rtail, status, sglv);
+            rans_decode_stage_kernel<<<NS, 64 * kRansWaves, 0, s>>>(w.params, sgv, w.d_sref, c->d_phi_lut, w.slots, w.d_rslot_off, p.rslot_cap, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, last, w.status, lr.act);
         }
     }
-    // 45 dependent stages (LLICTI_nets.py:440-498; 9 L for a model of L levels): CNN of band b needs bands < b of this level, Co needs Y, Cg needs Y, Co
-    // A reduced decode (reduce = r >= 1) stops after level r: every pixel whose row and column are multiples of 2^r is final then, and nothing that
-    // ran reads a finer one.  The whole container has been unpacked above; the rANS bit region is read downwards from the stream's end and the coarse
-    // stages come first, so stopping is sound -- but the tail coder (the last stage's) never runs, and with it the end-of-stream check.
-    if (rv && M == 0) return fail(LLICTI_EINVAL, "decode_images: per-image reduces need rANS containers");
-    for (int lvl = p.nlev - 1; lvl >= reduce; --lvl) {
+    if (last) {
+        ProfSpan span(c, PROF_RANS_TAIL, s);
+        if (Q == 4) rans_tail_kernel<4><<<NS, 64 * (1 + kTailAhead) * kTailChains<4>, 0, s>>>(w.params, sgv, w.d_sref, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, w.status, w.slots, w.d_rslot_off, lr.act);
+        else if (Q == 2) rans_tail_kernel<2><<<NS, 64 * (1 + kTailAhead), 0, s>>>(w.params, sgv, w.d_sref, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, w.status, w.slots, w.d_rslot_off, lr.act);
+        else rans_tail_kernel<1><<<NS, 64 * (1 + kTailAhead), 0, s>>>(w.params, sgv, w.d_sref, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, w.status, w.slots, w.d_rslot_off, lr.act);
+    }
+}
+
+// One (level, band) of the reference-format container (equal sizes only; g: every image's geometry): Y, Co, Cg of this band as a pipeline over
+// chunks of the stage: chunk c of Co needs only chunk c of Y (mean update from the SAME pixel, LLICTI_nets.py:474-477), chunk c of Cg only chunk
+// c of Y and Co.  Three HIP streams; tables are built per chunk into one buffer per colour; the coder state of a stream travels between its
+// chunk launches in `acstate`.  The colour queues are joined back onto `s` at the end.
+static int ac_stage(llicti_ctx *c, const Plan &p, const DecodeBufs &w, const Geom &g, int lvl, int band, hipStream_t s)
+{
+    const int B = p.B;
+    const StageGeom sg = make_stage(g, band);
+    const long nc = (long)sg.hc * sg.wc;
+    const int C = ac_chunks(nc);
+    const long rows = ac_chunk_rows(nc);
+    hipStream_t q[3] = { s, c->sub[1], c->sub[2] };
+    if (C > 1) {
+        HIPCHK(hipEventRecord(c->ev_ac_band, s));
+        HIPCHK(hipStreamWaitEvent(q[1], c->ev_ac_band, 0));
+        HIPCHK(hipStreamWaitEvent(q[2], c->ev_ac_band, 0));
+    }
+    for (int ch = 0; ch < C; ++ch) {
+        const long n0 = (long)ch * rows, cnt = std::min(rows, nc - n0);
+        for (int clr = 0; clr < 3; ++clr) {
+            hipStream_t qs = (C > 1) ? q[clr] : s;
+            if (C > 1 && clr > 0) HIPCHK(hipStreamWaitEvent(qs, c->ev_ac[clr - 1][ch], 0));
+            ProfSpan span(c, PROF_AC, qs);
+            const bool anchors = ac_use_anchors(B, c->ac_anchor_min_batch);
+            const int row_stride = (clr == 0) ? 264 : 512;      // full rows: Y has Lp = 257, Co / Cg Lp <= 512
+            uint8_t *tab = w.tables + (size_t)clr * B * p.ac_cap_rows * (anchors ? (size_t)kAnchorRow : (size_t)1024);
+            if (anchors) { if (int rc = launch_cdf_anchors(w.planes, w.params, w.mm, g, band, clr, tab, n0, cnt, p.ac_cap_rows, qs)) return rc; }
+            else if (int rc = launch_cdf_table(w.planes, w.params, w.mm, g, band, clr, (uint16_t *)tab, row_stride, n0, cnt, p.ac_cap_rows, qs)) return rc;
+            const int st = stage_index(lvl, band, clr);
+            DecOut o;
+            memset(&o, 0, sizeof o);
+            o.planes = w.planes; o.fplanes = w.fplanes; o.minmax = w.mm; o.sg = sg; o.clr = clr;
+            o.len = w.slot_len + (size_t)st * B;
+            // the B streams of one stage sit in consecutive slots of equal capacity
+            const long in_stride_slots = p.slot_cap[(size_t)st * B];
+            AcChunk ck = { (int)n0, (int)cnt, (int)nc, (int)p.ac_cap_rows, w.acstate + (size_t)clr * B * 8 };
+            if (anchors) ac_decode_anchor_kernel<<<B, 64, 0, qs>>>(tab, w.slots + p.slot_off[(size_t)st * B], in_stride_slots, ck, o);
+            else ac_decode_kernel<<<B, 64, 0, qs>>>((const uint16_t *)tab, 0, row_stride, w.slots + p.slot_off[(size_t)st * B], in_stride_slots, ck, o);
+            if (C > 1 && clr < 2) HIPCHK(hipEventRecord(c->ev_ac[clr][ch], qs));
+        }
+    }
+    if (C > 1) {
+        for (int k = 1; k < 3; ++k) {
+            HIPCHK(hipEventRecord(c->ev_ac_end[k - 1], q[k]));
+            HIPCHK(hipStreamWaitEvent(s, c->ev_ac_end[k - 1], 0));
+        }
+    }
+    return 0;
+}
+
+// A transcode's tap behind a (level, band): the target plan's pairs from the stage's CNN outputs and symbols (the next band's CNN launch, which
+// overwrites `params`, follows on `s`)
+static int transcode_tap(llicti_ctx *c, const DecodeBufs &w, const DecodeSink &sink, int B, int lvl, int band, hipStream_t s)
+{
+    const Plan &q = sink.target->p;
+    const int k = lvl * 3 + band;
+    ProfSpan span(c, PROF_PAIRS, s);
+    cdf_pairs_kernel<<<dim3((unsigned)((q.lev_maxpos[lvl] + kPairsThreads - 1) / kPairsThreads), B), kPairsThreads, 0, s>>>(
+        w.planes, w.params, w.mm, q.sg[(size_t)k * B], sink.target->dev<StageGeom>(q.d_sg) + (size_t)k * B,
+        (uint32_t *)(sink.target_ws + q.off_pairs) + q.pair_base[k]);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// 45 dependent stages (LLICTI_nets.py:440-498; 9 L for a model of L levels): CNN of band b needs bands < b of this level, Co needs Y, Cg needs Y, Co
+// A reduced decode (run.stop = r >= 1) stops after level r: every pixel whose row and column are multiples of 2^r is final then, and nothing that
+// ran reads a finer one.  The whole container has been unpacked by the prologue; the rANS bit region is read downwards from the stream's end and the
+// coarse stages come first, so stopping is sound -- but the tail coder (the last stage's) never runs, and with it the end-of-stream check.
+static int decode_stages(llicti_ctx *c, PlanDev *pd, const DecodeCall &a, uint8_t *ws, hipStream_t s, const DecodeRun &run, const DecodeSink &sink)
+{
+    const Plan &p = pd->p;
+    const int B = p.B, M = p.M;
+    const DecodeBufs w(pd, ws);
+    if (int rc = decode_prologue(c, pd, w, a, s)) return rc;
+    if (run.rtab && M == 0) return fail(LLICTI_EINVAL, "decode_images: per-image reduces need rANS containers");
+    for (int lvl = p.nlev - 1; lvl >= run.stop; --lvl) {
         const Geom &g = p.geo[(size_t)lvl * B];                         // image 0's (equal sizes: every image's)
-        const Geom *gv = (p.uniform && !rv) ? nullptr : d_geo + (size_t)lvl * B;
-        const int NS = rv ? rv->q.s_n[lvl] : p.nstreams;               // (shadows the call's: the level's active streams)
-        const int *act = rv ? rv->dev<int>(rv->q.d_streams) + rv->q.s_off[lvl] : nullptr;
-        if (NS == 0 && M > 0) continue;                                 // (no image takes part in the level)
+        const LevelRun &lr = run.lev[lvl];
+        if (lr.NS == 0 && M > 0) continue;                              // (no image takes part in the level)
         for (int band = 0; band < 3; ++band) {
-            const TileRun *run = rv ? &rv->q.run[lvl * 3 + band] : &p.run[lvl * 3 + band];
-            const TileRef *tl = rv ? rv->dev<TileRef>(rv->q.d_tiles) + run->off : d_tiles ? d_tiles + run->off : nullptr;
-            if (int rc = launch_band_params(c, fplanes, g, band, params, s, gv, tl, run)) return rc;
-            const StageGeom *sgv = d_sg + (size_t)(lvl * 3 + band) * B;
-            if (M > 0) {
-                const int last = (lvl == 0 && band == 2) ? 1 : 0;      // the last stage's tail symbols are decoded by rans_tail_kernel
-                {
-                ProfSpan span(c, PROF_RANS_STAGE, s);
-                if (Q == 4) {
-                    rans_decode_stage_lane_kernel<4><<<NS, 256, 0, s>>>(params, sgv, d_sref, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status, c->d_phi_lut, act);
-                } else if (Q == 2) {
-                    rans_decode_stage_pair_kernel<<<NS, 64 * kRansWaves, 0, s>>>(params, sgv, d_sref, c->d_phi_lut, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status, act);
-                } else {
-                    rans_decode_stage_kernel<<<NS, 64 * kRansWaves, 0, s>>>(params, sgv, d_sref, c->d_phi_lut, slots, d_rslot_off, p.rslot_cap, rstate, rpos, rtail, planes, fplanes, mm, last, status, act);
-                }
-                }
-                if (last) {
-                    ProfSpan span(c, PROF_RANS_TAIL, s);
-                    if (Q == 4) rans_tail_kernel<4><<<NS, 64 * (1 + kTailAhead) * kTailChains<4>, 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off, act);
-                    else if (Q == 2) rans_tail_kernel<2><<<NS, 64 * (1 + kTailAhead), 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off, act);
-                    else rans_tail_kernel<1><<<NS, 64 * (1 + kTailAhead), 0, s>>>(params, sgv, d_sref, rstate, rpos, rtail, planes, fplanes, mm, status, slots, d_rslot_off, act);
-                }
-            }
-            if (M == 0) {
-                // (equal sizes only)  Y, Co, Cg of this band as a pipeline over chunks of the stage: chunk c of Co needs only chunk c
-                // of Y (mean update from the SAME pixel, LLICTI_nets.py:474-477), chunk c of Cg only chunk c of
-                // Y and Co.  Three HIP streams; tables are built per chunk into one buffer per colour; the coder
-                // state of a stream travels between its chunk launches in `acstate`.
-                const StageGeom sg = make_stage(g, band);
-                const long nc = (long)sg.hc * sg.wc;
-                const int C = ac_chunks(nc);
-                const long rows = ac_chunk_rows(nc);
-                hipStream_t q[3] = { s, c->sub[1], c->sub[2] };
-                if (C > 1) {
-                    HIPCHK(hipEventRecord(c->ev_ac_band, s));
-                    HIPCHK(hipStreamWaitEvent(q[1], c->ev_ac_band, 0));
-                    HIPCHK(hipStreamWaitEvent(q[2], c->ev_ac_band, 0));
-                }
-                for (int ch = 0; ch < C; ++ch) {
-                    const long n0 = (long)ch * rows, cnt = std::min(rows, nc - n0);
-                    for (int clr = 0; clr < 3; ++clr) {
-                        hipStream_t qs = (C > 1) ? q[clr] : s;
-                        if (C > 1 && clr > 0) HIPCHK(hipStreamWaitEvent(qs, c->ev_ac[clr - 1][ch], 0));
-                        ProfSpan span(c, PROF_AC, qs);
-                        const bool anchors = ac_use_anchors(B, c->ac_anchor_min_batch);
-                        const int row_stride = (clr == 0) ? 264 : 512;      // full rows: Y has Lp = 257, Co / Cg Lp <= 512
-                        uint8_t *tab = tables + (size_t)clr * B * p.ac_cap_rows * (anchors ? (size_t)kAnchorRow : (size_t)1024);
-                        if (anchors) { if (int rc = launch_cdf_anchors(planes, params, mm, g, band, clr, tab, n0, cnt, p.ac_cap_rows, qs)) return rc; }
-                        else if (int rc = launch_cdf_table(planes, params, mm, g, band, clr, (uint16_t *)tab, row_stride, n0, cnt, p.ac_cap_rows, qs)) return rc;
-                        const int st = stage_index(lvl, band, clr);
-                        DecOut o;
-                        memset(&o, 0, sizeof o);
-                        o.planes = planes; o.fplanes = fplanes; o.minmax = mm; o.sg = sg; o.clr = clr;
-                        o.len = slot_len + (size_t)st * B;
-                        // the B streams of one stage sit in consecutive slots of equal capacity
-                        const long in_stride_slots = p.slot_cap[(size_t)st * B];
-                        AcChunk ck = { (int)n0, (int)cnt, (int)nc, (int)p.ac_cap_rows, acstate + (size_t)clr * B * 8 };
-                        if (anchors) ac_decode_anchor_kernel<<<B, 64, 0, qs>>>(tab, slots + p.slot_off[(size_t)st * B], in_stride_slots, ck, o);
-                        else ac_decode_kernel<<<B, 64, 0, qs>>>((const uint16_t *)tab, 0, row_stride, slots + p.slot_off[(size_t)st * B], in_stride_slots, ck, o);
-                        if (C > 1 && clr < 2) HIPCHK(hipEventRecord(c->ev_ac[clr][ch], qs));
-                    }
-                }
-                if (C > 1) {
-                    for (int k = 1; k < 3; ++k) {
-                        HIPCHK(hipEventRecord(c->ev_ac_end[k - 1], q[k]));
-                        HIPCHK(hipStreamWaitEvent(s, c->ev_ac_end[k - 1], 0));
-                    }
-                }
-            }
-            if (sink.kind == DecodeSink::Transcode) {
-                // (the reference format's colour queues have been joined back onto `s` above; the next band's CNN launch, which overwrites
-                // `params`, follows on `s`)
-                const Plan &q = sink.target->p;
-                const int k = lvl * 3 + band;
-                ProfSpan span(c, PROF_PAIRS, s);
-                cdf_pairs_kernel<<<dim3((unsigned)((q.lev_maxpos[lvl] + kPairsThreads - 1) / kPairsThreads), B), kPairsThreads, 0, s>>>(
-                    planes, params, mm, q.sg[(size_t)k * B], sink.target->dev<StageGeom>(q.d_sg) + (size_t)k * B,
-                    (uint32_t *)(sink.target_ws + q.off_pairs) + q.pair_base[k]);
-                HIPCHK(hipGetLastError());
-            }
+            const TileRun *tr = &lr.run[band];
+            if (int rc = launch_band_params(c, w.fplanes, g, band, w.params, s, lr.gv, lr.tiles ? lr.tiles + tr->off : nullptr, tr)) return rc;
+            if (M > 0) rans_stage(c, p, w, lvl, band, lr, s);
+            else if (int rc = ac_stage(c, p, w, g, lvl, band, s)) return rc;
+            if (sink.kind == DecodeSink::Transcode) if (int rc = transcode_tap(c, w, sink, B, lvl, band, s)) return rc;
         }
     }
-    return launch_sink(c, pd, sink, ws, s, reduce, rv);
+    return launch_sink(c, p, w, sink, s, run);
 }
 
 // Room for the per-image status words of a call on B images in the context's own copy (llicti_image_status); none are valid until the call has run
@@ -1313,67 +1356,62 @@ static int reserve_img_status(llicti_ctx *c, int B)
     return 0;
 }
 
-// rgb_off: the images' placement in a Planar sink's buffer (NULL: tight, and for every other kind)
-static int decode_batch(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len, int B, const int *Hs, const int *Ws,
-                        const int *modes, int n_modes, void *d_workspace, size_t workspace_bytes, const size_t *rgb_off, void *stream, int reduce, DecodeSink sink,
-                        const int *reduces = nullptr)
+static int decode_batch(llicti_ctx *c, const DecodeCall &a, DecodeSink sink)
 {
-    // reduces (the _rv calls, values that differ): B per-image values in the place of `reduce`; rgb_off then places the images at their own reduced sizes
+    const int B = a.B, *Hs = a.Hs, *Ws = a.Ws;
+    const Reduces &rd = a.rd;
     const bool own_out = sink.kind == DecodeSink::Views;      // (every group has its own output)
-    if (!c || !d_in || !d_seg_len || !d_workspace || (!sink.d_out && !own_out)) return fail(LLICTI_EINVAL, "decode_images: null pointer");
-    if (reduce < 0 || reduce > c->nlev) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", reduce, c->nlev, c->nlev);
+    if (!c || !a.d_in || !a.d_seg_len || !a.d_workspace || (!sink.d_out && !own_out)) return fail(LLICTI_EINVAL, "decode_images: null pointer");
+    if (!rd.per_image() && (rd.r < 0 || rd.r > c->nlev)) return fail(LLICTI_EINVAL, "decode_images: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", rd.r, c->nlev, c->nlev);
     if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
     int ME = 0;
     std::vector<int> Ms;
-    if (int rc = resolve_modes("decode_images", modes, n_modes, B, &ME, Ms)) return rc;
+    if (int rc = resolve_modes("decode_images", a.modes, a.n_modes, B, &ME, Ms)) return rc;
     if (int rc = check_model(c->nlev, "decode_images", ME, Ms)) return rc;
     if (int rc = check_stream_bits("decode_images", c->nlev, B, Hs, Ws, ME, Ms)) return rc;
-    if (reduces) if (int rc = admit_reduces("decode_images", B, reduces, c->nlev, ME)) return rc;
-    if (int rc = resolve_sink(sink, B, Hs, Ws, reduce, reduces)) return rc;
+    if (rd.per_image()) if (int rc = admit_reduces("decode_images", B, rd.rv, c->nlev, ME)) return rc;
+    if (int rc = resolve_sink(sink, B, Hs, Ws, rd)) return rc;
     if (int rc = check_source_modes("decode_images", "container", ME)) return rc;
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)a.stream;
+    const std::vector<PixGeo> *pix = sink.kind == DecodeSink::Interleaved ? &sink.pix : nullptr;
     PlanDev *pd = nullptr;
     // (an _rv call: the batch's full-size plan with tight placement, whatever the values and the sink -- outputs and windows are per-call tables)
-    if (reduces) { if (int rc = get_plan(c, B, Hs, Ws, nullptr, ME, modes_ptr(Ms), s, &pd)) return rc; }
-    else if (int rc = get_plan(c, B, Hs, Ws, rgb_off, ME, modes_ptr(Ms), s, &pd, reduce, sink.kind == DecodeSink::Interleaved ? &sink.pix : nullptr)) return rc;
+    if (rd.per_image()) { if (int rc = get_plan(c, B, Hs, Ws, nullptr, ME, modes_ptr(Ms), s, &pd)) return rc; }
+    else if (int rc = get_plan(c, B, Hs, Ws, a.rgb_off, ME, modes_ptr(Ms), s, &pd, rd.r, pix)) return rc;
     PlanUse use{ pd, s };
     const Plan &p = pd->p;
     if (!p.uniform && p.M == 0) return fail(LLICTI_EINVAL, "decode_images: a batch of mixed sizes needs a rANS container (the reference-format container codes equal sizes per call)");
-    if (int rc = check_in_stride("decode_images", p.nlev, B, Hs, Ws, in_stride)) return rc;
-    if (workspace_bytes < p.total)
-        return fail(LLICTI_ENOSPACE, "decode_images: workspace %zu < %zu", workspace_bytes, p.total);
+    if (int rc = check_in_stride("decode_images", p.nlev, B, Hs, Ws, a.in_stride)) return rc;
+    if (a.workspace_bytes < p.total)
+        return fail(LLICTI_ENOSPACE, "decode_images: workspace %zu < %zu", a.workspace_bytes, p.total);
 
     if (int rc = reserve_img_status(c, B)) return rc;
     RvCall rv;
-    if (reduces) {
+    if (rd.per_image()) {      // rgb_off then places the images at their own reduced sizes
         rv.c = c; rv.s = s;
-        build_reduce_schedule(rv.q, p, reduces, sink.kind == DecodeSink::Planar ? rgb_off : nullptr, c->n_cu, c->cnn_tile_rows,
-                              sink.kind == DecodeSink::Interleaved ? &sink.pix : nullptr);
+        build_reduce_schedule(rv.q, p, rd.rv, sink.kind == DecodeSink::Planar ? a.rgb_off : nullptr, c->n_cu, c->cnn_tile_rows, pix);
         if (int rc = rv.upload()) return rc;
-        reduce = rv.q.rmin;
     }
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pd, d_in, in_stride, d_seg_len, (uint8_t *)d_workspace, s, reduce, sink, reduces ? &rv : nullptr)) return rc;
+    if (int rc = decode_stages(c, pd, a, (uint8_t *)a.d_workspace, s, rd.per_image() ? rv_run(pd, rv) : plan_run(pd, rd.r), sink)) return rc;
     c->img_status_n = B;
     return LLICTI_OK;
 }
-// a Planar sink into d_rgb
-static DecodeSink planar_sink(uint8_t *d_rgb) { DecodeSink k; k.d_out = d_rgb; return k; }
 
 extern "C" int llicti_decode_images_v(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
                                       int B, const int *Hs, const int *Ws, int mode, void *d_workspace, size_t workspace_bytes,
                                       uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, &mode, 1, d_workspace, workspace_bytes, rgb_off, stream, 0, planar_sink(d_rgb));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, &mode, 1, d_workspace, workspace_bytes, rgb_off, stream, 0 }, planar_sink(d_rgb));
 }
 
 extern "C" int llicti_decode_images_vm(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
                                        int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
                                        uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, rgb_off, stream, 0, planar_sink(d_rgb));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, rgb_off, stream, 0 }, planar_sink(d_rgb));
 }
 
 extern "C" int llicti_reduced_dims(int H, int W, int reduce, int *Hr, int *Wr)
@@ -1388,7 +1426,7 @@ extern "C" int llicti_decode_images_reduced(llicti_ctx *c, const uint8_t *d_in, 
                                             int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
                                             void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, rgb_off, stream, reduce, planar_sink(d_rgb));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, rgb_off, stream, reduce }, planar_sink(d_rgb));
 }
 
 extern "C" int llicti_pixel_bytes(int format) { return pix_format_bytes(format); }
@@ -1407,9 +1445,8 @@ extern "C" int llicti_decode_images_px(llicti_ctx *c, const uint8_t *d_in, size_
                                        void *d_workspace, size_t workspace_bytes,
                                        uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream)
 {
-    DecodeSink sink;
-    sink.kind = DecodeSink::Interleaved; sink.d_out = d_pix; sink.px = { format, px_off, pitch };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce },
+                        px_sink(d_pix, { format, px_off, pitch }));
 }
 
 extern "C" int llicti_tensor_elem_bytes(int dtype) { return tensor_elem_bytes(dtype); }
@@ -1423,9 +1460,8 @@ extern "C" int llicti_decode_images_tensor(llicti_ctx *c, const uint8_t *d_in, s
                                            void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
                                            const float *mean, const float *std, void *stream)
 {
-    DecodeSink sink;
-    sink.kind = DecodeSink::Tensor; sink.d_out = (uint8_t *)d_out; sink.tensor = { dtype, Ho, Wo, y0, x0, flip, mean, std };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce },
+                        tensor_sink(d_out, { dtype, Ho, Wo, y0, x0, flip, mean, std }));
 }
 
 extern "C" int llicti_resize_window_ok(int H, int W, int reduce, int y0, int x0, int hs, int ws, int Ho, int Wo, int antialias)
@@ -1446,9 +1482,8 @@ extern "C" int llicti_decode_images_tensor_resized(llicti_ctx *c, const uint8_t 
                                                    void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
                                                    const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream)
 {
-    DecodeSink sink;
-    sink.kind = DecodeSink::Resized; sink.d_out = (uint8_t *)d_out; sink.resize = { dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce },
+                        resized_sink(d_out, { dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias }));
 }
 
 // (the plan: the same one -- image indices, boxes and flips of every view are kernel arguments of the groups' launches)
@@ -1457,21 +1492,20 @@ extern "C" int llicti_decode_images_tensor_views(llicti_ctx *c, const uint8_t *d
                                                  void *d_workspace, size_t workspace_bytes,
                                                  const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream)
 {
-    DecodeSink sink;
-    sink.kind = DecodeSink::Views; sink.views = { groups, G, mean, std };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce, std::move(sink));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, reduce },
+                        views_sink({ groups, G, mean, std }));
 }
 
 // ------------------------------------------------------------------------------------------------ per-image reduce
-// The five _rv calls: the scalar sibling with `int reduce` replaced by B host values.  All equal: the call IS the sibling (it delegates: same
-// launches, plan key and counters).  Otherwise decode_batch runs the per-call schedule (host_plan.hpp: ReduceSchedule).
-// -> 0 and *equal, or the refusal of a null array / a value out of range
-static int rv_head(llicti_ctx *c, const char *who, int B, const int *reduces, bool *equal)
+// The five _rv calls: the scalar sibling with `int reduce` replaced by B host values.  All equal: the call IS the sibling's (the scalar Reduces:
+// same launches, plan key and counters).  Otherwise decode_batch runs the per-call schedule (host_plan.hpp: ReduceSchedule).
+// -> 0 and *rd, or the refusal of a null array / a value out of range
+static int rv_head(llicti_ctx *c, const char *who, int B, const int *reduces, Reduces *rd)
 {
     if (!c) return fail(LLICTI_EINVAL, "%s: null ctx", who);
     if (B < 1) return fail(LLICTI_EINVAL, "%s: bad batch: B=%d", who, B);
     if (int rc = admit_reduces(who, B, reduces, c->nlev, 1)) return rc;      // (the container kind is held against the modes in decode_batch)
-    *equal = reduces_equal(B, reduces);
+    *rd = reduces_equal(B, reduces) ? Reduces(reduces[0]) : Reduces::each(reduces);
     return 0;
 }
 
@@ -1479,10 +1513,9 @@ extern "C" int llicti_decode_images_reduced_rv(llicti_ctx *c, const uint8_t *d_i
                                                int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
                                                void *d_workspace, size_t workspace_bytes, uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
-    bool equal = false;
-    if (int rc = rv_head(c, "decode_images_reduced_rv", B, reduces, &equal)) return rc;
-    if (equal) return llicti_decode_images_reduced(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_rgb, rgb_off, stream);
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, rgb_off, stream, 0, planar_sink(d_rgb), reduces);
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_reduced_rv", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, rgb_off, stream, rd }, planar_sink(d_rgb));
 }
 
 extern "C" int llicti_decode_images_px_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
@@ -1490,12 +1523,10 @@ extern "C" int llicti_decode_images_px_rv(llicti_ctx *c, const uint8_t *d_in, si
                                           void *d_workspace, size_t workspace_bytes,
                                           uint8_t *d_pix, int format, const size_t *px_off, const size_t *pitch, void *stream)
 {
-    bool equal = false;
-    if (int rc = rv_head(c, "decode_images_px_rv", B, reduces, &equal)) return rc;
-    if (equal) return llicti_decode_images_px(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_pix, format, px_off, pitch, stream);
-    DecodeSink sink;
-    sink.kind = DecodeSink::Interleaved; sink.d_out = d_pix; sink.px = { format, px_off, pitch };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_px_rv", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
+                        px_sink(d_pix, { format, px_off, pitch }));
 }
 
 extern "C" int llicti_decode_images_tensor_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
@@ -1504,13 +1535,10 @@ extern "C" int llicti_decode_images_tensor_rv(llicti_ctx *c, const uint8_t *d_in
                                               void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
                                               const float *mean, const float *std, void *stream)
 {
-    bool equal = false;
-    if (int rc = rv_head(c, "decode_images_tensor_rv", B, reduces, &equal)) return rc;
-    if (equal) return llicti_decode_images_tensor(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_out, dtype, Ho, Wo,
-                                                  y0, x0, flip, mean, std, stream);
-    DecodeSink sink;
-    sink.kind = DecodeSink::Tensor; sink.d_out = (uint8_t *)d_out; sink.tensor = { dtype, Ho, Wo, y0, x0, flip, mean, std };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_tensor_rv", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
+                        tensor_sink(d_out, { dtype, Ho, Wo, y0, x0, flip, mean, std }));
 }
 
 extern "C" int llicti_decode_images_tensor_resized_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
@@ -1519,13 +1547,10 @@ extern "C" int llicti_decode_images_tensor_resized_rv(llicti_ctx *c, const uint8
                                                       void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
                                                       const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream)
 {
-    bool equal = false;
-    if (int rc = rv_head(c, "decode_images_tensor_resized_rv", B, reduces, &equal)) return rc;
-    if (equal) return llicti_decode_images_tensor_resized(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, d_out, dtype,
-                                                          Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias, stream);
-    DecodeSink sink;
-    sink.kind = DecodeSink::Resized; sink.d_out = (uint8_t *)d_out; sink.resize = { dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_tensor_resized_rv", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
+                        resized_sink(d_out, { dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias }));
 }
 
 extern "C" int llicti_decode_images_tensor_views_rv(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
@@ -1533,13 +1558,10 @@ extern "C" int llicti_decode_images_tensor_views_rv(llicti_ctx *c, const uint8_t
                                                     void *d_workspace, size_t workspace_bytes,
                                                     const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream)
 {
-    bool equal = false;
-    if (int rc = rv_head(c, "decode_images_tensor_views_rv", B, reduces, &equal)) return rc;
-    if (equal) return llicti_decode_images_tensor_views(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, reduces[0], d_workspace, workspace_bytes, groups, G,
-                                                        mean, std, stream);
-    DecodeSink sink;
-    sink.kind = DecodeSink::Views; sink.views = { groups, G, mean, std };
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, 0, std::move(sink), reduces);
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_tensor_views_rv", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
+                        views_sink({ groups, G, mean, std }));
 }
 
 extern "C" int llicti_encode_images_f32(llicti_ctx *c, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,
@@ -1555,7 +1577,7 @@ extern "C" int llicti_decode_images(llicti_ctx *c, const uint8_t *d_in, size_t i
 {
     if (check_dims(B, H, W)) return LLICTI_EINVAL;
     std::vector<int> Hs(B, H), Ws(B, W);
-    return decode_batch(c, d_in, in_stride, d_seg_len, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, nullptr, stream, 0, planar_sink(d_rgb));
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs.data(), Ws.data(), &mode, 1, d_workspace, workspace_bytes, nullptr, stream, 0 }, planar_sink(d_rgb));
 }
 
 // ------------------------------------------------------------------------------------------------ transcode
@@ -1614,10 +1636,11 @@ extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_
     uint8_t *ws = (uint8_t *)d_workspace;
     DecodeSink tc;
     tc.kind = DecodeSink::Transcode; tc.target = pdd; tc.target_ws = ws + lay.off_dst;
+    const DecodeCall src{ d_in, in_stride, d_seg_len_in, B, Hs, Ws, src_modes, n_src, d_workspace, workspace_bytes, nullptr, stream, 0 };
 
     if (int rc = reserve_img_status(c, B)) return rc;
     CallScope call(c, s);
-    if (int rc = decode_stages(c, pds, d_in, in_stride, d_seg_len_in, ws, s, 0, tc)) return rc;
+    if (int rc = decode_stages(c, pds, src, ws, s, plan_run(pds, 0), tc)) return rc;
     const int16_t *planes = (const int16_t *)(ws + ps.off_planes);
     const int32_t *mm = (const int32_t *)(ws + ps.off_minmax);
     int32_t *status_dst = (int32_t *)(tc.target_ws + pt.off_status);

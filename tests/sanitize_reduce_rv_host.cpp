@@ -7,6 +7,8 @@
 //     TileRun is choose_tile_form's over those images; levels below min(r) have no launch
 //   - every level's stream list is exactly those images' streams, in the order of the plan's stream table
 //   - the output table has reduced_dim(H_b, r_b) sizes (counted as numpy's [::2^r] counts them) and tight, disjoint offsets, or the caller's
+//   - equal values r >= 1: the output table, max_rplane and pix_units are plan_add_reduced's (+ plan_add_pixels') at r, tight or placed
+//   - every image active: build_tile_lists returns build_plan's lists and runs, and an all-zero schedule holds the same lists per (level, band)
 //   - the tables fit the device block, apart and in bounds (the block is allocated to the byte: ASan sees a write past it)
 //   - the refusals: a null array, a value out of range, differing values with a reference-format container -- each names the image
 #include <stdio.h>
@@ -22,7 +24,7 @@ static long n_checks = 0;
         if (!(c)) { fprintf(stderr, "FAILED %s (%s:%d)\n", #c, __FILE__, __LINE__); exit(1); } \
     } while (0)
 
-static long n_batches = 0, n_equal = 0, n_nonzero = 0;
+static long n_batches = 0, n_equal = 0, n_nonzero = 0, n_scalar_twin = 0, n_tile_twin = 0;
 
 static void drive(int B, const int *Hs, const int *Ws, int ME, const int *Ms, int nlev, bool ragged, const int *rv, bool placed, int n_cu, int tile_rows)
 {
@@ -53,6 +55,41 @@ static void drive(int B, const int *Hs, const int *Ws, int ME, const int *Ms, in
         max_rplane = std::max(max_rplane, (long)hr * wr);
     }
     REQUIRE(q.max_rplane == max_rplane);
+    // equal values r >= 1: the table, max_rplane and pix_units are those of the scalar call's plan (plan_add_reduced + plan_add_pixels at r)
+    if (reduces_equal(B, rv) && rv[0] >= 1) {
+        ++n_scalar_twin;
+        Plan ps;
+        build_plan(ps, PlanSpec{ B, Hs, Ws, ME, Ms, nlev, ragged, nullptr, n_cu, tile_rows });
+        plan_add_reduced(ps, rv[0], placed ? off.data() : nullptr);
+        std::vector<int> Hw(B), Ww(B);
+        for (int b = 0; b < B; ++b) { Hw[b] = reduced_dim(Hs[b], rv[0]); Ww[b] = reduced_dim(Ws[b], rv[0]); }
+        std::vector<PixGeo> pix;
+        REQUIRE(resolve_pixels("test", B, Hw.data(), Ww.data(), LLICTI_PIX_RGB8, nullptr, nullptr, pix) == 0);
+        plan_add_pixels(ps, pix);
+        REQUIRE((int)ps.red.size() == B && ps.max_rplane == q.max_rplane && ps.pix_units == q.pix_units);
+        for (int b = 0; b < B; ++b) REQUIRE(ps.red[b].off == q.red[b].off && ps.red[b].Hr == q.red[b].Hr && ps.red[b].Wr == q.red[b].Wr);
+    }
+    // every image active: the shared tile-list builder returns build_plan's lists and runs exactly (a mixed-size plan has them)
+    if (!p.uniform) {
+        ++n_tile_twin;
+        std::vector<TileRef> tiles;
+        TileRun run[LLICTI_NLEVELS * 3];
+        build_tile_lists(p.geo, B, 0, nlev, [](int, int) { return true; }, n_cu, tile_rows, tiles, run);
+        REQUIRE(tiles.size() == p.tiles.size());
+        for (size_t k = 0; k < tiles.size(); ++k) REQUIRE(tiles[k].img == p.tiles[k].img && tiles[k].yx == p.tiles[k].yx);
+        for (int k = 0; k < LLICTI_NLEVELS * 3; ++k)
+            REQUIRE(run[k].off == p.run[k].off && run[k].n_tiles == p.run[k].n_tiles && run[k].TH == p.run[k].TH && run[k].gx == p.run[k].gx);
+        // ... and at all-zero reduces the schedule's lists are the plan's, level by level (the schedule walks the levels downwards)
+        const std::vector<int> zero(B, 0);
+        ReduceSchedule qz;
+        build_reduce_schedule(qz, p, zero.data(), nullptr, n_cu, tile_rows);
+        REQUIRE(qz.tiles.size() == p.tiles.size());
+        for (int k = 0; k < nlev * 3; ++k) {
+            REQUIRE(qz.run[k].n_tiles == p.run[k].n_tiles && qz.run[k].TH == p.run[k].TH && qz.run[k].gx == p.run[k].gx);
+            for (int i = 0; i < p.run[k].n_tiles; ++i)
+                REQUIRE(qz.tiles[qz.run[k].off + i].img == p.tiles[p.run[k].off + i].img && qz.tiles[qz.run[k].off + i].yx == p.tiles[p.run[k].off + i].yx);
+        }
+    }
     // streams and tiles, level by level
     size_t s_total = 0, t_total = 0;
     for (int lvl = 0; lvl < LLICTI_NLEVELS; ++lvl) {
@@ -171,7 +208,7 @@ int main()
         const int tile_rows = (it % 11 == 0) ? 4 : (it % 13 == 0) ? 16 : 0;
         drive(B, Hs.data(), Ws.data(), ME, per_image ? Ms.data() : nullptr, nlev, !equal_sizes && it % 2 == 0, rv.data(), it % 10 == 0, n_cu, tile_rows);
     }
-    REQUIRE(n_equal > 100 && n_nonzero > 100);
+    REQUIRE(n_equal > 100 && n_nonzero > 100 && n_scalar_twin > 100 && n_tile_twin > 100);
     printf("per-image reduce schedules ok: %ld batches (%ld all equal, %ld without a level-0 image), %ld checks\n", n_batches, n_equal, n_nonzero, n_checks);
     return 0;
 }
