@@ -529,6 +529,74 @@ int llicti_pack_records(llicti_ctx *ctx, const uint8_t *d_cont, size_t stride, c
 int llicti_unpack_records(llicti_ctx *ctx, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off /* [B+1] */, int B,
                           uint8_t *d_cont, size_t stride, int32_t *d_seg_len /* [B][49] */, void *stream);
 
+/* PROGRESSIVE RECORDS: a second record layout beside .llic, a permutation of the same bytes, of which a decode at reduce = r needs one
+ * contiguous PREFIX.  A rANS stream's bit region is read downwards from its end, coarse stages first, so a decode that stops after level r has
+ * touched only the bytes from the main coder's cursor upwards (and the states above the region).  The streams of an image are cut at the
+ * level boundaries and the pieces stored level-major, the coarsest level first.  xwide v4 containers only (LLICTI_MODE_RANS_X, fixed or
+ * "auto" counts, both models): a stream of 64 / 128 lanes keeps its T field at its bottom.  The containers themselves do not change by a bit.
+ *
+ * CUTS.  L = the model's levels (5 / 2).  For stream m of an image, cur[m][l] = the main coder's bit cursor behind the last stage of level l;
+ * c[m][l] = cur[m][l] >> 3 for l = 1 .. L-1, c[m][0] = 0, c[m][L] = len_m (the stream's bytes).  The level-l PIECE of stream m is its bytes
+ * [c[m][l], c[m][l+1]): the cursors only move down, so the pieces tile the stream.  The level L-1 piece holds the states, the end marker and
+ * the 9-bit field; the level-0 piece the tail coder's spill.
+ *
+ * THE RECORD (little-endian).  P = the container's payload, its n segments back to back, S bytes; stream m occupies P[off_m : off_m + len_m]
+ * (M > 32: behind its segment's length table, as the decoder locates it).  The payload's bytes outside every stream are the FRAME bytes: the
+ * header segments first, then the length tables.
+ *   0        b"LLIP", u8 version = 1, u8 n (49 / 22), u8 L (5 / 2), u8 0, u16 M (1 .. 128), u16 0
+ *   12       u32 seg_len[n]                                   the plain record's
+ *   12+4n    per stream m: u32 off_m, u32 len_m, u32 c[m][1] .. c[m][L-1]                 (L + 1 words a stream)
+ *   T        the frame bytes, in payload order (F = S - sum len_m of them)                T = 12 + 4n + 4 M (L + 1)
+ *   T+F      the level L-1 pieces of streams 0 .. M-1, then level L-2, ..., then level 0
+ * Prefix lengths: P_r = T + F + sum over l >= r and m of (c[m][l+1] - c[m][l]); P_L = T + F (the header alone: the DC band), P_0 = T + S (the
+ * whole record).  The first P_r bytes hold everything a decode at reduce >= r reads.  A progressive record is a function of the plain record.
+ *
+ * llicti_level_cuts: the arguments of llicti_decode_images_vm with d_cuts -- int32 [B][128][LLICTI_NLEVELS], entry [b][m][l] = c[m][l] of image
+ * b -- in place of the output pixels (and of their placement).  Rows m >= the image's stream count and entry l = 0 are zero.  A full decode
+ * that writes no pixels: behind each level >= 1 one small kernel stores every stream's cursor; the tail coder runs, so the container's
+ * end-of-stream check does: llicti_image_status is a full decode's.  Asynchronous on `stream`; no synchronisation and no allocation on a
+ * warm context.  Modes that are not xwide v4 (64- / 128-lane streams, the reference format): LLICTI_EINVAL before anything is launched.
+ *
+ * llicti_pack_progressive: llicti_pack_records' contract (a scan on the device, then the copy) for progressive records: d_rec_off[b] = first
+ * byte of record b, d_rec_off[B] = the total; d_prefix int64 [B][LLICTI_NLEVELS + 1]: P_0 .. P_L of every image (entries above L: 0).
+ *   - an image whose lengths (a negative entry, a sum above `stride` or of 2^31 or more -- the table's words have 32 bits, and the unpack
+ *     refuses one of 2^31 or more --, header segments other than 3 / 12 / 2), header (not an xwide v4
+ *     container of the context's model), length tables (M = 64 / 128) or cuts (a row that does not ascend within len_m) do not hold together
+ *     gets a ZERO-LENGTH record, an all-zero prefix row and LLICTI_EFORMAT; its neighbours are unaffected
+ *   - a total above blob_cap latches LLICTI_ENOSPACE as llicti_pack_records does; nothing at or past blob_cap is written
+ *
+ * llicti_unpack_progressive: record b is the bytes d_blob + d_rec_off[b] .. d_rec_off[b + 1]: the prefix P_{reduce[b]} alone or anything
+ * longer (reduce: HOST array of B ints).  EVERYTHING IS VALIDATED ON THE DEVICE BEFORE A FRAME OR PIECE BYTE IS READ: offsets inside the blob;
+ * magic, version, n and L equal to the context's; the zero bytes; 1 <= M <= 128; every length below 2^31 and S <= stride; the streams ascending
+ * and disjoint inside [0, S); 0 <= c[m][1] <= ... <= c[m][L-1] <= len_m; 0 <= reduce[b] <= L; at least P_{reduce[b]} bytes present.
+ *   - a good record gives its seg_len row (zeros up to 49), and the frame bytes and the pieces of the levels >= reduce[b] at their payload
+ *     positions in d_cont + b * stride; EVERY OTHER BYTE OF THE CONTAINER IS LEFT AS IT WAS
+ *   - a refused record gets LLICTI_EFORMAT for its image, an all-zero seg_len row and an untouched container; its neighbours unpack
+ *   - no read leaves the blob, no write leaves [d_cont + b * stride, + stride)
+ *   - whether off_m / len_m agree with the container's own length tables is the decoder's check, as it is for a plain record
+ *   - a decode finer than reduce[b] reads stream bytes nobody delivered: garbage or LLICTI_EFORMAT, memory-safe as for any corrupt container.
+ *     The decoders parse the TOP of every stream whatever the reduce (rans_init_kernel: end marker and states), so at reduce[b] = L -- no
+ *     stream byte delivered -- an image is flagged where the container's old bytes leave a zero on top of a bit region
+ * Both calls are asynchronous on `stream` and neither allocates nor synchronises warm; the reduces travel as kernel arguments.  They report
+ * through the latched status as the record calls do.  LLICTI_EINVAL before anything is launched: as for the record calls, and a null or
+ * overlapping d_cuts / d_prefix.
+ *
+ * THE COPY of both calls: the record's dense side behind its table is cut into ranges of LLICTI_RECORD_CHUNK bytes, one workgroup each, so a
+ * record of a few huge pieces and one of 640 tiny ones load the chip alike; a workgroup finds the pieces its range overlaps from the record's
+ * own table and moves each overlap with 16-byte stores.  All offsets are 64-bit.
+ *
+ * llicti_progressive_prefix (host helper, no device): from the first `bytes` bytes of a record -- at least its table, T bytes -- the prefix
+ * lengths prefix[0 .. LLICTI_NLEVELS] (entries above the record's L: 0); LLICTI_EFORMAT for a head that breaks one of the rules above (the
+ * same code checks them on the device), whichever of the two models it names. */
+int llicti_level_cuts(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                      int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
+                      int32_t *d_cuts /* [B][128][LLICTI_NLEVELS] */, void *stream);
+int llicti_pack_progressive(llicti_ctx *ctx, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B, const int32_t *d_cuts,
+                            uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off /* [B+1] */, int64_t *d_prefix /* [B][LLICTI_NLEVELS+1] */, void *stream);
+int llicti_unpack_progressive(llicti_ctx *ctx, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off /* [B+1] */, int B,
+                              const int *reduce /* host, [B] */, uint8_t *d_cont, size_t stride, int32_t *d_seg_len /* [B][49] */, void *stream);
+int llicti_progressive_prefix(const uint8_t *head, size_t bytes, int64_t *prefix /* [LLICTI_NLEVELS+1] */);
+
 /* Where llicti_encode_images / llicti_decode_images of B images of H x W in `mode` keep the YCoCg-R planes inside the caller's workspace
  * (byte offsets): int16 [B][3][H][W] (Y - 127, Co, Cg) and float32 [B][3][H][W] = planes / 255 -- the second is the `x_ycocg` the
  * reference's compress() returns beside the streams (LLICTI_nets.py:143-144, :159), so a caller that wants it reads it from the workspace

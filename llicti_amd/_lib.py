@@ -120,6 +120,10 @@ _SIGS = {
     "llicti_record_bytes_n": (_sz, [_i, _vp]),
     "llicti_pack_records": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz, _vp, _vp]),
     "llicti_unpack_records": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _sz, _vp, _vp]),
+    "llicti_level_cuts": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "llicti_pack_progressive": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "llicti_unpack_progressive": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
+    "llicti_progressive_prefix": (_i, [_vp, _sz, _vp]),
     "llicti_encode_images": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "llicti_check_status": (_i, [_vp, _vp]),

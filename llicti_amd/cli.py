@@ -4,7 +4,8 @@
    python -m llicti_amd.cli transcode IN.llic OUT.llic [--container ac|auto|rans<M>|wrans<M>|xrans<M>] [--checkpoint model_best.pth.tar] [--config llicti_B.json]
    python -m llicti_amd.cli info   IN.llic | ARCHIVE.llia
    python -m llicti_amd.cli pack   ARCHIVE.llia SRC... [--container ...] [--checkpoint ...] [--config ...] [--batch N]
-   python -m llicti_amd.cli unpack ARCHIVE.llia DIR [--as llic|png|ppm] [--checkpoint ...] [--config ...] [--batch N]
+   python -m llicti_amd.cli pack   --progressive ARCHIVE.llpa IMAGE... --container auto|xrans<M> [--checkpoint ...] [--config ...] [--batch N]
+   python -m llicti_amd.cli unpack ARCHIVE.llia|ARCHIVE.llpa DIR [--as llic|png|ppm] [--checkpoint ...] [--config ...] [--batch N]
 
 File-level front end of the MI355X hot path (needs a GPU: there is no CPU fallback).  Without a checkpoint the
 seed-1337 default init is used, as the reference does when `model_best.pth.tar` is missing (agents/base.py:78-80).  --config names the
@@ -16,7 +17,10 @@ from the coarse levels alone -- a decimation without smoothing, so fine texture 
 are made (it needs the model the file was written with, like decode).  pack writes an image archive (llicti_amd/archive.py): SRC are images, coded
 in batches of --batch (one encode, one on-device pack of the records and one dense download per batch), or .llic files, taken as they are; unpack
 writes every image of an archive into DIR under its name, as the .llic file it holds (no GPU) or decoded to png / ppm (one dense upload, one
-on-device unpack and one decode per batch); info on an archive lists its images."""
+on-device unpack and one decode per batch); info on an archive lists its images.  pack --progressive writes a `.llpa` archive of progressive
+records (llicti_amd/progressive.py: the same bytes level-major, so that a reduced decode reads a prefix of a record alone; it costs one decode
+per batch on top of the encode) -- xwide containers only; info on one prints every image's prefix lengths P_r; unpack --as llic turns its
+records back into .llic files on the host."""
 from __future__ import annotations
 
 import argparse
@@ -61,6 +65,7 @@ def build_parser():
     p = sub.add_parser("pack"); p.add_argument("archive"); p.add_argument("src", nargs="+")
     p.add_argument("--container", default="ac"); p.add_argument("--checkpoint", default=None); p.add_argument("--config", default=None)
     p.add_argument("--batch", type=_batch_arg, default=24, metavar="N", help="images per batched encode")
+    p.add_argument("--progressive", action="store_true", help="write a .llpa archive of progressive records (xwide containers: --container auto or xrans<M>)")
     u = sub.add_parser("unpack"); u.add_argument("archive"); u.add_argument("dir")
     u.add_argument("--as", dest="fmt", choices=("llic", "png", "ppm"), default="llic")
     u.add_argument("--checkpoint", default=None); u.add_argument("--config", default=None)
@@ -75,14 +80,87 @@ def _batch_arg(v):
     return n
 
 
-def _is_archive(path):
+def _archive_kind(path):
+    """b"LLIA" / b"LLPA" for an archive of plain / progressive records, None for anything else"""
     from .archive import MAGIC, TRAILER_BYTES
+    from .progressive import ARCHIVE_MAGIC
     with open(path, "rb") as fh:
         size = fh.seek(0, 2)
         if size < TRAILER_BYTES:
-            return False
+            return None
         fh.seek(size - TRAILER_BYTES)
-        return fh.read(4) == MAGIC
+        magic = fh.read(4)
+        return magic if magic in (MAGIC, ARCHIVE_MAGIC) else None
+
+
+def _is_archive(path):
+    from .archive import MAGIC
+    return _archive_kind(path) == MAGIC
+
+
+def progressive_container_ok(name) -> bool:
+    """pack --progressive takes the containers whose streams are xwide: "auto" and "xrans<M>\""""
+    return name == "auto" or (name.startswith("xrans") and name[5:].isdigit())
+
+
+def _info_progressive(path):
+    from .codec import name_of_mode
+    from .progressive import ProgressiveReader
+    with ProgressiveReader(path) as ar:
+        print(f"{path}: {len(ar)} images, n = {ar.nseg} segments per record, {ar.total_bytes} bytes of progressive records")
+        for k in range(len(ar)):
+            (H, W), pre = ar.sizes[k], [int(v) for v in ar.prefix[k]]
+            print(f"  {ar.names[k]}: {W}x{H}, container {name_of_mode(ar.modes[k])}, {pre[0]} bytes, {8.0 * pre[0] / (H * W):.4f} bpp; prefix bytes "
+                  + ", ".join(f"P_{r}={v}" for r, v in enumerate(pre)))
+    return 0
+
+
+def _pack_progressive(a):
+    import os
+    from . import fileio
+    from .progressive import ProgressiveWriter
+    if not progressive_container_ok(a.container):
+        print(f"pack --progressive: container {a.container!r} has no xwide streams; progressive records need --container auto (or xrans<M>)", file=sys.stderr)
+        return 2
+    if any(s.lower().endswith(".llic") for s in a.src):
+        print("pack --progressive takes images: a .llic file's level cuts come from a decode (transcode it, or pack the image)", file=sys.stderr)
+        return 2
+    names = [os.path.splitext(os.path.basename(s))[0] for s in a.src]
+    model, torch = _model(a.container, a.checkpoint, a.config)
+    t0, total = time.time(), 0
+    with ProgressiveWriter(a.archive, model.codec().nseg) as aw:
+        for g0 in range(0, len(a.src), a.batch):
+            g1 = min(len(a.src), g0 + a.batch)
+            imgs = [fileio.read_image(s, layout="hwc") for s in a.src[g0:g1]]
+            blob, rec_off, _ = model.encode_batch_async(imgs, pixels="rgb").records(progressive=True)
+            aw.append_records(blob, rec_off, names[g0:g1])
+            total += int(rec_off[-1])
+    print(f"{len(a.src)} images -> {a.archive}: {total} bytes of progressive records, {time.time() - t0:.3f} s")
+    return 0
+
+
+def _unpack_progressive(a):
+    import os
+    from . import fileio
+    from .progressive import ProgressiveReader, to_llic
+    os.makedirs(a.dir, exist_ok=True)
+    t0 = time.time()
+    with ProgressiveReader(a.archive) as ar:
+        names = [os.path.basename(n) or str(k) for k, n in enumerate(ar.names)]
+        if a.fmt == "llic":                                  # (on the host: no GPU)
+            for k in range(len(ar)):
+                with open(os.path.join(a.dir, names[k] + ".llic"), "wb") as fh:
+                    fh.write(to_llic(ar.record(k)))
+        else:
+            model, torch = _model("ac", a.checkpoint, a.config)
+            for g0 in range(0, len(ar), a.batch):
+                g1 = min(len(ar), g0 + a.batch)
+                outs = model.decode_batch_async(ar.read_batch(range(g0, g1)), torch.device("cuda:0"), pixels="rgb")
+                model.codec().check()
+                for k, hwc in zip(range(g0, g1), outs):
+                    fileio.write_image(os.path.join(a.dir, names[k] + "." + a.fmt), hwc.cpu().numpy(), layout="hwc")
+        print(f"{a.archive} -> {a.dir}: {len(ar)} images as {a.fmt}, {time.time() - t0:.3f} s")
+    return 0
 
 
 def _groups(keys, limit):
@@ -168,10 +246,13 @@ def _unpack(a):
 def main(argv=None):
     a = build_parser().parse_args(argv)
     from . import fileio
+    from .progressive import ARCHIVE_MAGIC
     if a.cmd == "pack":
-        return _pack(a)
+        return _pack_progressive(a) if a.progressive else _pack(a)
     if a.cmd == "unpack":
-        return _unpack(a)
+        return _unpack_progressive(a) if _archive_kind(a.archive) == ARCHIVE_MAGIC else _unpack(a)
+    if a.cmd == "info" and _archive_kind(a.src) == ARCHIVE_MAGIC:
+        return _info_progressive(a.src)
     if a.cmd == "info" and _is_archive(a.src):
         return _info_archive(a.src)
     if a.cmd == "info":

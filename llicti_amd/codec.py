@@ -22,6 +22,8 @@ MODE_AC = 0                      # the reference's container: 45 torchac-algorit
 MODELS = {88: 5, 60: 2}          # head width -> wavelet levels: config A, config B (configs/llicti_{A,B}.json)
 B_MAX_STREAMS = 18               # config B: xwide streams per image (one per container segment; 9 x 2 levels)
 B_MAX_AUTO = 13                  # ... and the largest size-rule count of its "auto" mode (auto_counts(13)[-1] = 18)
+NLEVELS_MAX = 5                  # LLICTI_NLEVELS: the level axis of the C-ABI's per-level tables (config B uses the first 2)
+PROG_MAX_STREAMS = 128           # rows of llicti_level_cuts' table: the streams of an image
 
 
 # ---- container "auto": a PURE FUNCTION OF THE IMAGE'S SIZE (round 6).  Round 5's rule also looked at the batch size, the compute-unit count and -- through a
@@ -1026,6 +1028,80 @@ class HipCodec:
         assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
         _lib.check(self.L.llicti_unpack_records(self.ctx, C.c_void_p(blob.data_ptr()), blob.numel(), _ptr(ro_d), B,
                                                 C.c_void_p(out.data_ptr()), cstride, _ptr(seg_len), _stream_ptr(self.device)))
+        return out, seg_len
+
+    # ---- progressive records (llicti_level_cuts / llicti_pack_progressive / llicti_unpack_progressive): the same bytes level-major, so that a
+    # decode at reduce = r needs a prefix of the record alone (llicti_amd/progressive.py states the format)
+    def level_cuts(self, containers, seg_len, Hs, Ws, mode, out=None):
+        """device xwide v4 containers of B images (mode: one, or one per image -- what container_modes gives) -> int32 device tensor
+        [B, 128, 5]: entry [b, m, l] the byte of stream m at which the main coder's cursor stands behind level l (l >= 1; row m >= the image's
+        stream count and l = 0: zero).  A full decode without pixels, async; check() / image_status() are a full decode's."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        assert containers.shape[0] == B and containers.dtype == torch.uint8 and containers.is_cuda
+        ws = self.workspace_v(Hs, Ws, mode)
+        modes = np.ascontiguousarray(np.broadcast_to(np.asarray(mode, dtype=np.int32), (B,)))
+        if out is None:
+            out = torch.empty((B, PROG_MAX_STREAMS, NLEVELS_MAX), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_cuda and tuple(out.shape) == (B, PROG_MAX_STREAMS, NLEVELS_MAX) and out.is_contiguous()
+        cstride = int(containers.stride(0)) if B > 1 else int(containers.shape[1])
+        _lib.check(self.L.llicti_level_cuts(self.ctx, C.c_void_p(containers.data_ptr()), cstride, _ptr(seg_len), B, _ptr(Hs), _ptr(Ws), _ptr(modes),
+                                            _ptr(ws), ws.numel(), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def pack_progressive(self, containers, seg_len, cuts, out=None, rec_off=None, prefix=None):
+        """device containers + seg_len + level_cuts' table -> (blob, rec_off, prefix): the images' progressive records back to back from
+        blob[0], their offsets (int64 [B + 1]) and every image's prefix lengths P_0 .. P_L (int64 [B, 6]; entries above the model's L: 0), all
+        on the device, async.  pack_records' contract: out's numel is the capacity (None: the worst case), ENOSPACE / EFORMAT as there; an
+        image whose header, lengths, length tables or cuts do not hold together gets a zero-length record."""
+        assert containers.dtype == torch.uint8 and containers.is_cuda and containers.dim() == 2 and containers.stride(1) == 1
+        B, stride = int(containers.shape[0]), int(containers.stride(0)) if containers.shape[0] > 1 else int(containers.shape[1])
+        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
+        assert cuts.dtype == torch.int32 and cuts.is_cuda and tuple(cuts.shape) == (B, PROG_MAX_STREAMS, NLEVELS_MAX) and cuts.is_contiguous()
+        if out is None:
+            out = torch.empty((B * (12 + 4 * self.nseg + 4 * PROG_MAX_STREAMS * (self.nlevels + 1) + int(containers.shape[1])),), dtype=torch.uint8, device=self.device)
+        if rec_off is None:
+            rec_off = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        if prefix is None:
+            prefix = torch.empty((B, NLEVELS_MAX + 1), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1 and out.stride(0) == 1
+        assert rec_off.dtype == torch.int64 and rec_off.is_cuda and rec_off.numel() == B + 1 and rec_off.is_contiguous()
+        assert prefix.dtype == torch.int64 and prefix.is_cuda and tuple(prefix.shape) == (B, NLEVELS_MAX + 1) and prefix.is_contiguous()
+        _lib.check(self.L.llicti_pack_progressive(self.ctx, C.c_void_p(containers.data_ptr()), stride, _ptr(seg_len), B, _ptr(cuts),
+                                                  C.c_void_p(out.data_ptr()), out.numel(), _ptr(rec_off), _ptr(prefix), _stream_ptr(self.device)))
+        return out, rec_off, prefix
+
+    def unpack_progressive(self, blob, rec_off, reduce=0, stride=None, out=None, seg_len=None):
+        """blob (flat uint8 device tensor) + rec_off ([B + 1] int64 offsets: record b is blob[rec_off[b]:rec_off[b + 1]], the prefix P_{r_b} of a
+        progressive record or anything longer) + reduce (one int, or one per image) -> (containers uint8 [B, stride], seg_len int32 [B, 49]),
+        async: the frame bytes and the pieces of the levels >= r_b at their places, every other byte of `out` as it was.  Everything is
+        validated on the device first; a refused record gives EFORMAT, a zero seg_len row and an untouched container.  out=None: a new,
+        uninitialised tensor as unpack_records makes -- but for the images with r_b = L, whose rows are filled with 0x80: the decoders parse the
+        top of every stream whatever the reduce, a zero there is an EFORMAT, and at r_b < L that top is among the delivered bytes; stride as
+        unpack_records -- with no `out` the caller gives it: a prefix does not say how long the payload is."""
+        assert blob.dtype == torch.uint8 and blob.is_cuda and blob.dim() == 1 and blob.stride(0) == 1
+        if isinstance(rec_off, torch.Tensor) and rec_off.is_cuda:
+            ro_d = rec_off
+        else:
+            ro_h = np.ascontiguousarray(rec_off.numpy() if isinstance(rec_off, torch.Tensor) else rec_off, dtype=np.int64)
+            ro_d = torch.from_numpy(ro_h).to(self.device, non_blocking=True)
+        assert ro_d.dtype == torch.int64 and ro_d.dim() == 1 and ro_d.numel() >= 2 and ro_d.is_contiguous()
+        B = ro_d.numel() - 1
+        if out is None:
+            if stride is None:
+                raise ValueError("unpack_progressive: the caller gives stride (or out)")
+            out = torch.empty((B, int(stride)), dtype=torch.uint8, device=self.device)
+            for b, r in enumerate(np.broadcast_to(np.asarray(reduce), (B,))):
+                if int(r) >= self.nlevels:           # (no stream byte is delivered: the one case in which old bytes meet the decoders' parser)
+                    out[b].fill_(0x80)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1
+        cstride = int(out.stride(0)) if B > 1 else int(out.shape[1])
+        if seg_len is None:
+            seg_len = torch.empty((B, NSEG), dtype=torch.int32, device=self.device)
+        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
+        red = np.ascontiguousarray(np.broadcast_to(np.asarray(reduce, dtype=np.int32), (B,)))
+        _lib.check(self.L.llicti_unpack_progressive(self.ctx, C.c_void_p(blob.data_ptr()), blob.numel(), _ptr(ro_d), B, _ptr(red),
+                                                    C.c_void_p(out.data_ptr()), cstride, _ptr(seg_len), _stream_ptr(self.device)))
         return out, seg_len
 
     def container_modes(self, containers):

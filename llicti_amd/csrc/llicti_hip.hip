@@ -20,6 +20,7 @@
 //   rans_tail_kernel<Q>               the serial tail coder behind the lanes' initial states      (latency bound)
 //   header / pack / unpack kernels    container assembly in HBM
 //   record_* kernels                  strided containers <-> one dense blob of .llic records: validation + a realigning 16-byte copy (HBM bound)
+//   level_cuts / prog_* kernels       progressive records: the level cuts of a decode, validation + a piecewise copy in level-major order (HBM bound)
 //
 // No CPU path exists in this library: every entry point needs a gfx950 device.
 #include <hip/hip_runtime.h>
@@ -50,6 +51,7 @@ using namespace llicti;
 #include "rans_coder.hpp"
 #include "container.hpp"
 #include "records.hpp"
+#include "records_progressive.hpp"
 #include "host_plan.hpp"
 
 // ------------------------------------------------------------------------------------------------ context
@@ -1020,7 +1022,7 @@ struct DecodeCall {
 // decode_batch validates that against the call's images (resolve_sink: the kind's payload, which is all launch_sink reads) -- reduced planar
 // output is Planar at reduce > 0.
 struct DecodeSink {
-    enum Kind { Planar, Interleaved, Tensor, Resized, Views, Transcode } kind = Planar;
+    enum Kind { Planar, Interleaved, Tensor, Resized, Views, Transcode, Cuts } kind = Planar;
     uint8_t *d_out = nullptr;               // the caller's buffer (Views: none, every group has its own)
     // as the caller gave them
     PixArgs px{};                           // Interleaved
@@ -1036,12 +1038,15 @@ struct DecodeSink {
     // behind every (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
     PlanDev *target = nullptr;
     uint8_t *target_ws = nullptr;
+    // Cuts (llicti_level_cuts): d_out is the call's int32 [B][128][LLICTI_NLEVELS] table.  decode_stages zeroes it and writes every stream's byte
+    // cursor behind each level >= 1 (level_cuts_kernel); no pixels -- the sink latches the status words alone.
 };
 static DecodeSink planar_sink(uint8_t *d_rgb) { DecodeSink k; k.d_out = d_rgb; return k; }
 static DecodeSink px_sink(uint8_t *d_pix, const PixArgs &px) { DecodeSink k; k.kind = DecodeSink::Interleaved; k.d_out = d_pix; k.px = px; return k; }
 static DecodeSink tensor_sink(void *d_out, const TensorArgs &t) { DecodeSink k; k.kind = DecodeSink::Tensor; k.d_out = (uint8_t *)d_out; k.tensor = t; return k; }
 static DecodeSink resized_sink(void *d_out, const ResizeArgs &t) { DecodeSink k; k.kind = DecodeSink::Resized; k.d_out = (uint8_t *)d_out; k.resize = t; return k; }
 static DecodeSink views_sink(const ViewArgs &a) { DecodeSink k; k.kind = DecodeSink::Views; k.views = a; return k; }
+static DecodeSink cuts_sink(int32_t *d_cuts) { DecodeSink k; k.kind = DecodeSink::Cuts; k.d_out = (uint8_t *)d_cuts; return k; }
 
 static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, const Reduces &rd)
 {
@@ -1134,6 +1139,9 @@ static int launch_sink(llicti_ctx *c, const Plan &p, const DecodeBufs &w, const 
     if (k.kind == DecodeSink::Transcode) return 0;      // (no pixels: the caller goes on with the target's header and coder, and latches the status words itself)
     ProfSpan span(c, PROF_MISC, s);
     switch (k.kind) {
+    case DecodeSink::Cuts:
+        level_cuts_latch_kernel<<<1, 256, 0, s>>>(w.status, kStatusHead, c->d_status, c->d_img_status, B);
+        break;
     case DecodeSink::Tensor: {
         // full size or reduced: the windows are this call's kernel arguments, kTensorWinMax images per launch; every launch latches its own
         // images' status words, the first one the call's
@@ -1326,6 +1334,8 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const DecodeCall &a, uint8_
     const DecodeBufs w(pd, ws);
     if (int rc = decode_prologue(c, pd, w, a, s)) return rc;
     if (run.rtab && M == 0) return fail(LLICTI_EINVAL, "decode_images: per-image reduces need rANS containers");
+    int32_t *cuts = sink.kind == DecodeSink::Cuts ? (int32_t *)sink.d_out : nullptr;
+    if (cuts) HIPCHK(hipMemsetAsync(cuts, 0, (size_t)B * kProgMaxStreams * LLICTI_NLEVELS * sizeof(int32_t), s));
     for (int lvl = p.nlev - 1; lvl >= run.stop; --lvl) {
         const Geom &g = p.geo[(size_t)lvl * B];                         // image 0's (equal sizes: every image's)
         const LevelRun &lr = run.lev[lvl];
@@ -1337,6 +1347,7 @@ static int decode_stages(llicti_ctx *c, PlanDev *pd, const DecodeCall &a, uint8_
             else if (int rc = ac_stage(c, p, w, g, lvl, band, s)) return rc;
             if (sink.kind == DecodeSink::Transcode) if (int rc = transcode_tap(c, w, sink, B, lvl, band, s)) return rc;
         }
+        if (cuts && lvl >= 1) level_cuts_kernel<<<(lr.NS + 255) / 256, 256, 0, s>>>(w.rpos, w.d_sref, lr.NS, lvl, cuts);
     }
     return launch_sink(c, p, w, sink, s, run);
 }
@@ -1372,6 +1383,8 @@ static int decode_batch(llicti_ctx *c, const DecodeCall &a, DecodeSink sink)
     if (rd.per_image()) if (int rc = admit_reduces("decode_images", B, rd.rv, c->nlev, ME)) return rc;
     if (int rc = resolve_sink(sink, B, Hs, Ws, rd)) return rc;
     if (int rc = check_source_modes("decode_images", "container", ME)) return rc;
+    if (sink.kind == DecodeSink::Cuts && ((ME & 0xFF) == 0 || ((ME >> 8) & 3) != 2))
+        return fail(LLICTI_EINVAL, "level_cuts: progressive records hold xwide v4 streams (LLICTI_MODE_RANS_X): a stream of 64 / 128 lanes keeps its T field at its bottom, the reference format has no cursor");
     for (int b = 0; b < 3; ++b) if (!c->have[b]) return fail(LLICTI_ENOWEIGHTS, "band %d weights not set", b);
     DeviceGuard guard(c);
     hipStream_t s = (hipStream_t)a.stream;
@@ -1412,6 +1425,13 @@ extern "C" int llicti_decode_images_vm(llicti_ctx *c, const uint8_t *d_in, size_
                                        uint8_t *d_rgb, const size_t *rgb_off, void *stream)
 {
     return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, rgb_off, stream, 0 }, planar_sink(d_rgb));
+}
+
+extern "C" int llicti_level_cuts(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                 int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
+                                 int32_t *d_cuts, void *stream)
+{
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, B, d_workspace, workspace_bytes, nullptr, stream, 0 }, cuts_sink(d_cuts));
 }
 
 extern "C" int llicti_reduced_dims(int H, int W, int reduce, int *Hr, int *Wr)
@@ -1733,6 +1753,68 @@ extern "C" int llicti_unpack_records(llicti_ctx *c, const uint8_t *d_blob, size_
     if (int rc = reserve_img_status(c, B)) return rc;
     record_check_kernel<<<B, 64, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, n, (long)stride, d_seg_len, c->d_status, c->d_img_status);
     record_unpack_kernel<<<record_grid(max_payload, B), kRecThreads, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, B, n, d_cont, (long)stride, c->d_img_status);
+    HIPCHK(hipGetLastError());
+    c->img_status_n = B;
+    return LLICTI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ progressive records
+extern "C" int llicti_progressive_prefix(const uint8_t *head, size_t bytes, int64_t *prefix)
+{
+    if (!head || !prefix) return fail(LLICTI_EINVAL, "progressive_prefix: null pointer");
+    ProgHead h;
+    if (!prog_check(head, (long)std::min<size_t>(bytes, (size_t)1 << 62), 0, 0, -1, &h, prefix))
+        return fail(LLICTI_EFORMAT, "progressive_prefix: not the head of a progressive record (magic, version, model, stream count, a length of 2^31 or more, "
+                    "streams that overlap or leave the payload, cuts that do not ascend within their stream, or fewer bytes than the table)");
+    return LLICTI_OK;
+}
+
+extern "C" int llicti_pack_progressive(llicti_ctx *c, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B, const int32_t *d_cuts,
+                                       uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off, int64_t *d_prefix, void *stream)
+{
+    if (int rc = admit_records("pack_progressive", c, d_cont, stride, d_seg_len, B, d_blob, blob_cap, d_rec_off)) return rc;
+    if (!d_cuts || !d_prefix) return fail(LLICTI_EINVAL, "pack_progressive: null pointer");
+    const size_t cuts_bytes = (size_t)B * kProgMaxStreams * LLICTI_NLEVELS * sizeof(int32_t), prefix_bytes = (size_t)B * (LLICTI_NLEVELS + 1) * sizeof(int64_t);
+    if (ranges_overlap(d_blob, blob_cap, d_cuts, cuts_bytes) || ranges_overlap(d_blob, blob_cap, d_prefix, prefix_bytes) ||
+        ranges_overlap(d_prefix, prefix_bytes, d_cuts, cuts_bytes) || ranges_overlap(d_prefix, prefix_bytes, d_cont, (size_t)B * stride) ||
+        ranges_overlap(d_prefix, prefix_bytes, d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t)) || ranges_overlap(d_prefix, prefix_bytes, d_rec_off, ((size_t)B + 1) * sizeof(int64_t)))
+        return fail(LLICTI_EINVAL, "pack_progressive: the cuts or the prefix table overlap another buffer of the call");
+    const int n = 4 + 9 * c->nlev;
+    if ((stride + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "pack_progressive: stride %zu", stride);
+    DeviceGuard guard(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = reserve_img_status(c, B)) return rc;
+    prog_measure_kernel<<<B, kProgThreads, 0, s>>>(d_cont, (long)stride, d_seg_len, n, c->nlev, d_cuts, d_prefix, c->d_status, c->d_img_status);
+    prog_scan_kernel<<<1, kRecThreads, 0, s>>>(d_prefix, B, (long)blob_cap, d_rec_off, c->d_status);
+    prog_head_kernel<<<B, kProgThreads, 0, s>>>(d_cont, (long)stride, d_seg_len, n, c->nlev, d_cuts, d_blob, (long)blob_cap, d_rec_off);
+    ProgReduces none;
+    memset(&none, 0, sizeof none);
+    prog_copy_kernel<true><<<record_grid(stride, B), kRecThreads, 0, s>>>(d_blob, (long)blob_cap, d_rec_off, 0, B, none, const_cast<uint8_t *>(d_cont), (long)stride, c->d_img_status);
+    HIPCHK(hipGetLastError());
+    c->img_status_n = B;
+    return LLICTI_OK;
+}
+
+extern "C" int llicti_unpack_progressive(llicti_ctx *c, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off, int B, const int *reduce,
+                                         uint8_t *d_cont, size_t stride, int32_t *d_seg_len, void *stream)
+{
+    if (int rc = admit_records("unpack_progressive", c, d_cont, stride, d_seg_len, B, d_blob, blob_bytes, d_rec_off)) return rc;
+    if (!reduce) return fail(LLICTI_EINVAL, "unpack_progressive: null pointer");
+    const int n = 4 + 9 * c->nlev;
+    const size_t max_dense = std::min(stride, blob_bytes);
+    if ((max_dense + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "unpack_progressive: stride %zu", stride);
+    DeviceGuard guard(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = reserve_img_status(c, B)) return rc;
+    // the reduces are kernel arguments, kProgReduceMax images a launch (a value outside 0 .. 15 travels as 15: the device check refuses it)
+    for (int b0 = 0; b0 < B; b0 += kProgReduceMax) {
+        const int nb = std::min(kProgReduceMax, B - b0);
+        ProgReduces red;
+        memset(&red, 0, sizeof red);
+        for (int i = 0; i < nb; ++i) red.w[i >> 3] |= (uint32_t)((reduce[b0 + i] < 0 || reduce[b0 + i] > 15) ? 15 : reduce[b0 + i]) << (4 * (i & 7));
+        prog_check_kernel<<<nb, kProgThreads, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, b0, n, c->nlev, red, (long)stride, d_seg_len, c->d_status, c->d_img_status);
+        prog_copy_kernel<false><<<record_grid(max_dense, nb), kRecThreads, 0, s>>>(const_cast<uint8_t *>(d_blob), (long)blob_bytes, d_rec_off, b0, b0 + nb, red, d_cont, (long)stride, c->d_img_status);
+    }
     HIPCHK(hipGetLastError());
     c->img_status_n = B;
     return LLICTI_OK;

@@ -21,6 +21,7 @@ from torch import nn
 
 from ...codec import (MODE_AC, MODE_RANS, NSEG, HipCodec, auto_modes, bytestream_list_to_container, container_to_bytestream_list, header_dims, mode_of_header, mode_of_name, pixel_bytes, pixel_format, reduced_dims)
 from ...archive import Batch
+from ...progressive import ProgressiveBatch
 from ...config import check_supported, model_shape
 
 
@@ -463,7 +464,10 @@ class LLICTI(nn.Module):
         blob_d.record_stream(cur)
         ro_d.record_stream(cur)
         with torch.cuda.device(codec.device):
-            cont_d, seg_d = codec.unpack_records(blob_d, ro_d, stride=int(batch.stride))
+            if isinstance(batch, ProgressiveBatch):      # prefixes of progressive records: the levels >= batch.reduce[b] of image b, nothing else
+                cont_d, seg_d = codec.unpack_progressive(blob_d, ro_d, reduce=[int(r) for r in batch.reduce], stride=int(batch.stride))
+            else:
+                cont_d, seg_d = codec.unpack_records(blob_d, ro_d, stride=int(batch.stride))
         return codec, cont_d, seg_d, Hs, Ws, mode, mixed
 
     @torch.no_grad()
@@ -500,7 +504,7 @@ class LLICTI(nn.Module):
         return EncodedBatch(codec, None, cont_h, seg_h, ev, None, dst_mode, Hs, Ws).lists()
 
     @torch.no_grad()
-    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=0, pixels=None, tensor=None):
+    def decode_batch_async(self, lists, devc=None, slot=0, flat=False, reduce=None, pixels=None, tensor=None):
         """bytestream_lists of B images -> uint8 [B,3,H,W] on the device, enqueued (upload from a pinned buffer + decode); device-side
         failures are reported by codec().check() / image_status().  The images of a call share a container kind; in a rANS container their
         SIZES may differ -- then (or with flat=True) the result is (flat uint8 device tensor, Hs, Ws): the images back to back, [3][H][W] each.
@@ -523,10 +527,23 @@ class LLICTI(nn.Module):
         reduce.  `views` goes with neither `boxes`, `origin` nor `size` at the top level.
         lists may be an archive.Batch (ArchiveReader.read_batch) instead: the records of B images in one host buffer -- one dense upload and
         HipCodec.unpack_records in place of the per-image staging (`slot` is not used: the batch owns its buffer, which must stay untouched until
-        the upload has run); sizes and modes are the archive index's, everything behind the containers is the same path."""
+        the upload has run); sizes and modes are the archive index's, everything behind the containers is the same path.
+        lists may be a progressive.ProgressiveBatch (ProgressiveReader.read_batch(reduce=...)): the PREFIXES of the images' progressive records,
+        holding the levels >= batch.reduce[b] of image b alone -- HipCodec.unpack_progressive in place of unpack_records.  reduce= then defaults to
+        the batch's; a requested r_b BELOW what the batch holds for its image is a ValueError (those bytes were never read).  Otherwise reduce
+        defaults to 0."""
         if tensor is not None and (pixels is not None or flat):
             raise ValueError("tensor=... gives one dense float tensor: it goes with neither pixels= nor flat=")
-        if isinstance(lists, Batch):        # an archive's records: one dense upload, cut into containers on the device
+        if isinstance(lists, ProgressiveBatch):
+            held = [int(r) for r in lists.reduce]
+            if reduce is None:
+                reduce = held[0] if all(r == held[0] for r in held) else held
+            want = [int(reduce)] * len(held) if isinstance(reduce, (int, np.integer)) else [int(r) for r in reduce]
+            if len(want) == len(held) and any(w < h for w, h in zip(want, held)):
+                raise ValueError(f"reduce {want} asks for finer levels than the batch holds ({held}): read the batch at the reduce it is decoded at")
+        elif reduce is None:
+            reduce = 0
+        if isinstance(lists, (Batch, ProgressiveBatch)):        # an archive's records: one dense upload, cut into containers on the device
             codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_batch(lists, devc)
         else:
             codec, cont_d, seg_d, Hs, Ws, mode, mixed = self._upload_lists(lists, devc, slot)
@@ -576,12 +593,19 @@ class EncodedBatch:
         self.cont_d = self.seg_d = None     # the device containers / segment lengths of the encode (records())
         self._rec_stage = None              # pinned staging buffer of records(): nbytes -> flat uint8 host tensor
         self._records = None
+        self._records_prog = None
 
-    def records(self, check=True):
-        """The batch as ONE dense blob of .llic records -> (blob, rec_off): blob a uint8 numpy view of the pinned staging buffer (valid until
+    def records(self, check=True, progressive=False):
+        """progressive=True: the batch as one dense blob of PROGRESSIVE records (llicti_amd/progressive.py) -> (blob, rec_off, prefix): as below,
+        plus prefix int64 [B, 6], every image's P_0 .. P_L; what progressive.ProgressiveWriter.append_records takes.  xwide containers only
+        ("auto", "xrans<M>").  HipCodec.level_cuts + pack_progressive behind the encode: this costs ONE DECODE of the batch (the cuts are the
+        decoder's cursors) -- archives are built once.
+        Otherwise: the batch as ONE dense blob of .llic records -> (blob, rec_off): blob a uint8 numpy view of the pinned staging buffer (valid until
         the next records() of the same slot), rec_off int64 [B + 1]; blob[rec_off[b]:rec_off[b + 1]] is image b's .llic file, the whole blob what
         archive.ArchiveWriter.append_records takes.  Made on the device (HipCodec.pack_records) behind the encode and downloaded as one dense
         copy of rec_off[B] bytes -- the real bytes, not B container strides.  Synchronous; check as for lists()."""
+        if progressive:
+            return self._records_progressive(check)
         if self._records is None:
             if self.cont_d is None:
                 raise ValueError("this handle does not hold its device containers")
@@ -599,6 +623,31 @@ class EncodedBatch:
                 codec.check()
             self._records = (host[:total].numpy(), ro_h.numpy())
         return self._records
+
+    def _records_progressive(self, check):
+        if self._records_prog is None:
+            if self.cont_d is None:
+                raise ValueError("this handle does not hold its device containers")
+            codec = self.codec
+            cur = torch.cuda.current_stream(codec.device)
+            cur.wait_event(self.ev)
+            with torch.cuda.device(codec.device):
+                hdr = self.cont_d[:, :17].contiguous().cpu().numpy()          # (what the encoder wrote: an "auto" encode picks the stream counts)
+                modes = [mode_of_header(hdr[b]) for b in range(hdr.shape[0])]
+                if any((m >> 8) != 5 for m in modes):
+                    raise ValueError("progressive records hold xwide containers: encode with container \"auto\" or \"xrans<M>\"")
+                dims = [header_dims(bytes(hdr[b])) for b in range(hdr.shape[0])]
+                cuts = codec.level_cuts(self.cont_d, self.seg_d, [d[0] for d in dims], [d[1] for d in dims], modes)
+                blob, ro, pre = codec.pack_progressive(self.cont_d, self.seg_d, cuts)
+                ro_h, pre_h = ro.cpu(), pre.cpu()
+                total = int(ro_h[-1])
+                host = torch.empty((max(total, 1),), dtype=torch.uint8).pin_memory()
+                host[:total].copy_(blob[:total], non_blocking=True)
+                cur.synchronize()
+            if check:
+                codec.check()
+            self._records_prog = (host[:total].numpy(), ro_h.numpy(), pre_h.numpy())
+        return self._records_prog
 
     def lists(self, check=True):
         """Wait for the download (NOT for anything enqueued after it) and cut the containers into bytestream_lists (1 + L lists x 9 `bytes`).
