@@ -524,6 +524,8 @@ int llicti_transcode_images(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stri
 #define LLICTI_RECORD_CHUNK 32768
 size_t llicti_record_bytes(const llicti_ctx *ctx, const int32_t *h_seg_len);
 size_t llicti_record_bytes_n(int n, const int32_t *h_seg_len);      /* the same for a segment count given outright (49 or 22, else 0): needs no context */
+/* All device buffers of a record call are PAIRWISE DISJOINT -- d_blob (blob_cap / blob_bytes), d_cont (B * stride), d_seg_len, d_rec_off --:
+ * any two that overlap are LLICTI_EINVAL before anything is launched, and llicti_last_error names both. */
 int llicti_pack_records(llicti_ctx *ctx, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B,
                         uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off /* [B+1] */, void *stream);
 int llicti_unpack_records(llicti_ctx *ctx, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off /* [B+1] */, int B,
@@ -591,6 +593,8 @@ int llicti_unpack_records(llicti_ctx *ctx, const uint8_t *d_blob, size_t blob_by
 int llicti_level_cuts(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
                       int B, const int *Hs, const int *Ws, const int *modes, void *d_workspace, size_t workspace_bytes,
                       int32_t *d_cuts /* [B][128][LLICTI_NLEVELS] */, void *stream);
+/* All device buffers of these two calls are PAIRWISE DISJOINT, as for the record calls above: d_blob, d_cont, d_seg_len, d_rec_off and, for
+ * llicti_pack_progressive, d_cuts and d_prefix (so d_cuts may not overlap d_rec_off, the containers or the segment lengths either). */
 int llicti_pack_progressive(llicti_ctx *ctx, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B, const int32_t *d_cuts,
                             uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off /* [B+1] */, int64_t *d_prefix /* [B][LLICTI_NLEVELS+1] */, void *stream);
 int llicti_unpack_progressive(llicti_ctx *ctx, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off /* [B+1] */, int B,

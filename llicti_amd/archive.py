@@ -14,6 +14,9 @@ File layout (little-endian throughout; DESIGN.md, "Image archives"):
 
 n is the segment count of every record of the archive: 49 (config A) or 22 (config B).  The index sits behind the records so that a writer
 streams records without knowing their number, and a reader finds it from the fixed-size trailer.
+
+The file layer -- RecordFileWriter, RecordFileReader -- is written once for every kind of record: a `Kind` says what tells one archive format
+from another (progressive.py's `.llpa` is the second), and a subclass adds what only its records can do.
 """
 from __future__ import annotations
 
@@ -32,6 +35,17 @@ VERSION = 1
 TRAILER = struct.Struct("<4sBBHQQI")
 TRAILER_BYTES = TRAILER.size            # 28
 EXT = ".llia"
+
+
+class Kind(NamedTuple):
+    """An archive format, as data: the trailer's magic and version; row(n) -> the numpy dtype of a record's index row (H, W, mode, then the
+    kind's own columns); min_record(n) -> the smallest legal record, bytes; parse(record bytes, n) -> the record's index row as a tuple,
+    ValueError for a record that is not a well-formed one of the model of n segments."""
+    magic: bytes
+    version: int
+    row: object
+    min_record: object
+    parse: object
 
 
 class Batch(NamedTuple):
@@ -70,8 +84,12 @@ def parse_record(buf, nseg):
     return H, W, mode_of_header(hdr)
 
 
-class ArchiveWriter:
-    """Write a `.llia` archive: append records (whole blobs from the device, or single .llic files), then close() writes index and trailer."""
+LLIA = Kind(MAGIC, VERSION, lambda nseg: np.dtype([("H", "<u2"), ("W", "<u2"), ("mode", "<u4")]), record_header_bytes, parse_record)
+
+
+class RecordFileWriter:
+    """Write an archive of KIND: append records, then close() writes index and trailer."""
+    KIND: Kind
 
     def __init__(self, path, nseg):
         if int(nseg) not in fileio.NSEGS:
@@ -79,15 +97,15 @@ class ArchiveWriter:
         self.path, self.nseg = path, int(nseg)
         self._fh = open(path, "wb")
         self._offsets = [0]
-        self._meta = []
+        self._rows = []
         self._names = []
 
     def __len__(self):
-        return len(self._meta)
+        return len(self._rows)
 
     def append_records(self, blob, rec_off, names=None):
-        """blob: bytes-like holding B records at rec_off[b] .. rec_off[b + 1] (what HipCodec.pack_records / EncodedBatch.records() give);
-        names: B strings or None (the running index as a decimal string).  H, W and mode come from each record's 17-byte container header."""
+        """blob: bytes-like holding B whole records at rec_off[b] .. rec_off[b + 1] (what EncodedBatch.records gives); names: B strings or
+        None (the running index as a decimal string).  The index row of each comes from the record itself (KIND.parse)."""
         if self._fh is None:
             raise ValueError("archive is closed")
         ro = np.asarray(rec_off, dtype=np.int64).reshape(-1)
@@ -97,30 +115,28 @@ class ArchiveWriter:
         mv = memoryview(blob).cast("B") if not isinstance(blob, np.ndarray) else memoryview(np.ascontiguousarray(blob, dtype=np.uint8)).cast("B")
         if B and (ro[0] < 0 or (np.diff(ro) < 0).any() or ro[-1] > len(mv)):
             raise ValueError("record offsets must ascend inside the blob")
-        metas = [parse_record(mv[int(ro[b]):int(ro[b + 1])], self.nseg) for b in range(B)]      # (all of them before a byte is written)
-        nm = [str(len(self._meta) + b) for b in range(B)] if names is None else [str(s) for s in names]
+        rows = [self.KIND.parse(mv[int(ro[b]):int(ro[b + 1])], self.nseg) for b in range(B)]      # (all of them before a byte is written)
+        nm = [str(len(self._rows) + b) for b in range(B)] if names is None else [str(s) for s in names]
         if any("\0" in s for s in nm):
             raise ValueError("a name holds a NUL")
         if B:
             self._fh.write(mv[int(ro[0]):int(ro[B])])          # (records b = [ro[b], ro[b + 1]) are adjacent: one write)
         base = self._offsets[-1] - (int(ro[0]) if B else 0)
         self._offsets += [base + int(v) for v in ro[1:]]
-        self._meta += metas
+        self._rows += rows
         self._names += nm
 
-    def append_llic(self, data, name=None):
-        """One .llic file's bytes."""
+    def _append_one(self, data, name):
         self.append_records(data, [0, len(data)], None if name is None else [name])
 
     def close(self):
         if self._fh is None:
             return
-        count = len(self._meta)
         index = np.asarray(self._offsets, dtype="<u8").tobytes()
-        index += b"".join(struct.pack("<HHI", H, W, mode) for H, W, mode in self._meta)
+        index += np.array(self._rows, dtype=self.KIND.row(self.nseg)).tobytes()
         index += b"".join(s.encode("utf-8") + b"\0" for s in self._names)
         self._fh.write(index)
-        self._fh.write(TRAILER.pack(MAGIC, VERSION, self.nseg, 0, count, self._offsets[-1], zlib.crc32(index) & 0xFFFFFFFF))
+        self._fh.write(TRAILER.pack(self.KIND.magic, self.KIND.version, self.nseg, 0, len(self._rows), self._offsets[-1], zlib.crc32(index) & 0xFFFFFFFF))
         self._fh.close()
         self._fh = None
 
@@ -131,40 +147,43 @@ class ArchiveWriter:
         self.close()
 
 
-class ArchiveReader:
-    """Memory-mapped `.llia` archive.  A bad trailer (magic, version, n, offsets that do not fit the file) or an index whose crc32 differs is a
-    ValueError; the records themselves are validated where they are used (loads_llic here, HipCodec.unpack_records on the device)."""
+class RecordFileReader:
+    """Memory-mapped archive of KIND.  A bad trailer (magic, version, n, offsets that do not fit the file), an index whose crc32 differs or
+    whose rows a subclass refuses (_load_rows) is a ValueError; the records themselves are validated where they are used."""
+    KIND: Kind
 
     def __init__(self, path):
         self.path = path
+        what = self.KIND.magic.decode()
         self._fh = open(path, "rb")
         try:
             size = self._fh.seek(0, 2)
             if size < TRAILER_BYTES:
-                raise ValueError(f"{path}: shorter than an LLIA trailer")
+                raise ValueError(f"{path}: shorter than an {what} trailer")
             self._mm = mmap.mmap(self._fh.fileno(), 0, access=mmap.ACCESS_READ)
             magic, version, nseg, zero, count, index_offset, crc = TRAILER.unpack(self._mm[size - TRAILER_BYTES:size])
-            if magic != MAGIC:
-                raise ValueError(f"{path}: not an LLIA archive (bad magic)")
-            if version != VERSION or zero != 0:
-                raise ValueError(f"{path}: unsupported LLIA version {version}")
+            if magic != self.KIND.magic:
+                raise ValueError(f"{path}: not an {what} archive (bad magic)")
+            if version != self.KIND.version or zero != 0:
+                raise ValueError(f"{path}: unsupported {what} version {version}")
             if nseg not in fileio.NSEGS:
                 raise ValueError(f"{path}: {nseg} segments per record (49 = config A, 22 = config B)")
+            row = self.KIND.row(nseg)
             index_end = size - TRAILER_BYTES
-            if index_offset > index_end or (count + 1) * 8 + count * 9 > index_end - index_offset:       # (offsets, 8 bytes of sizes and a NUL per image)
+            if index_offset > index_end or (count + 1) * 8 + count * (row.itemsize + 1) > index_end - index_offset:       # (offsets, a row and a NUL per image)
                 raise ValueError(f"{path}: index offset {index_offset} / count {count} do not fit a file of {size} bytes")
             index = self._mm[index_offset:index_end]
             if zlib.crc32(index) & 0xFFFFFFFF != crc:
                 raise ValueError(f"{path}: index crc32 mismatch")
             self.nseg, self.count, self.index_offset = int(nseg), int(count), int(index_offset)
             self.offsets = np.frombuffer(index, dtype="<u8", count=count + 1).astype(np.int64)
-            if self.offsets[0] != 0 or (np.diff(self.offsets) < record_header_bytes(nseg)).any() or self.offsets[-1] != index_offset:
+            if self.offsets[0] != 0 or (np.diff(self.offsets) < self.KIND.min_record(nseg)).any() or self.offsets[-1] != index_offset:
                 raise ValueError(f"{path}: record offsets do not tile the record region")
-            meta = np.frombuffer(index, dtype=np.dtype([("H", "<u2"), ("W", "<u2"), ("mode", "<u4")]), count=count, offset=(count + 1) * 8)
-            self.sizes = [(int(h), int(w)) for h, w in zip(meta["H"], meta["W"])]
-            self.modes = [int(m) for m in meta["mode"]]
-            raw = index[(count + 1) * 8 + count * 8:]
-            parts = raw.split(b"\0")
+            rows = np.frombuffer(index, dtype=row, count=count, offset=(count + 1) * 8)
+            self.sizes = [(int(h), int(w)) for h, w in zip(rows["H"], rows["W"])]
+            self.modes = [int(m) for m in rows["mode"]]
+            self._load_rows(rows)
+            parts = index[(count + 1) * 8 + count * row.itemsize:].split(b"\0")
             if len(parts) != count + 1 or parts[-1] != b"":
                 raise ValueError(f"{path}: the index does not hold {count} NUL-terminated names")
             self.names = [p.decode("utf-8") for p in parts[:-1]]
@@ -172,6 +191,9 @@ class ArchiveReader:
         except Exception:
             self.close()
             raise
+
+    def _load_rows(self, rows):
+        """A subclass sets its own public attributes from the kind's index columns here (ValueError for a file to refuse)."""
 
     def __len__(self):
         return self.count
@@ -181,41 +203,26 @@ class ArchiveReader:
         """Bytes of the record region."""
         return self.index_offset
 
-    def record(self, i) -> bytes:
-        """The bytes of record i: a .llic file."""
+    def _index(self, i):
         i = int(i)
         if not -self.count <= i < self.count:
             raise IndexError(i)
-        i %= self.count
+        return i % self.count
+
+    def record(self, i) -> bytes:
+        """The bytes of record i, whole."""
+        i = self._index(i)
         return bytes(self._mm[int(self.offsets[i]):int(self.offsets[i + 1])])
 
-    def __getitem__(self, i):
-        """-> the image's bytestream_list (fileio.loads_llic)."""
-        return fileio.loads_llic(self.record(i))
-
-    def read_batch(self, indices, pinned=True) -> Batch:
-        """The records of `indices` (any order, repeats allowed) gathered into ONE host buffer -> Batch.  Each run of consecutive indices is
-        one memcpy out of the mapping.  pinned: a page-locked buffer (one asynchronous H2D copy); without a GPU runtime it is an ordinary one."""
+    def _host_blob(self, lens, pinned):
+        """Room for records of `lens` bytes back to back -> (uint8 host tensor, its numpy view, rec_off int64 [B + 1]).  pinned: page-locked
+        (one asynchronous H2D copy); without a GPU runtime an ordinary buffer.  A batch hands out a VIEW blob[:n] of this tensor, not the
+        tensor: measured (profiles/records_refactor/README.md), a batch whose blob is the pinned allocation itself makes the record call
+        that follows its upload and decode 15-25 us slower."""
         import torch
-        idx = [int(i) % self.count if -self.count <= int(i) < self.count else int(i) for i in indices]
-        if any(not 0 <= i < self.count for i in idx):
-            raise IndexError(f"an index outside 0 .. {self.count - 1}")
-        lens = np.array([self.offsets[i + 1] - self.offsets[i] for i in idx], dtype=np.int64)
         rec_off = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
         blob = torch.empty((max(1, int(rec_off[-1])),), dtype=torch.uint8, pin_memory=bool(pinned and torch.cuda.is_available()))
-        dst = blob.numpy()
-        k = 0
-        while k < len(idx):
-            e = k
-            while e + 1 < len(idx) and idx[e + 1] == idx[e] + 1:
-                e += 1
-            s0, s1 = int(self.offsets[idx[k]]), int(self.offsets[idx[e] + 1])
-            dst[int(rec_off[k]):int(rec_off[k]) + (s1 - s0)] = self._u8[s0:s1]
-            k = e + 1
-        hb = record_header_bytes(self.nseg)
-        stride = max(16, (int((lens - hb).max()) + 15) // 16 * 16) if len(idx) else 16
-        return Batch(blob[:max(1, int(rec_off[-1]))], rec_off, [self.sizes[i][0] for i in idx], [self.sizes[i][1] for i in idx],
-                     [self.modes[i] for i in idx], stride)
+        return blob, blob.numpy(), rec_off
 
     def close(self):
         self._u8 = None
@@ -234,3 +241,59 @@ class ArchiveReader:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class ArchiveWriter(RecordFileWriter):
+    """Write a `.llia` archive: append records (whole blobs from the device -- HipCodec.pack_records / EncodedBatch.records() --, or single
+    .llic files), then close() writes index and trailer.  H, W and mode come from each record's 17-byte container header."""
+    KIND = LLIA
+
+    def append_llic(self, data, name=None):
+        """One .llic file's bytes."""
+        self._append_one(data, name)
+
+
+class ArchiveReader(RecordFileReader):
+    """Memory-mapped `.llia` archive; its records are validated where they are used (loads_llic here, HipCodec.unpack_records on the device)."""
+    KIND = LLIA
+
+    def __getitem__(self, i):
+        """-> the image's bytestream_list (fileio.loads_llic)."""
+        return fileio.loads_llic(self.record(i))
+
+    def read_batch(self, indices, pinned=True) -> Batch:
+        """The records of `indices` (any order, repeats allowed) gathered into ONE host buffer -> Batch.  Each run of consecutive indices is
+        one memcpy out of the mapping.  pinned: a page-locked buffer (one asynchronous H2D copy); without a GPU runtime it is an ordinary one."""
+        if any(not -self.count <= int(i) < self.count for i in indices):
+            raise IndexError(f"an index outside 0 .. {self.count - 1}")
+        idx = [self._index(i) for i in indices]
+        lens = np.array([self.offsets[i + 1] - self.offsets[i] for i in idx], dtype=np.int64)
+        blob, dst, rec_off = self._host_blob(lens, pinned)
+        k = 0
+        while k < len(idx):
+            e = k
+            while e + 1 < len(idx) and idx[e + 1] == idx[e] + 1:
+                e += 1
+            s0, s1 = int(self.offsets[idx[k]]), int(self.offsets[idx[e] + 1])
+            dst[int(rec_off[k]):int(rec_off[k]) + (s1 - s0)] = self._u8[s0:s1]
+            k = e + 1
+        hb = record_header_bytes(self.nseg)
+        stride = max(16, (int((lens - hb).max()) + 15) // 16 * 16) if len(idx) else 16
+        return Batch(blob[:max(1, int(rec_off[-1]))], rec_off, [self.sizes[i][0] for i in idx], [self.sizes[i][1] for i in idx], [self.modes[i] for i in idx], stride)
+
+
+class NotAnArchive(ValueError):
+    """open_archive: the file ends in no archive's trailer."""
+
+
+def open_archive(path):
+    """-> the reader of the archive at `path`, chosen by the magic of its trailer: ArchiveReader (`.llia`) or progressive.ProgressiveReader
+    (`.llpa`); NotAnArchive (a ValueError) for a file that ends in neither, whatever that reader refuses for one that does."""
+    from .progressive import ProgressiveReader
+    with open(path, "rb") as fh:
+        fh.seek(max(0, fh.seek(0, 2) - TRAILER_BYTES))
+        tail = fh.read(TRAILER_BYTES)
+    for reader in (ArchiveReader, ProgressiveReader):
+        if len(tail) == TRAILER_BYTES and tail[:4] == reader.KIND.magic:
+            return reader(path)
+    raise NotAnArchive(f"{path}: neither an LLIA nor an LLPA archive")

@@ -80,87 +80,9 @@ def _batch_arg(v):
     return n
 
 
-def _archive_kind(path):
-    """b"LLIA" / b"LLPA" for an archive of plain / progressive records, None for anything else"""
-    from .archive import MAGIC, TRAILER_BYTES
-    from .progressive import ARCHIVE_MAGIC
-    with open(path, "rb") as fh:
-        size = fh.seek(0, 2)
-        if size < TRAILER_BYTES:
-            return None
-        fh.seek(size - TRAILER_BYTES)
-        magic = fh.read(4)
-        return magic if magic in (MAGIC, ARCHIVE_MAGIC) else None
-
-
-def _is_archive(path):
-    from .archive import MAGIC
-    return _archive_kind(path) == MAGIC
-
-
 def progressive_container_ok(name) -> bool:
     """pack --progressive takes the containers whose streams are xwide: "auto" and "xrans<M>\""""
     return name == "auto" or (name.startswith("xrans") and name[5:].isdigit())
-
-
-def _info_progressive(path):
-    from .codec import name_of_mode
-    from .progressive import ProgressiveReader
-    with ProgressiveReader(path) as ar:
-        print(f"{path}: {len(ar)} images, n = {ar.nseg} segments per record, {ar.total_bytes} bytes of progressive records")
-        for k in range(len(ar)):
-            (H, W), pre = ar.sizes[k], [int(v) for v in ar.prefix[k]]
-            print(f"  {ar.names[k]}: {W}x{H}, container {name_of_mode(ar.modes[k])}, {pre[0]} bytes, {8.0 * pre[0] / (H * W):.4f} bpp; prefix bytes "
-                  + ", ".join(f"P_{r}={v}" for r, v in enumerate(pre)))
-    return 0
-
-
-def _pack_progressive(a):
-    import os
-    from . import fileio
-    from .progressive import ProgressiveWriter
-    if not progressive_container_ok(a.container):
-        print(f"pack --progressive: container {a.container!r} has no xwide streams; progressive records need --container auto (or xrans<M>)", file=sys.stderr)
-        return 2
-    if any(s.lower().endswith(".llic") for s in a.src):
-        print("pack --progressive takes images: a .llic file's level cuts come from a decode (transcode it, or pack the image)", file=sys.stderr)
-        return 2
-    names = [os.path.splitext(os.path.basename(s))[0] for s in a.src]
-    model, torch = _model(a.container, a.checkpoint, a.config)
-    t0, total = time.time(), 0
-    with ProgressiveWriter(a.archive, model.codec().nseg) as aw:
-        for g0 in range(0, len(a.src), a.batch):
-            g1 = min(len(a.src), g0 + a.batch)
-            imgs = [fileio.read_image(s, layout="hwc") for s in a.src[g0:g1]]
-            blob, rec_off, _ = model.encode_batch_async(imgs, pixels="rgb").records(progressive=True)
-            aw.append_records(blob, rec_off, names[g0:g1])
-            total += int(rec_off[-1])
-    print(f"{len(a.src)} images -> {a.archive}: {total} bytes of progressive records, {time.time() - t0:.3f} s")
-    return 0
-
-
-def _unpack_progressive(a):
-    import os
-    from . import fileio
-    from .progressive import ProgressiveReader, to_llic
-    os.makedirs(a.dir, exist_ok=True)
-    t0 = time.time()
-    with ProgressiveReader(a.archive) as ar:
-        names = [os.path.basename(n) or str(k) for k, n in enumerate(ar.names)]
-        if a.fmt == "llic":                                  # (on the host: no GPU)
-            for k in range(len(ar)):
-                with open(os.path.join(a.dir, names[k] + ".llic"), "wb") as fh:
-                    fh.write(to_llic(ar.record(k)))
-        else:
-            model, torch = _model("ac", a.checkpoint, a.config)
-            for g0 in range(0, len(ar), a.batch):
-                g1 = min(len(ar), g0 + a.batch)
-                outs = model.decode_batch_async(ar.read_batch(range(g0, g1)), torch.device("cuda:0"), pixels="rgb")
-                model.codec().check()
-                for k, hwc in zip(range(g0, g1), outs):
-                    fileio.write_image(os.path.join(a.dir, names[k] + "." + a.fmt), hwc.cpu().numpy(), layout="hwc")
-        print(f"{a.archive} -> {a.dir}: {len(ar)} images as {a.fmt}, {time.time() - t0:.3f} s")
-    return 0
 
 
 def _groups(keys, limit):
@@ -175,14 +97,15 @@ def _groups(keys, limit):
     return out
 
 
-def _info_archive(path):
-    from .archive import ArchiveReader
+def _info(ar):
     from .codec import name_of_mode
-    with ArchiveReader(path) as ar:
-        print(f"{path}: {len(ar)} images, n = {ar.nseg} segments per record, {ar.total_bytes} bytes of records")
-        for k in range(len(ar)):
-            (H, W), nb = ar.sizes[k], int(ar.offsets[k + 1] - ar.offsets[k])
-            print(f"  {ar.names[k]}: {W}x{H}, container {name_of_mode(ar.modes[k])}, {nb} bytes, {8.0 * nb / (H * W):.4f} bpp")
+    from .progressive import ProgressiveReader
+    prog = isinstance(ar, ProgressiveReader)
+    print(f"{ar.path}: {len(ar)} images, n = {ar.nseg} segments per record, {ar.total_bytes} bytes of {'progressive records' if prog else 'records'}")
+    for k in range(len(ar)):
+        (H, W), nb = ar.sizes[k], int(ar.offsets[k + 1] - ar.offsets[k])
+        tail = "; prefix bytes " + ", ".join(f"P_{r}={int(v)}" for r, v in enumerate(ar.prefix[k])) if prog else ""
+        print(f"  {ar.names[k]}: {W}x{H}, container {name_of_mode(ar.modes[k])}, {nb} bytes, {8.0 * nb / (H * W):.4f} bpp{tail}")
     return 0
 
 
@@ -190,8 +113,15 @@ def _pack(a):
     import os
     from . import fileio
     from .archive import ArchiveWriter
-    names = [os.path.splitext(os.path.basename(s))[0] for s in a.src]
+    from .progressive import ProgressiveWriter
     is_llic = [s.lower().endswith(".llic") for s in a.src]
+    if a.progressive and not progressive_container_ok(a.container):
+        print(f"pack --progressive: container {a.container!r} has no xwide streams; progressive records need --container auto (or xrans<M>)", file=sys.stderr)
+        return 2
+    if a.progressive and any(is_llic):
+        print("pack --progressive takes images: a .llic file's level cuts come from a decode (transcode it, or pack the image)", file=sys.stderr)
+        return 2
+    names = [os.path.splitext(os.path.basename(s))[0] for s in a.src]
     model = torch = None
     if not all(is_llic):
         model, torch = _model(a.container, a.checkpoint, a.config)
@@ -200,9 +130,9 @@ def _pack(a):
         with open(a.src[0], "rb") as fh:
             nseg = fh.read(6)[5]
     t0, total = time.time(), 0
-    with ArchiveWriter(a.archive, nseg) as aw:
-        imgs = {k: fileio.read_image(s, layout="hwc") for k, s in enumerate(a.src) if not is_llic[k]}
-        # a batch is a run of images; the reference format codes one size per call
+    with (ProgressiveWriter if a.progressive else ArchiveWriter)(a.archive, nseg) as aw:
+        # a batch is a run of images; the reference format codes one size per call, so its images are read ahead for their sizes
+        imgs = {k: fileio.read_image(s, layout="hwc") for k, s in enumerate(a.src) if not is_llic[k]} if a.container == "ac" else {}
         keys = [("llic", k) if is_llic[k] else ("img", imgs[k].shape[:2] if a.container == "ac" else None) for k in range(len(a.src))]
         for g0, g1 in _groups(keys, a.batch):
             if is_llic[g0]:
@@ -211,29 +141,32 @@ def _pack(a):
                 aw.append_llic(data, names[g0])
                 total += len(data)
                 continue
-            blob, rec_off = model.encode_batch_async([imgs[k] for k in range(g0, g1)], pixels="rgb").records()
+            batch = [imgs[k] if k in imgs else fileio.read_image(a.src[k], layout="hwc") for k in range(g0, g1)]
+            blob, rec_off = model.encode_batch_async(batch, pixels="rgb").records(progressive=a.progressive)[:2]
             aw.append_records(blob, rec_off, names[g0:g1])
             total += int(rec_off[-1])
-    print(f"{len(a.src)} images -> {a.archive}: {total} bytes of records, {time.time() - t0:.3f} s")
+    print(f"{len(a.src)} images -> {a.archive}: {total} bytes of {'progressive records' if a.progressive else 'records'}, {time.time() - t0:.3f} s")
     return 0
 
 
 def _unpack(a):
     import os
     from . import fileio
-    from .archive import ArchiveReader
+    from .archive import open_archive
+    from .progressive import ProgressiveReader, to_llic
     os.makedirs(a.dir, exist_ok=True)
     t0 = time.time()
-    with ArchiveReader(a.archive) as ar:
+    with open_archive(a.archive) as ar:
+        prog = isinstance(ar, ProgressiveReader)
         names = [os.path.basename(n) or str(k) for k, n in enumerate(ar.names)]
-        if a.fmt == "llic":
+        if a.fmt == "llic":                                  # (on the host: no GPU)
             for k in range(len(ar)):
                 with open(os.path.join(a.dir, names[k] + ".llic"), "wb") as fh:
-                    fh.write(ar.record(k))
+                    fh.write(to_llic(ar.record(k)) if prog else ar.record(k))
         else:
             model, torch = _model("ac", a.checkpoint, a.config)
-            # a batch is a run of images of one container kind (the reference format: of one size too)
-            keys = [(m & ~0xFF, ar.sizes[k] if m == 0 else None) for k, m in enumerate(ar.modes)]
+            # a batch is a run of images; of plain records: of one container kind (the reference format: of one size too)
+            keys = [None if prog else (m & ~0xFF, ar.sizes[k] if m == 0 else None) for k, m in enumerate(ar.modes)]
             for g0, g1 in _groups(keys, a.batch):
                 outs = model.decode_batch_async(ar.read_batch(range(g0, g1)), torch.device("cuda:0"), pixels="rgb")
                 model.codec().check()
@@ -246,15 +179,17 @@ def _unpack(a):
 def main(argv=None):
     a = build_parser().parse_args(argv)
     from . import fileio
-    from .progressive import ARCHIVE_MAGIC
     if a.cmd == "pack":
-        return _pack_progressive(a) if a.progressive else _pack(a)
+        return _pack(a)
     if a.cmd == "unpack":
-        return _unpack_progressive(a) if _archive_kind(a.archive) == ARCHIVE_MAGIC else _unpack(a)
-    if a.cmd == "info" and _archive_kind(a.src) == ARCHIVE_MAGIC:
-        return _info_progressive(a.src)
-    if a.cmd == "info" and _is_archive(a.src):
-        return _info_archive(a.src)
+        return _unpack(a)
+    if a.cmd == "info":
+        from .archive import NotAnArchive, open_archive
+        try:
+            with open_archive(a.src) as ar:
+                return _info(ar)
+        except NotAnArchive:
+            pass                                             # a .llic file
     if a.cmd == "info":
         from .codec import header_dims, levels_of_header, mode_of_header, name_of_mode, reduced_dims
         bl = fileio.read_llic(a.src)

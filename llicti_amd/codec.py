@@ -591,15 +591,20 @@ class HipCodec:
             self._ws_grown = True
         return self._ws
 
-    def workspace(self, B, H, W, mode=MODE_AC):
-        key = (B, H, W, mode)
+    def _ws_bytes(self, key, ask):
+        """The workspace bytes of the call `key` names: remembered (the table is cleared at 256 entries), else ask()ed of the library."""
         n = self._ws_need.get(key)
         if n is None:
             if len(self._ws_need) > 256:
                 self._ws_need.clear()
+            n = self._ws_need[key] = int(ask())
+        return n
+
+    def workspace(self, B, H, W, mode=MODE_AC):
+        def ask():
             Hs, Ws, m = (C.c_int * B)(*([H] * B)), (C.c_int * B)(*([W] * B)), (C.c_int * 1)(mode)
-            n = self._ws_need[key] = int(self.L.llicti_workspace_bytes_ctx(self.ctx, B, Hs, Ws, m, 1))      # (the context's model)
-        return self._workspace_of(n)
+            return self.L.llicti_workspace_bytes_ctx(self.ctx, B, Hs, Ws, m, 1)      # (the context's model)
+        return self._workspace_of(self._ws_bytes((B, H, W, mode), ask))
 
     @staticmethod
     def _modes_arg(mode, B):
@@ -613,15 +618,9 @@ class HipCodec:
     def workspace_v(self, Hs, Ws, mode):
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         one, per = self._modes_arg(mode, len(Hs))
-        key = (Hs.tobytes(), Ws.tobytes(), one if per is None else per.tobytes())
-        n = self._ws_need.get(key)
-        if n is None:
-            if len(self._ws_need) > 256:
-                self._ws_need.clear()
-            n = int(self.L.llicti_workspace_bytes_ctx(self.ctx, len(Hs), _ptr(Hs), _ptr(Ws), (C.c_int * 1)(one), 1)) if per is None else \
-                int(self.L.llicti_workspace_bytes_ctx(self.ctx, len(Hs), _ptr(Hs), _ptr(Ws), _ptr(per), len(Hs)))
-            self._ws_need[key] = n
-        return self._workspace_of(n)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        return self._workspace_of(self._ws_bytes((Hs.tobytes(), Ws.tobytes(), one if per is None else per.tobytes()), lambda: self.L.llicti_workspace_bytes_ctx(
+            self.ctx, len(Hs), _ptr(Hs), _ptr(Ws), _ptr(modes), len(modes))))
 
     def max_container_bytes(self, H, W):
         n = self._mc.get((H, W))
@@ -671,22 +670,32 @@ class HipCodec:
         offs = np.concatenate(([0], np.cumsum(sizes)))
         return offs[:-1], int(offs[-1])
 
+    def _containers_out(self, Hs, Ws, out, seg_len):
+        """The output side of a call that writes containers for images of sizes Hs[b] x Ws[b]: the caller's tensors, or new ones of the widest
+        container stride among the sizes -> (out uint8 [B, stride], seg_len int32 [B, 49], that stride)"""
+        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
+        if out is None:
+            out = torch.empty((len(Hs), stride), dtype=torch.uint8, device=self.device)
+        if seg_len is None:
+            seg_len = torch.zeros((len(Hs), NSEG), dtype=torch.int32, device=self.device)
+        return out, seg_len, stride
+
+    def _encode_front(self, Hs, Ws, mode, out, seg_len):
+        """The front of the encode calls on mixed sizes: sizes as int32 arrays, the workspace, the outputs and the mode as one int (per None)
+        or one per image (one None: stream counts may differ) -> (Hs, Ws, B, ws, out, seg_len, one, per)"""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        ws = self.workspace_v(Hs, Ws, mode)
+        out, seg_len, stride = self._containers_out(Hs, Ws, out, seg_len)
+        assert out.shape[1] >= stride
+        return (Hs, Ws, len(Hs), ws, out, seg_len) + self._modes_arg(mode, len(Hs))
+
     def encode_v(self, rgb_flat, Hs, Ws, mode, out=None, seg_len=None):
         """rgb_flat: uint8 device tensor holding B images of sizes Hs[b] x Ws[b] back to back ([3][H][W] each) -> (containers uint8
         [B, stride], seg_len int32 [B, 49]), async.  Image b's bytes are those of encode() on that image alone."""
         assert rgb_flat.dtype == torch.uint8 and rgb_flat.is_cuda and rgb_flat.dim() == 1 and rgb_flat.is_contiguous()
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
         assert rgb_flat.numel() >= self.flat_offsets(Hs, Ws)[1]
-        ws = self.workspace_v(Hs, Ws, mode)
-        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
-        if out is None:
-            out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
-        if seg_len is None:
-            seg_len = torch.zeros((B, NSEG), dtype=torch.int32, device=self.device)
-        assert out.shape[1] >= stride
-        one, per = self._modes_arg(mode, B)         # one mode for the call, or one per image (stream counts may differ: llicti_encode_images_vm)
-        if per is None:
+        Hs, Ws, B, ws, out, seg_len, one, per = self._encode_front(Hs, Ws, mode, out, seg_len)
+        if per is None:                             # (one mode for the call; else llicti_encode_images_vm)
             _lib.check(self.L.llicti_encode_images_v(self.ctx, _ptr(rgb_flat), None, B, _ptr(Hs), _ptr(Ws), one, _ptr(ws), ws.numel(),
                                                      _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
         else:
@@ -762,18 +771,9 @@ class HipCodec:
         starts at byte px_off[b] with rows pitch[b] bytes apart (None: tight rows / the windows back to back), so a window may be a crop of a
         larger frame -> (containers, seg_len) as encode_v: the bytes of the planar call on the same pixel values.  Alpha is ignored.  Async."""
         assert pix.dtype == torch.uint8 and pix.is_cuda and pix.dim() == 1 and pix.is_contiguous()
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
+        Hs, Ws, B, ws, out, seg_len, one, per = self._encode_front(Hs, Ws, mode, out, seg_len)
         fmt, offs, pt, total = self._px_layout(fmt, list(zip(Hs.tolist(), Ws.tolist())), px_off, pitch)
         assert pix.numel() >= total
-        ws = self.workspace_v(Hs, Ws, mode)
-        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
-        if out is None:
-            out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
-        if seg_len is None:
-            seg_len = torch.zeros((B, NSEG), dtype=torch.int32, device=self.device)
-        assert out.shape[1] >= stride
-        one, per = self._modes_arg(mode, B)
         modes = np.full(B, one, dtype=np.int32) if per is None else per
         _lib.check(self.L.llicti_encode_images_px(self.ctx, _ptr(pix), fmt, _ptr(offs), _ptr(pt), B, _ptr(Hs), _ptr(Ws), _ptr(modes),
                                                   _ptr(ws), ws.numel(), _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
@@ -898,20 +898,11 @@ class HipCodec:
         back to back) -> (containers, seg_len), async.  A sample x is the pixel round(x * 255) (half to even, as torch.round), clamped to
         0 .. 255, NaN -> 0; the bytes are those of encode_v on these pixel values."""
         assert x_flat.dtype == torch.float32 and x_flat.is_cuda and x_flat.dim() == 1 and x_flat.is_contiguous()
-        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
-        B = len(Hs)
+        Hs, Ws, B, ws, out, seg_len, one, per = self._encode_front(Hs, Ws, mode, out, seg_len)
         sizes = 3 * Hs.astype(np.int64) * Ws.astype(np.int64)
         offs = None if x_off is None else np.ascontiguousarray(x_off, dtype=np.uint64)
         assert offs is None or offs.shape == (B,)
         assert x_flat.numel() >= (int(sizes.sum()) if offs is None else max(int(o) + int(n) for o, n in zip(offs, sizes)))
-        ws = self.workspace_v(Hs, Ws, mode)
-        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
-        if out is None:
-            out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
-        if seg_len is None:
-            seg_len = torch.zeros((B, NSEG), dtype=torch.int32, device=self.device)
-        assert out.shape[1] >= stride
-        one, per = self._modes_arg(mode, B)
         modes = np.full(B, one, dtype=np.int32) if per is None else per
         _lib.check(self.L.llicti_encode_images_f32(self.ctx, _ptr(x_flat), _ptr(offs), B, _ptr(Hs), _ptr(Ws), _ptr(modes), _ptr(ws), ws.numel(),
                                                    _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
@@ -928,13 +919,8 @@ class HipCodec:
         for mode in (src_mode, dst_mode):
             one, per = self._modes_arg(mode, B)
             sides.append(np.array([one], dtype=np.int32) if per is None else per)
-        key = ("transcode", Hs.tobytes(), Ws.tobytes(), sides[0].tobytes(), sides[1].tobytes())
-        n = self._ws_need.get(key)
-        if n is None:
-            if len(self._ws_need) > 256:
-                self._ws_need.clear()
-            n = self._ws_need[key] = int(self.L.llicti_transcode_workspace_bytes(self.ctx, B, _ptr(Hs), _ptr(Ws), _ptr(sides[0]), len(sides[0]),
-                                                                                 _ptr(sides[1]), len(sides[1])))
+        n = self._ws_bytes(("transcode", Hs.tobytes(), Ws.tobytes(), sides[0].tobytes(), sides[1].tobytes()), lambda: self.L.llicti_transcode_workspace_bytes(
+            self.ctx, B, _ptr(Hs), _ptr(Ws), _ptr(sides[0]), len(sides[0]), _ptr(sides[1]), len(sides[1])))
         if n == 0:
             raise _lib.LlictiError(_lib.EINVAL, "transcode: a combination of sizes and container modes the call refuses (an \"auto\" source, mixed lane kinds, "
                                                 "the reference format with images of different sizes, a mode the model does not take)")
@@ -949,11 +935,7 @@ class HipCodec:
         B = len(Hs)
         assert containers.dtype == torch.uint8 and containers.is_cuda and containers.dim() == 2 and containers.shape[0] == B and containers.is_contiguous()
         ws, (src, dst) = self.transcode_workspace(Hs, Ws, src_mode, dst_mode)
-        stride = max(self.max_container_bytes(int(h), int(w)) for h, w in set(zip(Hs.tolist(), Ws.tolist())))
-        if out is None:
-            out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
-        if seg_len_out is None:
-            seg_len_out = torch.zeros((B, NSEG), dtype=torch.int32, device=self.device)
+        out, seg_len_out, _ = self._containers_out(Hs, Ws, out, seg_len_out)
         _lib.check(self.L.llicti_transcode_images(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws),
                                                   _ptr(src), len(src), _ptr(dst), len(dst), _ptr(ws), ws.numel(),
                                                   _ptr(out), out.shape[1], _ptr(seg_len_out), _stream_ptr(self.device)))
@@ -972,6 +954,44 @@ class HipCodec:
         assert sl.ndim == 1 and sl.size >= self.nseg
         return int(self.L.llicti_record_bytes(self.ctx, _ptr(sl)))
 
+    def _record_containers(self, containers, seg_len):
+        """The container side of a record call, checked: device containers uint8 [B, .] whose rows may be strided (one row: its length is the
+        stride) and their seg_len int32 [B, 49] -> (B, the row stride in bytes)"""
+        assert containers.dtype == torch.uint8 and containers.is_cuda and containers.dim() == 2 and containers.stride(1) == 1
+        B = int(containers.shape[0])
+        stride = int(containers.stride(0)) if B > 1 else int(containers.shape[1])
+        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
+        return B, stride
+
+    def _pack_out(self, B, worst, out, rec_off):
+        """The blob side of a pack: the caller's blob and offsets, checked, or new ones (the blob of `worst` bytes) -> (out, rec_off)"""
+        if out is None:
+            out = torch.empty((worst,), dtype=torch.uint8, device=self.device)
+        if rec_off is None:
+            rec_off = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1 and out.stride(0) == 1
+        assert rec_off.dtype == torch.int64 and rec_off.is_cuda and rec_off.numel() == B + 1 and rec_off.is_contiguous()
+        return out, rec_off
+
+    def _unpack_front(self, blob, rec_off, stride, out, seg_len):
+        """The blob side of an unpack: the blob checked, rec_off (a host array / tensor, or a device tensor) on the device, and the containers
+        to write -- the caller's, or new ones of `stride` bytes a row (None: the tight stride of HOST offsets) -- with their seg_len ->
+        (ro_d, B, out, its row stride, seg_len)"""
+        assert blob.dtype == torch.uint8 and blob.is_cuda and blob.dim() == 1 and blob.stride(0) == 1
+        if isinstance(rec_off, torch.Tensor) and rec_off.is_cuda:
+            ro_h, ro_d = None, rec_off
+        else:
+            ro_h = np.ascontiguousarray(rec_off.numpy() if isinstance(rec_off, torch.Tensor) else rec_off, dtype=np.int64)
+            ro_d = torch.from_numpy(ro_h).to(self.device, non_blocking=True)
+        assert ro_d.dtype == torch.int64 and ro_d.dim() == 1 and ro_d.numel() >= 2 and ro_d.is_contiguous()
+        B = ro_d.numel() - 1
+        if out is None:
+            out = torch.empty((B, int(self.tight_stride(ro_h, self.nseg) if stride is None else stride)), dtype=torch.uint8, device=self.device)
+        if seg_len is None:
+            seg_len = torch.empty((B, NSEG), dtype=torch.int32, device=self.device)
+        assert out.shape[0] == B
+        return (ro_d, B, out, self._record_containers(out, seg_len)[1], seg_len)
+
     def pack_records(self, containers, seg_len, out=None, rec_off=None):
         """device containers uint8 [B, stride] + seg_len int32 [B, 49] -> (blob, rec_off): the images' .llic records back to back from blob[0]
         (flat uint8 device tensor) and their offsets, int64 device tensor [B + 1] -- rec_off[b] the first byte of record b, rec_off[B] the
@@ -980,16 +1000,9 @@ class HipCodec:
         write into (its numel is the capacity; None: the worst case, B x (header + stride)); a total above the capacity makes check() raise
         ENOSPACE with rec_off[B] = the capacity needed.  An image whose seg_len row is unusable (a negative entry, a sum above stride) gets a
         zero-length record and EFORMAT in image_status()."""
-        assert containers.dtype == torch.uint8 and containers.is_cuda and containers.dim() == 2 and containers.stride(1) == 1
-        B, stride = int(containers.shape[0]), int(containers.stride(0)) if containers.shape[0] > 1 else int(containers.shape[1])
+        B, stride = self._record_containers(containers, seg_len)
         assert stride >= containers.shape[1]
-        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
-        if out is None:
-            out = torch.empty((B * (6 + 4 * self.nseg + int(containers.shape[1])),), dtype=torch.uint8, device=self.device)
-        if rec_off is None:
-            rec_off = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1 and out.stride(0) == 1
-        assert rec_off.dtype == torch.int64 and rec_off.is_cuda and rec_off.numel() == B + 1 and rec_off.is_contiguous()
+        out, rec_off = self._pack_out(B, B * (6 + 4 * self.nseg + int(containers.shape[1])), out, rec_off)
         _lib.check(self.L.llicti_pack_records(self.ctx, C.c_void_p(containers.data_ptr()), stride, _ptr(seg_len), B,
                                               C.c_void_p(out.data_ptr()), out.numel(), _ptr(rec_off), _stream_ptr(self.device)))
         return out, rec_off
@@ -1007,25 +1020,9 @@ class HipCodec:
         the device before a payload byte is read; one that fails gives an all-zero seg_len row, EFORMAT in image_status() (and check()), and
         leaves its container untouched -- a decode behind it refuses that image the same way.  stride=None: the largest payload rounded up to
         16, from rec_off when that is on the host; with device offsets the caller gives it (the decoders need no more than the payloads)."""
-        assert blob.dtype == torch.uint8 and blob.is_cuda and blob.dim() == 1 and blob.stride(0) == 1
-        if isinstance(rec_off, torch.Tensor) and rec_off.is_cuda:
-            if stride is None and out is None:
-                raise ValueError("unpack_records: with rec_off on the device the caller gives stride (or out)")
-            ro_d = rec_off
-        else:
-            ro_h = np.ascontiguousarray(rec_off.numpy() if isinstance(rec_off, torch.Tensor) else rec_off, dtype=np.int64)
-            if stride is None and out is None:
-                stride = self.tight_stride(ro_h, self.nseg)
-            ro_d = torch.from_numpy(ro_h).to(self.device, non_blocking=True)
-        assert ro_d.dtype == torch.int64 and ro_d.dim() == 1 and ro_d.numel() >= 2 and ro_d.is_contiguous()
-        B = ro_d.numel() - 1
-        if out is None:
-            out = torch.empty((B, int(stride)), dtype=torch.uint8, device=self.device)
-        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1
-        cstride = int(out.stride(0)) if B > 1 else int(out.shape[1])
-        if seg_len is None:
-            seg_len = torch.empty((B, NSEG), dtype=torch.int32, device=self.device)
-        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
+        if stride is None and out is None and isinstance(rec_off, torch.Tensor) and rec_off.is_cuda:
+            raise ValueError("unpack_records: with rec_off on the device the caller gives stride (or out)")
+        ro_d, B, out, cstride, seg_len = self._unpack_front(blob, rec_off, stride, out, seg_len)
         _lib.check(self.L.llicti_unpack_records(self.ctx, C.c_void_p(blob.data_ptr()), blob.numel(), _ptr(ro_d), B,
                                                 C.c_void_p(out.data_ptr()), cstride, _ptr(seg_len), _stream_ptr(self.device)))
         return out, seg_len
@@ -1054,18 +1051,11 @@ class HipCodec:
         blob[0], their offsets (int64 [B + 1]) and every image's prefix lengths P_0 .. P_L (int64 [B, 6]; entries above the model's L: 0), all
         on the device, async.  pack_records' contract: out's numel is the capacity (None: the worst case), ENOSPACE / EFORMAT as there; an
         image whose header, lengths, length tables or cuts do not hold together gets a zero-length record."""
-        assert containers.dtype == torch.uint8 and containers.is_cuda and containers.dim() == 2 and containers.stride(1) == 1
-        B, stride = int(containers.shape[0]), int(containers.stride(0)) if containers.shape[0] > 1 else int(containers.shape[1])
-        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
+        B, stride = self._record_containers(containers, seg_len)
         assert cuts.dtype == torch.int32 and cuts.is_cuda and tuple(cuts.shape) == (B, PROG_MAX_STREAMS, NLEVELS_MAX) and cuts.is_contiguous()
-        if out is None:
-            out = torch.empty((B * (12 + 4 * self.nseg + 4 * PROG_MAX_STREAMS * (self.nlevels + 1) + int(containers.shape[1])),), dtype=torch.uint8, device=self.device)
-        if rec_off is None:
-            rec_off = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        out, rec_off = self._pack_out(B, B * (12 + 4 * self.nseg + 4 * PROG_MAX_STREAMS * (self.nlevels + 1) + int(containers.shape[1])), out, rec_off)
         if prefix is None:
             prefix = torch.empty((B, NLEVELS_MAX + 1), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 1 and out.stride(0) == 1
-        assert rec_off.dtype == torch.int64 and rec_off.is_cuda and rec_off.numel() == B + 1 and rec_off.is_contiguous()
         assert prefix.dtype == torch.int64 and prefix.is_cuda and tuple(prefix.shape) == (B, NLEVELS_MAX + 1) and prefix.is_contiguous()
         _lib.check(self.L.llicti_pack_progressive(self.ctx, C.c_void_p(containers.data_ptr()), stride, _ptr(seg_len), B, _ptr(cuts),
                                                   C.c_void_p(out.data_ptr()), out.numel(), _ptr(rec_off), _ptr(prefix), _stream_ptr(self.device)))
@@ -1079,26 +1069,14 @@ class HipCodec:
         uninitialised tensor as unpack_records makes -- but for the images with r_b = L, whose rows are filled with 0x80: the decoders parse the
         top of every stream whatever the reduce, a zero there is an EFORMAT, and at r_b < L that top is among the delivered bytes; stride as
         unpack_records -- with no `out` the caller gives it: a prefix does not say how long the payload is."""
-        assert blob.dtype == torch.uint8 and blob.is_cuda and blob.dim() == 1 and blob.stride(0) == 1
-        if isinstance(rec_off, torch.Tensor) and rec_off.is_cuda:
-            ro_d = rec_off
-        else:
-            ro_h = np.ascontiguousarray(rec_off.numpy() if isinstance(rec_off, torch.Tensor) else rec_off, dtype=np.int64)
-            ro_d = torch.from_numpy(ro_h).to(self.device, non_blocking=True)
-        assert ro_d.dtype == torch.int64 and ro_d.dim() == 1 and ro_d.numel() >= 2 and ro_d.is_contiguous()
-        B = ro_d.numel() - 1
-        if out is None:
-            if stride is None:
-                raise ValueError("unpack_progressive: the caller gives stride (or out)")
-            out = torch.empty((B, int(stride)), dtype=torch.uint8, device=self.device)
+        fresh = out is None
+        if fresh and stride is None:
+            raise ValueError("unpack_progressive: the caller gives stride (or out)")
+        ro_d, B, out, cstride, seg_len = self._unpack_front(blob, rec_off, stride, out, seg_len)
+        if fresh:
             for b, r in enumerate(np.broadcast_to(np.asarray(reduce), (B,))):
                 if int(r) >= self.nlevels:           # (no stream byte is delivered: the one case in which old bytes meet the decoders' parser)
                     out[b].fill_(0x80)
-        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1
-        cstride = int(out.stride(0)) if B > 1 else int(out.shape[1])
-        if seg_len is None:
-            seg_len = torch.empty((B, NSEG), dtype=torch.int32, device=self.device)
-        assert seg_len.dtype == torch.int32 and seg_len.is_cuda and tuple(seg_len.shape) == (B, NSEG) and seg_len.is_contiguous()
         red = np.ascontiguousarray(np.broadcast_to(np.asarray(reduce, dtype=np.int32), (B,)))
         _lib.check(self.L.llicti_unpack_progressive(self.ctx, C.c_void_p(blob.data_ptr()), blob.numel(), _ptr(ro_d), B, _ptr(red),
                                                     C.c_void_p(out.data_ptr()), cstride, _ptr(seg_len), _stream_ptr(self.device)))

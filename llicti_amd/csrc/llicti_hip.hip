@@ -31,6 +31,7 @@
 #include <string.h>
 #include <map>
 #include <memory>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <type_traits>
@@ -1696,66 +1697,68 @@ extern "C" size_t llicti_record_bytes_n(int n, const int32_t *h_seg_len)
 }
 
 constexpr int kRecMaxBatch = 1 << 20;
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+// One buffer of a record call; a record call's buffers are pairwise disjoint (include/llicti_hip.h)
+struct RecordBuf { const void *p; size_t bytes; const char *name; };
+// What the four record calls have in hand once record_call has admitted them: the model's segment count, the stream, the grid of the copy
+// kernel (x walks the chunks of the longest dense run the call can hold, y the images), the context's device made current until the call returns
+struct RecordCall { int n; hipStream_t s; dim3 grid; std::optional<DeviceGuard> guard; };
+
+// Everything the four record calls do before their launches: refuse a null pointer, a batch, stride or blob out of range, any two buffers that
+// overlap, more chunks than a grid holds (max_dense: the longest run of bytes one image can move); then make room for the B status words.
+static int record_call(RecordCall &rc, const char *who, llicti_ctx *c, int B, size_t stride, size_t blob_bytes, size_t max_dense,
+                       std::initializer_list<RecordBuf> bufs, void *stream)
 {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-// what both record calls refuse before they launch: the blob against the three other buffers of the call
-static int admit_records(const char *who, const llicti_ctx *c, const void *d_cont, size_t stride, const void *d_seg_len, int B,
-                         const void *d_blob, size_t blob_bytes, const void *d_rec_off)
-{
-    if (!c || !d_cont || !d_seg_len || !d_blob || !d_rec_off) return fail(LLICTI_EINVAL, "%s: null pointer", who);
+    if (!c) return fail(LLICTI_EINVAL, "%s: null pointer", who);
+    for (const RecordBuf &u : bufs) if (!u.p) return fail(LLICTI_EINVAL, "%s: null pointer", who);
     if (B < 1 || B > kRecMaxBatch) return fail(LLICTI_EINVAL, "%s: B=%d (need 1 <= B <= %d)", who, B, kRecMaxBatch);
     if (stride < 1 || stride > ((size_t)1 << 62) / (size_t)B) return fail(LLICTI_EINVAL, "%s: stride %zu", who, stride);
     if (blob_bytes > ((size_t)1 << 62)) return fail(LLICTI_EINVAL, "%s: a blob of %zu bytes", who, blob_bytes);
-    if (ranges_overlap(d_blob, blob_bytes, d_cont, (size_t)B * stride)) return fail(LLICTI_EINVAL, "%s: the blob overlaps the containers", who);
-    if (ranges_overlap(d_blob, blob_bytes, d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t))) return fail(LLICTI_EINVAL, "%s: the blob overlaps the segment lengths", who);
-    if (ranges_overlap(d_blob, blob_bytes, d_rec_off, ((size_t)B + 1) * sizeof(int64_t))) return fail(LLICTI_EINVAL, "%s: the blob overlaps the record offsets", who);
-    if (ranges_overlap(d_cont, (size_t)B * stride, d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t)) ||
-        ranges_overlap(d_cont, (size_t)B * stride, d_rec_off, ((size_t)B + 1) * sizeof(int64_t)) ||
-        ranges_overlap(d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t), d_rec_off, ((size_t)B + 1) * sizeof(int64_t)))
-        return fail(LLICTI_EINVAL, "%s: the containers, the segment lengths and the record offsets overlap", who);
-    return 0;
+    for (const RecordBuf *u = bufs.begin(); u != bufs.end(); ++u)
+        for (const RecordBuf *v = u + 1; v != bufs.end(); ++v) {
+            const uintptr_t u0 = (uintptr_t)u->p, v0 = (uintptr_t)v->p;
+            if (u0 < v0 + v->bytes && v0 < u0 + u->bytes) return fail(LLICTI_EINVAL, "%s: %s overlaps %s", who, u->name, v->name);
+        }
+    const size_t chunks = std::max<size_t>(1, (max_dense + kRecChunk - 1) / kRecChunk);
+    if (chunks > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "%s: stride %zu", who, stride);
+    rc.n = 4 + 9 * c->nlev;
+    rc.s = (hipStream_t)stream;
+    rc.grid = dim3((unsigned)chunks, (unsigned)std::min(B, 65535));
+    rc.guard.emplace(c);
+    return reserve_img_status(c, B);
 }
-// grid of the two copy kernels: x walks the chunks of the longest payload the call can hold, y the images
-static dim3 record_grid(size_t max_payload, int B)
+// ... and behind them
+static int record_call_end(llicti_ctx *c, int B)
 {
-    const size_t chunks = std::max<size_t>(1, (max_payload + kRecChunk - 1) / kRecChunk);
-    return dim3((unsigned)std::min<size_t>(chunks, 0x7FFFFFFFu), (unsigned)std::min(B, 65535));
+    HIPCHK(hipGetLastError());
+    c->img_status_n = B;
+    return LLICTI_OK;
 }
+// the sizes of a call's per-image buffers
+static size_t seg_len_bytes(int B) { return (size_t)B * LLICTI_NSEG * sizeof(int32_t); }
+static size_t rec_off_bytes(int B) { return ((size_t)B + 1) * sizeof(int64_t); }
 
 extern "C" int llicti_pack_records(llicti_ctx *c, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B,
                                    uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off, void *stream)
 {
-    if (int rc = admit_records("pack_records", c, d_cont, stride, d_seg_len, B, d_blob, blob_cap, d_rec_off)) return rc;
-    const int n = 4 + 9 * c->nlev;
-    if ((stride + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "pack_records: stride %zu", stride);
-    DeviceGuard guard(c);
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = reserve_img_status(c, B)) return rc;
-    record_scan_kernel<<<1, kRecThreads, 0, s>>>(d_seg_len, B, n, (long)stride, (long)blob_cap, d_rec_off, c->d_status, c->d_img_status);
-    record_pack_kernel<<<record_grid(stride, B), kRecThreads, 0, s>>>(d_cont, (long)stride, d_seg_len, B, n, d_blob, (long)blob_cap, d_rec_off);
-    HIPCHK(hipGetLastError());
-    c->img_status_n = B;
-    return LLICTI_OK;
+    RecordCall rc;
+    if (int e = record_call(rc, "pack_records", c, B, stride, blob_cap, stride, { { d_blob, blob_cap, "the blob" }, { d_cont, (size_t)B * stride, "the containers" },
+                            { d_seg_len, seg_len_bytes(B), "the segment lengths" }, { d_rec_off, rec_off_bytes(B), "the record offsets" } }, stream)) return e;
+    record_offsets_kernel<<<1, kRecThreads, 0, rc.s>>>(RecordSizeOfLengths{ d_seg_len, rc.n, (long)stride, c->d_img_status }, B, (long)blob_cap,
+                                                       d_rec_off, c->d_status);
+    record_pack_kernel<<<rc.grid, kRecThreads, 0, rc.s>>>(d_cont, (long)stride, d_seg_len, B, rc.n, d_blob, (long)blob_cap, d_rec_off);
+    return record_call_end(c, B);
 }
 
 extern "C" int llicti_unpack_records(llicti_ctx *c, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off, int B,
                                      uint8_t *d_cont, size_t stride, int32_t *d_seg_len, void *stream)
 {
-    if (int rc = admit_records("unpack_records", c, d_cont, stride, d_seg_len, B, d_blob, blob_bytes, d_rec_off)) return rc;
-    const int n = 4 + 9 * c->nlev;
-    const size_t max_payload = std::min(stride, blob_bytes);
-    if ((max_payload + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "unpack_records: stride %zu", stride);
-    DeviceGuard guard(c);
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = reserve_img_status(c, B)) return rc;
-    record_check_kernel<<<B, 64, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, n, (long)stride, d_seg_len, c->d_status, c->d_img_status);
-    record_unpack_kernel<<<record_grid(max_payload, B), kRecThreads, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, B, n, d_cont, (long)stride, c->d_img_status);
-    HIPCHK(hipGetLastError());
-    c->img_status_n = B;
-    return LLICTI_OK;
+    RecordCall rc;
+    if (int e = record_call(rc, "unpack_records", c, B, stride, blob_bytes, std::min(stride, blob_bytes), { { d_blob, blob_bytes, "the blob" },
+                            { d_cont, (size_t)B * stride, "the containers" }, { d_seg_len, seg_len_bytes(B), "the segment lengths" },
+                            { d_rec_off, rec_off_bytes(B), "the record offsets" } }, stream)) return e;
+    record_check_kernel<<<B, 64, 0, rc.s>>>(d_blob, (long)blob_bytes, d_rec_off, rc.n, (long)stride, d_seg_len, c->d_status, c->d_img_status);
+    record_unpack_kernel<<<rc.grid, kRecThreads, 0, rc.s>>>(d_blob, (long)blob_bytes, d_rec_off, B, rc.n, d_cont, (long)stride, c->d_img_status);
+    return record_call_end(c, B);
 }
 
 // ------------------------------------------------------------------------------------------------ progressive records
@@ -1772,52 +1775,39 @@ extern "C" int llicti_progressive_prefix(const uint8_t *head, size_t bytes, int6
 extern "C" int llicti_pack_progressive(llicti_ctx *c, const uint8_t *d_cont, size_t stride, const int32_t *d_seg_len, int B, const int32_t *d_cuts,
                                        uint8_t *d_blob, size_t blob_cap, int64_t *d_rec_off, int64_t *d_prefix, void *stream)
 {
-    if (int rc = admit_records("pack_progressive", c, d_cont, stride, d_seg_len, B, d_blob, blob_cap, d_rec_off)) return rc;
-    if (!d_cuts || !d_prefix) return fail(LLICTI_EINVAL, "pack_progressive: null pointer");
-    const size_t cuts_bytes = (size_t)B * kProgMaxStreams * LLICTI_NLEVELS * sizeof(int32_t), prefix_bytes = (size_t)B * (LLICTI_NLEVELS + 1) * sizeof(int64_t);
-    if (ranges_overlap(d_blob, blob_cap, d_cuts, cuts_bytes) || ranges_overlap(d_blob, blob_cap, d_prefix, prefix_bytes) ||
-        ranges_overlap(d_prefix, prefix_bytes, d_cuts, cuts_bytes) || ranges_overlap(d_prefix, prefix_bytes, d_cont, (size_t)B * stride) ||
-        ranges_overlap(d_prefix, prefix_bytes, d_seg_len, (size_t)B * LLICTI_NSEG * sizeof(int32_t)) || ranges_overlap(d_prefix, prefix_bytes, d_rec_off, ((size_t)B + 1) * sizeof(int64_t)))
-        return fail(LLICTI_EINVAL, "pack_progressive: the cuts or the prefix table overlap another buffer of the call");
-    const int n = 4 + 9 * c->nlev;
-    if ((stride + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "pack_progressive: stride %zu", stride);
-    DeviceGuard guard(c);
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = reserve_img_status(c, B)) return rc;
-    prog_measure_kernel<<<B, kProgThreads, 0, s>>>(d_cont, (long)stride, d_seg_len, n, c->nlev, d_cuts, d_prefix, c->d_status, c->d_img_status);
-    prog_scan_kernel<<<1, kRecThreads, 0, s>>>(d_prefix, B, (long)blob_cap, d_rec_off, c->d_status);
-    prog_head_kernel<<<B, kProgThreads, 0, s>>>(d_cont, (long)stride, d_seg_len, n, c->nlev, d_cuts, d_blob, (long)blob_cap, d_rec_off);
+    RecordCall rc;
+    if (int e = record_call(rc, "pack_progressive", c, B, stride, blob_cap, stride, { { d_blob, blob_cap, "the blob" }, { d_cont, (size_t)B * stride, "the containers" },
+                            { d_seg_len, seg_len_bytes(B), "the segment lengths" }, { d_rec_off, rec_off_bytes(B), "the record offsets" },
+                            { d_cuts, (size_t)B * kProgMaxStreams * LLICTI_NLEVELS * sizeof(int32_t), "the cuts" },
+                            { d_prefix, (size_t)B * (LLICTI_NLEVELS + 1) * sizeof(int64_t), "the prefix table" } }, stream)) return e;
+    prog_measure_kernel<<<B, kProgThreads, 0, rc.s>>>(d_cont, (long)stride, d_seg_len, rc.n, c->nlev, d_cuts, d_prefix, c->d_status, c->d_img_status);
+    record_offsets_kernel<<<1, kRecThreads, 0, rc.s>>>(RecordSizeOfPrefix{ d_prefix }, B, (long)blob_cap, d_rec_off, c->d_status);
+    prog_head_kernel<<<B, kProgThreads, 0, rc.s>>>(d_cont, (long)stride, d_seg_len, rc.n, c->nlev, d_cuts, d_blob, (long)blob_cap, d_rec_off);
     ProgReduces none;
     memset(&none, 0, sizeof none);
-    prog_copy_kernel<true><<<record_grid(stride, B), kRecThreads, 0, s>>>(d_blob, (long)blob_cap, d_rec_off, 0, B, none, const_cast<uint8_t *>(d_cont), (long)stride, c->d_img_status);
-    HIPCHK(hipGetLastError());
-    c->img_status_n = B;
-    return LLICTI_OK;
+    prog_copy_kernel<true><<<rc.grid, kRecThreads, 0, rc.s>>>(d_blob, (long)blob_cap, d_rec_off, 0, B, none, const_cast<uint8_t *>(d_cont), (long)stride, c->d_img_status);
+    return record_call_end(c, B);
 }
 
 extern "C" int llicti_unpack_progressive(llicti_ctx *c, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off, int B, const int *reduce,
                                          uint8_t *d_cont, size_t stride, int32_t *d_seg_len, void *stream)
 {
-    if (int rc = admit_records("unpack_progressive", c, d_cont, stride, d_seg_len, B, d_blob, blob_bytes, d_rec_off)) return rc;
     if (!reduce) return fail(LLICTI_EINVAL, "unpack_progressive: null pointer");
-    const int n = 4 + 9 * c->nlev;
-    const size_t max_dense = std::min(stride, blob_bytes);
-    if ((max_dense + kRecChunk - 1) / kRecChunk > 0x7FFFFFFFu) return fail(LLICTI_EINVAL, "unpack_progressive: stride %zu", stride);
-    DeviceGuard guard(c);
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = reserve_img_status(c, B)) return rc;
+    RecordCall rc;
+    if (int e = record_call(rc, "unpack_progressive", c, B, stride, blob_bytes, std::min(stride, blob_bytes), { { d_blob, blob_bytes, "the blob" },
+                            { d_cont, (size_t)B * stride, "the containers" }, { d_seg_len, seg_len_bytes(B), "the segment lengths" },
+                            { d_rec_off, rec_off_bytes(B), "the record offsets" } }, stream)) return e;
     // the reduces are kernel arguments, kProgReduceMax images a launch (a value outside 0 .. 15 travels as 15: the device check refuses it)
     for (int b0 = 0; b0 < B; b0 += kProgReduceMax) {
         const int nb = std::min(kProgReduceMax, B - b0);
         ProgReduces red;
         memset(&red, 0, sizeof red);
         for (int i = 0; i < nb; ++i) red.w[i >> 3] |= (uint32_t)((reduce[b0 + i] < 0 || reduce[b0 + i] > 15) ? 15 : reduce[b0 + i]) << (4 * (i & 7));
-        prog_check_kernel<<<nb, kProgThreads, 0, s>>>(d_blob, (long)blob_bytes, d_rec_off, b0, n, c->nlev, red, (long)stride, d_seg_len, c->d_status, c->d_img_status);
-        prog_copy_kernel<false><<<record_grid(max_dense, nb), kRecThreads, 0, s>>>(const_cast<uint8_t *>(d_blob), (long)blob_bytes, d_rec_off, b0, b0 + nb, red, d_cont, (long)stride, c->d_img_status);
+        prog_check_kernel<<<nb, kProgThreads, 0, rc.s>>>(d_blob, (long)blob_bytes, d_rec_off, b0, rc.n, c->nlev, red, (long)stride, d_seg_len, c->d_status, c->d_img_status);
+        prog_copy_kernel<false><<<dim3(rc.grid.x, (unsigned)nb), kRecThreads, 0, rc.s>>>(const_cast<uint8_t *>(d_blob), (long)blob_bytes, d_rec_off, b0, b0 + nb, red,
+                                                                                         d_cont, (long)stride, c->d_img_status);
     }
-    HIPCHK(hipGetLastError());
-    c->img_status_n = B;
-    return LLICTI_OK;
+    return record_call_end(c, B);
 }
 
 extern "C" int llicti_check_status(llicti_ctx *c, void *stream)

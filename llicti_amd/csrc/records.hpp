@@ -73,47 +73,69 @@ __device__ __forceinline__ void record_copy_chunk(uint8_t *__restrict__ dst, con
     for (int t = head + (nvec << 4) + tid; t < n; t += kRecThreads) dst[t] = src[t];
 }
 
-// pack, step 1 (one workgroup): image b's record size from its n segment lengths -- 6 + 4n + sum, or 0 for a row with a negative entry or a sum
-// above `stride` (LLICTI_EFORMAT for that image) --, the exclusive scan of the sizes into rec_off[0 .. B] (rec_off[B]: the total), and
-// LLICTI_ENOSPACE where the total exceeds blob_cap.  Status goes straight into the context's latched words: the call has no workspace.
-__global__ __launch_bounds__(kRecThreads) void record_scan_kernel(const int32_t *__restrict__ seg_len, int B, int n, long stride, long blob_cap,
-                                                                  int64_t *__restrict__ rec_off, int32_t *latched, int32_t *__restrict__ img_latched)
+// By EVERY thread of a workgroup of kRecThreads: the sum of v over the threads below this one (Hillis-Steele over sh[kRecThreads]); behind it
+// sh[kRecThreads - 1] is the workgroup's total.  A caller that reads sh puts a __syncthreads() between that and its next call.
+__device__ __forceinline__ long long block_exclusive_scan(long long v, long long *sh)
 {
-    __shared__ long long sh[kRecThreads];
-    __shared__ long long carry;
     const int tid = (int)threadIdx.x;
-    if (tid == 0) carry = 0;
+    sh[tid] = v;
     __syncthreads();
-    for (int base = 0; base < B; base += kRecThreads) {
-        const int b = base + tid;
-        long long size = 0;
-        if (b < B) {
-            const int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
-            bool bad = false;
-            long long sum = 0;
-            for (int k = 0; k < n; ++k) {
-                const int v = sl[k];
-                if (v < 0) bad = true; else sum += v;
-            }
-            if (sum > stride) bad = true;
-            size = bad ? 0 : record_header_bytes(n) + sum;
-            img_latched[b] = bad ? LLICTI_EFORMAT : 0;
-            if (bad) atomicExch(latched, LLICTI_EFORMAT);
-        }
-        sh[tid] = size;
+    for (int d = 1; d < kRecThreads; d <<= 1) {
+        const long long t = tid >= d ? sh[tid - d] : 0;
         __syncthreads();
-        for (int d = 1; d < kRecThreads; d <<= 1) {
-            const long long t = tid >= d ? sh[tid - d] : 0;
-            __syncthreads();
-            sh[tid] += t;
-            __syncthreads();
-        }
-        if (b < B) rec_off[b] = carry + sh[tid] - size;
-        __syncthreads();
-        if (tid == kRecThreads - 1) carry += sh[tid];
+        sh[tid] += t;
         __syncthreads();
     }
+    return sh[tid] - v;
+}
+
+// The verdict on image b of a record call, by the threads tid of one workgroup (at least LLICTI_NSEG of them): its seg_len row -- the n
+// lengths (v: thread tid's) of a good record, zeros up to 49 behind them and throughout a refused one --, img_latched[b], and the call's status.
+__device__ __forceinline__ void record_verdict(int b, int tid, int n, bool ok, int32_t v, int32_t *__restrict__ seg_len, int32_t *latched,
+                                               int32_t *__restrict__ img_latched)
+{
+    if (tid < LLICTI_NSEG) seg_len[(long)b * LLICTI_NSEG + tid] = (ok && tid < n) ? v : 0;
     if (tid == 0) {
+        img_latched[b] = ok ? 0 : LLICTI_EFORMAT;
+        if (!ok) atomicExch(latched, LLICTI_EFORMAT);
+    }
+}
+
+// How a thread of record_offsets_kernel obtains image b's record size.  Here: from the image's n segment lengths -- 6 + 4n + sum, or 0 for a
+// row with a negative entry or a sum above `stride`, which is also the image's verdict (LLICTI_EFORMAT).  (The other: RecordSizeOfPrefix.)
+struct RecordSizeOfLengths {
+    const int32_t *seg_len; int n; long stride; int32_t *img_latched;
+    __device__ __forceinline__ long long operator()(int b, int32_t *latched) const
+    {
+        const int32_t *sl = seg_len + (long)b * LLICTI_NSEG;
+        bool bad = false;
+        long long sum = 0;
+        for (int k = 0; k < n; ++k) {
+            const int v = sl[k];
+            if (v < 0) bad = true; else sum += v;
+        }
+        if (sum > stride) bad = true;
+        img_latched[b] = bad ? LLICTI_EFORMAT : 0;
+        if (bad) atomicExch(latched, LLICTI_EFORMAT);
+        return bad ? 0 : record_header_bytes(n) + sum;
+    }
+};
+
+// pack (one workgroup): the exclusive scan of the B record sizes into rec_off[0 .. B] (rec_off[B]: the total), kRecThreads images a round, and
+// LLICTI_ENOSPACE where the total exceeds blob_cap.  Status goes straight into the context's latched words: the call has no workspace.
+template <class SizeOf>
+__global__ __launch_bounds__(kRecThreads) void record_offsets_kernel(const SizeOf size_of, int B, long blob_cap, int64_t *__restrict__ rec_off, int32_t *latched)
+{
+    __shared__ long long sh[kRecThreads];
+    long long carry = 0;                                                // (the same in every thread)
+    for (int base = 0; base < B; base += kRecThreads) {
+        const int b = base + (int)threadIdx.x;
+        const long long before = block_exclusive_scan(b < B ? size_of(b, latched) : 0, sh);
+        if (b < B) rec_off[b] = carry + before;
+        carry += sh[kRecThreads - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
         rec_off[B] = carry;
         if (carry > blob_cap) atomicExch(latched, LLICTI_ENOSPACE);
     }
@@ -169,11 +191,7 @@ __global__ __launch_bounds__(64) void record_check_kernel(const uint8_t *__restr
     unsigned long long sum = v;
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
     ok = ok && (long)sum <= stride && hdr + (long)sum == o1 - o0;
-    if (tid < LLICTI_NSEG) seg_len[(long)b * LLICTI_NSEG + tid] = (ok && tid < n) ? (int32_t)v : 0;
-    if (tid == 0) {
-        img_latched[b] = ok ? 0 : LLICTI_EFORMAT;
-        if (!ok) atomicExch(latched, LLICTI_EFORMAT);
-    }
+    record_verdict(b, tid, n, ok, (int32_t)v, seg_len, latched, img_latched);
 }
 
 // unpack, step 2: grid (chunks, images); workgroup (x, b) copies chunk x of record b's payload to d_cont + b * stride.  The lengths are the ones

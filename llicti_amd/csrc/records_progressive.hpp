@@ -133,36 +133,11 @@ __global__ __launch_bounds__(kProgThreads) void prog_measure_kernel(const uint8_
     }
 }
 
-// pack, step 2 (one workgroup): the exclusive scan of the record sizes P_0 into rec_off[0 .. B], LLICTI_ENOSPACE for a total above blob_cap
-__global__ __launch_bounds__(kRecThreads) void prog_scan_kernel(const int64_t *__restrict__ prefix, int B, long blob_cap, int64_t *__restrict__ rec_off,
-                                                                int32_t *latched)
-{
-    __shared__ long long sh[kRecThreads];
-    __shared__ long long carry;
-    const int tid = (int)threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < B; base += kRecThreads) {
-        const int b = base + tid;
-        const long long size = b < B ? prefix[(long)b * (LLICTI_NLEVELS + 1)] : 0;
-        sh[tid] = size;
-        __syncthreads();
-        for (int d = 1; d < kRecThreads; d <<= 1) {
-            const long long t = tid >= d ? sh[tid - d] : 0;
-            __syncthreads();
-            sh[tid] += t;
-            __syncthreads();
-        }
-        if (b < B) rec_off[b] = carry + sh[tid] - size;
-        __syncthreads();
-        if (tid == kRecThreads - 1) carry += sh[tid];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        rec_off[B] = carry;
-        if (carry > blob_cap) atomicExch(latched, LLICTI_ENOSPACE);
-    }
-}
+// pack, step 2: record_offsets_kernel over the record sizes P_0 of the prefix rows step 1 wrote (its verdicts stand)
+struct RecordSizeOfPrefix {
+    const int64_t *prefix;
+    __device__ __forceinline__ long long operator()(int b, int32_t *) const { return prefix[(long)b * (LLICTI_NLEVELS + 1)]; }
+};
 
 // pack, step 3: a workgroup per image writes the record's fixed bytes, lengths and table (a record that would end past blob_cap is not written)
 __global__ __launch_bounds__(kProgThreads) void prog_head_kernel(const uint8_t *__restrict__ cont, long stride, const int32_t *__restrict__ seg_len,
@@ -236,11 +211,7 @@ __global__ __launch_bounds__(kProgThreads) void prog_check_kernel(const uint8_t 
         prog_prefixes(h, S, (long)sh[2], lvl, prefix);
         ok = o1 - o0 >= prog_prefix_at(prefix, r);
     }
-    if (tid < LLICTI_NSEG) seg_len[(long)b * LLICTI_NSEG + tid] = (ok && tid < n) ? (int32_t)v : 0;
-    if (tid == 0) {
-        img_latched[b] = ok ? 0 : LLICTI_EFORMAT;
-        if (!ok) atomicExch(latched, LLICTI_EFORMAT);
-    }
+    record_verdict(b, tid, n, ok, (int32_t)v, seg_len, latched, img_latched);
 }
 
 // The copy of both directions: grid (chunks, images).  A record's dense side behind its table -- the frame bytes, then the pieces level by
@@ -254,7 +225,7 @@ __global__ __launch_bounds__(kRecThreads) void prog_copy_kernel(uint8_t *__restr
                                                                 const int32_t *__restrict__ img_latched)
 {
     __shared__ long sh_dense[kRecThreads * kProgPer + 1], sh_pay[kRecThreads * kProgPer];
-    __shared__ long sh_scan[kRecThreads];
+    __shared__ long long sh_scan[kRecThreads];
     __shared__ unsigned long long sh_S;
     const int tid = (int)threadIdx.x;
     for (int b = b0 + (int)blockIdx.y; b < b1; b += (int)gridDim.y) {
@@ -284,15 +255,7 @@ __global__ __launch_bounds__(kRecThreads) void prog_copy_kernel(uint8_t *__restr
             if (i < np) prog_piece(rec, h, S, i, &pay[k], &len[k]);
             mine += len[k];
         }
-        sh_scan[tid] = mine;
-        __syncthreads();
-        for (int d = 1; d < kRecThreads; d <<= 1) {
-            const long t = tid >= d ? sh_scan[tid - d] : 0;
-            __syncthreads();
-            sh_scan[tid] += t;
-            __syncthreads();
-        }
-        long at = sh_scan[tid] - mine;
+        long at = (long)block_exclusive_scan(mine, sh_scan);
 #pragma unroll
         for (int k = 0; k < kProgPer; ++k) { sh_dense[tid * kProgPer + k] = at; sh_pay[tid * kProgPer + k] = pay[k]; at += len[k]; }
         if (tid == kRecThreads - 1) sh_dense[kRecThreads * kProgPer] = at;

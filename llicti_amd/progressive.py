@@ -18,7 +18,7 @@ level l (HipCodec.level_cuts), c[m][0] = 0, c[m][L] = len_m; the level-l piece o
 
     P_r = T + F + sum over l >= r and m of (c[m][l+1] - c[m][l]);  P_L = T + F (the header alone: the DC band),  P_0 = T + S (everything)
 
-A `.llpa` archive is `.llia`'s layout (archive.py) around such records: the records back to back, the index -- (count + 1) x u64 offsets,
+A `.llpa` archive is `.llia`'s layout and file layer (archive.py) around such records: the records back to back, the index -- (count + 1) x u64 offsets,
 count x { u16 H, u16 W, u32 mode, u32 P_1 .. P_L }, the names -- and the trailer b"LLPA", u8 version = 1, u8 n, u16 0, u64 count, u64
 index_offset, u32 crc32(index).  `.llia` is unchanged.
 
@@ -26,14 +26,13 @@ Everything in this module is pure Python on the host; the device side is HipCode
 """
 from __future__ import annotations
 
-import mmap
 import struct
-import zlib
 from typing import NamedTuple
 
 import numpy as np
 
 from . import fileio
+from .archive import TRAILER_BYTES, Kind, RecordFileReader, RecordFileWriter
 
 MAGIC = b"LLIP"
 VERSION = 1
@@ -42,8 +41,6 @@ MAX_STREAMS = 128
 MODELS = {49: 5, 22: 2}                 # n -> L
 ARCHIVE_MAGIC = b"LLPA"
 ARCHIVE_VERSION = 1
-TRAILER = struct.Struct("<4sBBHQQI")
-TRAILER_BYTES = TRAILER.size
 EXT = ".llpa"
 
 
@@ -165,137 +162,38 @@ class ProgressiveBatch(NamedTuple):
     reduce: list
 
 
-class ProgressiveWriter:
+def index_row(record, nseg):
+    """A whole progressive record of an archive of `nseg` segments -> its index row (H, W, mode, (P_1 .. P_L)); ValueError as record_meta's."""
+    H, W, mode, h = record_meta(record)
+    if h.n != nseg:
+        raise ValueError(f"a record of {h.n} segments in an archive of {nseg}")
+    return H, W, mode, tuple(h.prefix[1:])
+
+
+LLPA = Kind(ARCHIVE_MAGIC, ARCHIVE_VERSION, lambda nseg: np.dtype([("H", "<u2"), ("W", "<u2"), ("mode", "<u4"), ("P", "<u4", (MODELS[nseg],))]),
+            lambda nseg: table_bytes(nseg, MODELS[nseg], 1), index_row)
+
+
+class ProgressiveWriter(RecordFileWriter):
     """Write a `.llpa` archive: append progressive records (EncodedBatch.records(progressive=True) / HipCodec.pack_progressive), close()."""
-
-    def __init__(self, path, nseg):
-        if int(nseg) not in MODELS:
-            raise ValueError(f"nseg must be one of {sorted(MODELS)} (config B, config A), got {nseg}")
-        self.path, self.nseg = path, int(nseg)
-        self._fh = open(path, "wb")
-        self._offsets = [0]
-        self._meta = []
-        self._names = []
-
-    def __len__(self):
-        return len(self._meta)
-
-    def append_records(self, blob, rec_off, names=None):
-        """blob: bytes-like holding B whole progressive records at rec_off[b] .. rec_off[b + 1]; names: B strings or None."""
-        if self._fh is None:
-            raise ValueError("archive is closed")
-        ro = np.asarray(rec_off, dtype=np.int64).reshape(-1)
-        B = ro.size - 1
-        if B < 0 or (names is not None and len(names) != B):
-            raise ValueError("rec_off holds B + 1 offsets, names B strings")
-        mv = memoryview(blob).cast("B") if not isinstance(blob, np.ndarray) else memoryview(np.ascontiguousarray(blob, dtype=np.uint8)).cast("B")
-        if B and (ro[0] < 0 or (np.diff(ro) < 0).any() or ro[-1] > len(mv)):
-            raise ValueError("record offsets must ascend inside the blob")
-        metas = []
-        for b in range(B):                                  # (all of them before a byte is written)
-            H, W, mode, h = record_meta(mv[int(ro[b]):int(ro[b + 1])])
-            if h.n != self.nseg:
-                raise ValueError(f"a record of {h.n} segments in an archive of {self.nseg}")
-            metas.append((H, W, mode, tuple(h.prefix[1:])))
-        nm = [str(len(self._meta) + b) for b in range(B)] if names is None else [str(s) for s in names]
-        if any("\0" in s for s in nm):
-            raise ValueError("a name holds a NUL")
-        if B:
-            self._fh.write(mv[int(ro[0]):int(ro[B])])
-        base = self._offsets[-1] - (int(ro[0]) if B else 0)
-        self._offsets += [base + int(v) for v in ro[1:]]
-        self._meta += metas
-        self._names += nm
+    KIND = LLPA
 
     def append(self, record, name=None):
         """One progressive record's bytes."""
-        self.append_records(record, [0, len(record)], None if name is None else [name])
-
-    def close(self):
-        if self._fh is None:
-            return
-        L = MODELS[self.nseg]
-        index = np.asarray(self._offsets, dtype="<u8").tobytes()
-        index += b"".join(struct.pack("<HHI%dI" % L, H, W, mode, *pre) for H, W, mode, pre in self._meta)
-        index += b"".join(s.encode("utf-8") + b"\0" for s in self._names)
-        self._fh.write(index)
-        self._fh.write(TRAILER.pack(ARCHIVE_MAGIC, ARCHIVE_VERSION, self.nseg, 0, len(self._meta), self._offsets[-1], zlib.crc32(index) & 0xFFFFFFFF))
-        self._fh.close()
-        self._fh = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._append_one(record, name)
 
 
-class ProgressiveReader:
+class ProgressiveReader(RecordFileReader):
     """Memory-mapped `.llpa` archive.  A bad trailer, an index whose crc32 differs or whose prefix lengths do not descend inside their record is
     a ValueError; the records themselves are validated where they are used (to_llic here, HipCodec.unpack_progressive on the device)."""
+    KIND = LLPA
 
-    def __init__(self, path):
-        self.path = path
-        self._fh = open(path, "rb")
-        try:
-            size = self._fh.seek(0, 2)
-            if size < TRAILER_BYTES:
-                raise ValueError(f"{path}: shorter than an LLPA trailer")
-            self._mm = mmap.mmap(self._fh.fileno(), 0, access=mmap.ACCESS_READ)
-            magic, version, nseg, zero, count, index_offset, crc = TRAILER.unpack(self._mm[size - TRAILER_BYTES:size])
-            if magic != ARCHIVE_MAGIC:
-                raise ValueError(f"{path}: not an LLPA archive (bad magic)")
-            if version != ARCHIVE_VERSION or zero != 0:
-                raise ValueError(f"{path}: unsupported LLPA version {version}")
-            if nseg not in MODELS:
-                raise ValueError(f"{path}: {nseg} segments per record (49 = config A, 22 = config B)")
-            L = MODELS[nseg]
-            index_end = size - TRAILER_BYTES
-            per = 8 + 4 * L
-            if index_offset > index_end or (count + 1) * 8 + count * (per + 1) > index_end - index_offset:
-                raise ValueError(f"{path}: index offset {index_offset} / count {count} do not fit a file of {size} bytes")
-            index = self._mm[index_offset:index_end]
-            if zlib.crc32(index) & 0xFFFFFFFF != crc:
-                raise ValueError(f"{path}: index crc32 mismatch")
-            self.nseg, self.nlevels, self.count, self.index_offset = int(nseg), L, int(count), int(index_offset)
-            self.offsets = np.frombuffer(index, dtype="<u8", count=count + 1).astype(np.int64)
-            if self.offsets[0] != 0 or (np.diff(self.offsets) < table_bytes(nseg, L, 1)).any() or self.offsets[-1] != index_offset:
-                raise ValueError(f"{path}: record offsets do not tile the record region")
-            meta = np.frombuffer(index, dtype=np.dtype([("H", "<u2"), ("W", "<u2"), ("mode", "<u4"), ("P", "<u4", (L,))]), count=count, offset=(count + 1) * 8)
-            self.sizes = [(int(h), int(w)) for h, w in zip(meta["H"], meta["W"])]
-            self.modes = [int(m) for m in meta["mode"]]
-            # prefix[i] = [P_0 .. P_L] of record i: P_0 is the record's length
-            self.prefix = np.concatenate((np.diff(self.offsets)[:, None], meta["P"].astype(np.int64).reshape(count, L)), axis=1)
-            if count and ((np.diff(self.prefix, axis=1) > 0).any() or (self.prefix[:, L] < table_bytes(nseg, L, 1)).any()):
-                raise ValueError(f"{path}: prefix lengths do not descend inside their records")
-            raw = index[(count + 1) * 8 + count * per:]
-            parts = raw.split(b"\0")
-            if len(parts) != count + 1 or parts[-1] != b"":
-                raise ValueError(f"{path}: the index does not hold {count} NUL-terminated names")
-            self.names = [p.decode("utf-8") for p in parts[:-1]]
-            self._u8 = np.frombuffer(self._mm, dtype=np.uint8)
-        except Exception:
-            self.close()
-            raise
-
-    def __len__(self):
-        return self.count
-
-    @property
-    def total_bytes(self):
-        """Bytes of the record region."""
-        return self.index_offset
-
-    def _index(self, i):
-        i = int(i)
-        if not -self.count <= i < self.count:
-            raise IndexError(i)
-        return i % self.count
-
-    def record(self, i) -> bytes:
-        """The bytes of record i: a whole progressive record."""
-        i = self._index(i)
-        return bytes(self._mm[int(self.offsets[i]):int(self.offsets[i + 1])])
+    def _load_rows(self, rows):
+        L = self.nlevels = MODELS[self.nseg]
+        # prefix[i] = [P_0 .. P_L] of record i: P_0 is the record's length
+        self.prefix = np.concatenate((np.diff(self.offsets)[:, None], rows["P"].astype(np.int64).reshape(self.count, L)), axis=1)
+        if self.count and ((np.diff(self.prefix, axis=1) > 0).any() or (self.prefix[:, L] < table_bytes(self.nseg, L, 1)).any()):
+            raise ValueError(f"{self.path}: prefix lengths do not descend inside their records")
 
     def __getitem__(self, i):
         """-> the image's bytestream_list (through to_llic: no GPU)."""
@@ -312,37 +210,15 @@ class ProgressiveReader:
         """The PREFIXES P_{r_b} of the records of `indices` (any order, repeats allowed; reduce: one int or one per image) gathered into ONE
         host buffer of exactly sum P_{r_b} bytes -> ProgressiveBatch.  One memcpy per image out of the mapping: nothing behind a prefix is
         touched.  pinned: a page-locked buffer (one asynchronous H2D copy); without a GPU runtime it is an ordinary one."""
-        import torch
         idx = [self._index(i) for i in indices]
         red = [int(r) for r in np.broadcast_to(np.asarray(reduce, dtype=np.int64), (len(idx),))]
         if any(not 0 <= r <= self.nlevels for r in red):
             raise ValueError(f"reduce outside 0 .. {self.nlevels}")
         lens = np.array([self.prefix[i, r] for i, r in zip(idx, red)], dtype=np.int64)
-        rec_off = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
-        blob = torch.empty((max(1, int(rec_off[-1])),), dtype=torch.uint8, pin_memory=bool(pinned and torch.cuda.is_available()))
-        dst = blob.numpy()
+        blob, dst, rec_off = self._host_blob(lens, pinned)
         for k, i in enumerate(idx):
             s0 = int(self.offsets[i])
             dst[int(rec_off[k]):int(rec_off[k + 1])] = self._u8[s0:s0 + int(lens[k])]
         pay = max((self.payload_bytes(i) for i in idx), default=0)
         stride = max(16, (pay + 15) // 16 * 16)
-        return ProgressiveBatch(blob[:max(1, int(rec_off[-1]))], rec_off, [self.sizes[i][0] for i in idx], [self.sizes[i][1] for i in idx],
-                                [self.modes[i] for i in idx], stride, red)
-
-    def close(self):
-        self._u8 = None
-        mm, self._mm = getattr(self, "_mm", None), None
-        if mm is not None:
-            try:
-                mm.close()
-            except BufferError:          # (a caller still holds a view of the mapping: it goes with the last view)
-                pass
-        fh, self._fh = getattr(self, "_fh", None), None
-        if fh is not None:
-            fh.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return ProgressiveBatch(blob[:max(1, int(rec_off[-1]))], rec_off, [self.sizes[i][0] for i in idx], [self.sizes[i][1] for i in idx], [self.modes[i] for i in idx], stride, red)

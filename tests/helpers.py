@@ -199,6 +199,32 @@ class StreamGate:
         return e0, e1
 
 
+# ---- device buffers of the record tests (tests/test_hip_archive.py, tests/test_hip_progressive.py)
+DEV = "cuda:0"
+POISON = 0xA5
+GUARD = 64
+
+
+def _dev(torch, a):
+    return torch.from_numpy(np.array(a, order="C")).to(DEV)           # (a writable copy: some inputs are views of `bytes`)
+
+
+def guarded(torch, nbytes, offset=0):
+    """-> (buffer, view, base): a poisoned buffer with GUARD bytes before and at least GUARD after a view of nbytes that starts `offset` bytes
+    past a 256-byte boundary"""
+    buf = torch.full((256 + GUARD + offset + nbytes + GUARD + 16,), POISON, dtype=torch.uint8, device=DEV)
+    base = (-buf.data_ptr()) % 256 + GUARD + offset
+    if base < GUARD:
+        base += 256
+    view = buf[base:base + nbytes]
+    assert view.data_ptr() % 16 == offset % 16
+    return buf, view, base
+
+
+def guards_intact(buf, base, nbytes):
+    return bool((buf[:base] == POISON).all()) and bool((buf[base + nbytes:] == POISON).all())
+
+
 def crop_windows(img, y0, x0, ch=None, cw=None, margin=2, levels=5):
     """A crop of a large image that the CPU oracle can afford, and where the crop's band grids equal the image's (tests/test_large_cpu.py holds the
     rule on the oracle; tests/test_hip_large.py uses it on images the oracle cannot run whole).  The band CNN is local -- a 5x5 window of its band

@@ -1,5 +1,5 @@
 """numpy restatement of llicti_pack_records / llicti_unpack_records (include/llicti_hip.h, "RECORDS") -- what the device must write, byte for
-byte, the validation verdicts and what a refused record leaves behind included -- and a second, literal reader of the `.llia` archive layout
+byte, the validation verdicts and what a refused record leaves behind included -- and a second, literal reader of the `.llia` / `.llpa` archive layout
 that shares no code with llicti_amd/archive.py ("Image archives").  Test infrastructure: nothing here imports the package."""
 from __future__ import annotations
 
@@ -141,16 +141,16 @@ def malformed_cases(n):
             "payload_larger_than_stride": (big_payload, 1)}
 
 
-# ---------------------------------------------------------------------------------------------- .llia, read literally
-def read_llia(buf: bytes):
-    """A `.llia` file's bytes -> dict(n, count, offsets, sizes, modes, names, records), straight from the written layout:
-         records | (count + 1) x u64 | count x (u16 H, u16 W, u32 mode) | count NUL-terminated UTF-8 names |
-         b"LLIA" u8 version u8 n u16 0 u64 count u64 index_offset u32 crc32(index)
-    ValueError for anything that contradicts it."""
+# ---------------------------------------------------------------------------------------------- .llia and .llpa, read literally
+def read_archive(buf: bytes, magic: bytes, extra_words: int):
+    """An archive file's bytes -> dict(n, count, offsets, sizes, modes, extra, names, records), straight from the written layout:
+         records | (count + 1) x u64 | count x (u16 H, u16 W, u32 mode, extra_words x u32) | count NUL-terminated UTF-8 names |
+         magic u8 version u8 n u16 0 u64 count u64 index_offset u32 crc32(index)
+    extra: per record its extra_words words (`.llpa`: P_1 .. P_L, so extra_words = L).  ValueError for anything that contradicts it."""
     if len(buf) < 28:
         raise ValueError("too short for a trailer")
     t = buf[-28:]
-    if t[0:4] != b"LLIA":
+    if t[0:4] != magic:
         raise ValueError("magic")
     version, n = t[4], t[5]
     (zero,) = struct.unpack_from("<H", t, 6)
@@ -166,16 +166,18 @@ def read_llia(buf: bytes):
     index = buf[index_offset:end]
     if zlib.crc32(index) & 0xFFFFFFFF != crc:
         raise ValueError("crc")
-    if len(index) < (count + 1) * 8 + count * 8:
+    per = 8 + 4 * extra_words
+    if len(index) < (count + 1) * 8 + count * per:
         raise ValueError("index too short")
     offsets = [struct.unpack_from("<Q", index, 8 * k)[0] for k in range(count + 1)]
     pos = (count + 1) * 8
-    sizes, modes = [], []
+    sizes, modes, extra = [], [], []
     for k in range(count):
-        H, W, mode = struct.unpack_from("<HHI", index, pos + 8 * k)
+        H, W, mode = struct.unpack_from("<HHI", index, pos + per * k)
         sizes.append((H, W))
         modes.append(mode)
-    pos += 8 * count
+        extra.append(list(struct.unpack_from("<%dI" % extra_words, index, pos + per * k + 8)))
+    pos += per * count
     names = []
     for k in range(count):
         e = index.index(b"\0", pos)
@@ -185,5 +187,10 @@ def read_llia(buf: bytes):
         raise ValueError("bytes behind the names")
     if offsets[0] != 0 or offsets[-1] != index_offset or any(a > b for a, b in zip(offsets, offsets[1:])):
         raise ValueError("offsets")
-    return dict(n=n, count=count, offsets=offsets, sizes=sizes, modes=modes, names=names,
+    return dict(n=n, count=count, offsets=offsets, sizes=sizes, modes=modes, extra=extra, names=names,
                 records=[buf[offsets[k]:offsets[k + 1]] for k in range(count)])
+
+
+def read_llia(buf: bytes):
+    """A `.llia` file's bytes, read literally: read_archive with its magic and no extra index words."""
+    return read_archive(buf, b"LLIA", 0)

@@ -10,19 +10,12 @@ import numpy as np
 import pytest
 
 import ref_records as rr
-from helpers import make_image
+from helpers import DEV, GUARD, POISON, _dev, guarded, guards_intact, make_image          # noqa: F401
 from test_hip_streams import Run, codecs, env, torch_mod          # noqa: F401  (the gated queue and its fixtures; that file stays as it is)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-POISON = 0xA5
-GUARD = 64
 MIXED = [(32, 32), (33, 35), (67, 93), (64, 96)]
-
-
-def _dev(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)           # (a writable copy: some inputs are views of `bytes`)
 
 
 def _mode(name):
@@ -60,22 +53,6 @@ def llic_files(cont_np, seg_np, nlevels):
     from llicti_amd import fileio
     from llicti_amd.codec import container_to_bytestream_list
     return [fileio.dumps_llic(container_to_bytestream_list(cont_np[b], seg_np[b], nlevels=nlevels)) for b in range(len(cont_np))]
-
-
-def guarded(torch, nbytes, offset=0):
-    """-> (buffer, view): a poisoned buffer with GUARD bytes before and at least GUARD after a view of nbytes that starts `offset` bytes past a
-    256-byte boundary"""
-    buf = torch.full((256 + GUARD + offset + nbytes + GUARD + 16,), POISON, dtype=torch.uint8, device=DEV)
-    base = (-buf.data_ptr()) % 256 + GUARD + offset
-    if base < GUARD:
-        base += 256
-    view = buf[base:base + nbytes]
-    assert view.data_ptr() % 16 == offset % 16
-    return buf, view, base
-
-
-def guards_intact(buf, base, nbytes):
-    return bool((buf[:base] == POISON).all()) and bool((buf[base + nbytes:] == POISON).all())
 
 
 def decoded_images(torch, c, cont, seg, sizes, mode):
@@ -350,6 +327,50 @@ def test_host_side_refusals_launch_nothing(torch_mod, codecs):
     torch.cuda.synchronize()
     c.check()
     assert bool((cont == POISON).all()) and bool((blob == POISON).all()) and bool((ro == -7).all()) and bool((seg == 0).all())
+
+
+@pytest.mark.parametrize("B", [257, 513])
+def test_more_images_than_one_round_of_the_scan(torch_mod, codecs, B):
+    """The offsets come from a scan of 256 images a round: B = 257 and 513 make the total of a round carry into the next one (two and three
+    rounds, the last of ONE image), with a malformed row / record at index 256, the first of the second round.  Synthetic containers of 22
+    segments against the numpy restatement: offsets, blob, containers, and every image's status -- the bad one's neighbours included."""
+    torch = torch_mod
+    from llicti_amd import _lib
+    c = codecs("b_trainedlike")
+    n, stride, bad = c.nseg, 160, 256
+    assert n == 22
+    cont_np, seg_np = rr.synthetic_containers(np.random.default_rng(B), B, n, stride)
+    # pack: row 256 has a negative length
+    seg_bad = seg_np.copy()
+    seg_bad[bad, 7] = -1
+    cap = sum(rr.record_size(seg_bad[b], n, stride) for b in range(B)) + 7
+    ref_blob, ref_off, ref_img, ref_st = rr.pack(cont_np, seg_bad, n, np.full(cap, POISON, np.uint8))
+    assert ref_st == _lib.EFORMAT and ref_off[bad] == ref_off[bad + 1] and ref_off[-1] == cap - 7
+    buf, view, base = guarded(torch, cap, 3)
+    ro = torch.full((B + 1,), -7, dtype=torch.int64, device=DEV)
+    c.pack_records(_dev(torch, cont_np), _dev(torch, seg_bad), out=view, rec_off=ro)
+    status = c.image_status(B)
+    with pytest.raises(_lib.LlictiError) as ei:
+        c.check()
+    assert ei.value.code == _lib.EFORMAT
+    assert np.array_equal(ro.cpu().numpy(), ref_off) and np.array_equal(view.cpu().numpy(), ref_blob) and guards_intact(buf, base, cap)
+    assert np.array_equal(status, ref_img) and list(status[bad - 1:bad + 2]) == [0, _lib.EFORMAT, 0][:B - bad + 1]
+    # unpack: the well-formed blob with record 256's magic damaged
+    good_blob, good_off, img0, st0 = rr.pack(cont_np, seg_np, n, np.zeros(int(ref_off[-1]) + stride + 6 + 4 * n, np.uint8))
+    assert st0 == rr.OK and (img0 == 0).all()
+    blob_np = good_blob[:good_off[-1]].copy()
+    blob_np[good_off[bad] + 2] ^= 0x40
+    ref_cont, ref_seg, ref_img, ref_st = rr.unpack(blob_np, good_off, n, np.full((B, stride), POISON, np.uint8))
+    assert ref_st == _lib.EFORMAT and (ref_cont[bad] == POISON).all()
+    cbuf, cflat, cbase = guarded(torch, B * stride, 5)
+    seg = torch.full((B, 49), -3, dtype=torch.int32, device=DEV)
+    c.unpack_records(_dev(torch, blob_np), good_off, out=cflat.view(B, stride), seg_len=seg)
+    status = c.image_status(B)
+    with pytest.raises(_lib.LlictiError) as ei:
+        c.check()
+    assert ei.value.code == _lib.EFORMAT
+    assert np.array_equal(cflat.view(B, stride).cpu().numpy(), ref_cont) and np.array_equal(seg.cpu().numpy(), ref_seg) and guards_intact(cbuf, cbase, B * stride)
+    assert np.array_equal(status, ref_img) and list(status[bad - 1:bad + 2]) == [0, _lib.EFORMAT, 0][:B - bad + 1]
 
 
 # ------------------------------------------------------------------------------------------------ 6. offsets past 4 GiB

@@ -10,13 +10,10 @@ import pytest
 import ref_progressive as rp
 import ref_rans as rr
 from conftest import GOLDEN, load_state_dict
-from helpers import StreamGate, make_image
+from helpers import DEV, GUARD, POISON, StreamGate, _dev, guarded, guards_intact, make_image          # noqa: F401
 from test_hip_ref_rans import HipPlanes, _segs
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-POISON = 0xA5
-GUARD = 64
 EFORMAT = -5
 sys.path.insert(0, GOLDEN)
 
@@ -50,10 +47,6 @@ def codecs(torch_mod):
         c.close()
 
 
-def _dev(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)
-
-
 def _mode(c, name, H, W):
     """The encoder mode of a container name.  "auto" is the size rule's xwide mode (MODE_RANS_AUTO: the encoder picks the count); an image
     too small for the rule to give it an xwide stream (below ~160 x 160: container "auto" codes it in 64 lanes, which level_cuts refuses --
@@ -62,21 +55,6 @@ def _mode(c, name, H, W):
     if name != "auto":
         return cd.mode_of_name(name)
     return cd.MODE_RANS_AUTO(max(1, cd.image_streams(H, W, c.nlevels)))
-
-
-def guarded(torch, nbytes, offset=0):
-    """-> (buffer, view, base): a poisoned buffer with GUARD bytes before and after a view of nbytes that starts `offset` bytes past a 256-byte boundary"""
-    buf = torch.full((256 + GUARD + offset + nbytes + GUARD + 16,), POISON, dtype=torch.uint8, device=DEV)
-    base = (-buf.data_ptr()) % 256 + GUARD + offset
-    if base < GUARD:
-        base += 256
-    view = buf[base:base + nbytes]
-    assert view.data_ptr() % 16 == offset % 16
-    return buf, view, base
-
-
-def guards_intact(buf, base, nbytes):
-    return bool((buf[:base] == POISON).all()) and bool((buf[base + nbytes:] == POISON).all())
 
 
 class Built:
@@ -293,7 +271,72 @@ def test_config_b(torch_mod, codecs):
     assert c.image_status(1)[0] == EFORMAT and not seg.any() and bool((out == POISON).all())
 
 
+def test_more_images_than_one_launch_of_the_unpack(torch_mod, codecs):
+    """B = 1025: five rounds of the pack's offset scan (256 images each, the last of one) and two launches of the unpack kernels (1024 images'
+    reduces travel with a launch, the second carries ONE).  One config B container tiled on the device with its cuts, reduces cycling
+    0 .. L: every record and every unpacked container against the single image's, the offsets against the cumulative sizes."""
+    torch = torch_mod
+    c = codecs("b_rand1337")
+    b = built(torch, c, "b_rand1337", [(40, 33)], ["xrans3"])
+    B, L, rec = 1025, c.nlevels, b.rec[0]
+    stride = (b.S[0] + 15) // 16 * 16
+    blob, ro, pre = c.pack_progressive(b.cont[:, :stride].repeat(B, 1), b.seg.repeat(B, 1), b.cuts.repeat(B, 1, 1))
+    c.check()
+    assert (c.image_status(B) == 0).all()
+    assert ro.tolist() == [len(rec) * k for k in range(B + 1)] and pre.tolist() == [rp.prefixes(rec) + [0, 0, 0]] * B
+    assert torch.equal(blob[:B * len(rec)].view(B, len(rec)), _dev(torch, np.frombuffer(rec, np.uint8)).expand(B, -1))
+    reds = [k % (L + 1) for k in range(B)]
+    assert reds[1022:] == [2, 0, 1]                                          # images 1023, 1024 and 1025: one on either side of the launch boundary
+    cuts_at = rp.prefixes(rec)
+    ro_h = np.concatenate(([0], np.cumsum([cuts_at[r] for r in reds]))).astype(np.int64)
+    cbuf, cflat, cbase = guarded(torch, B * stride, 5)
+    out = cflat.view(B, stride)
+    seg = torch.full((B, 49), -3, dtype=torch.int32, device=DEV)
+    c.unpack_progressive(_dev(torch, np.frombuffer(b"".join(rec[:cuts_at[r]] for r in reds), np.uint8)), ro_h, reduce=reds, out=out, seg_len=seg)
+    c.check()
+    assert (c.image_status(B) == 0).all() and guards_intact(cbuf, cbase, B * stride)
+    want = np.stack([expect_unpacked(b, [r], stride)[0] for r in range(L + 1)])          # the single image at each reduce
+    assert len({w.tobytes() for w in want}) == L + 1
+    assert torch.equal(out, _dev(torch, want)[torch.tensor(reds, device=DEV)]) and torch.equal(seg, b.seg.expand(B, -1))
+    for k in (1022, 1023, 1024):
+        assert np.array_equal(out[k].cpu().numpy(), want[reds[k]]), k
+
+
 # ------------------------------------------------------------------------------------------------ 3. what is refused
+def test_pack_refuses_cuts_that_overlap_another_buffer(torch_mod, codecs):
+    """All buffers of a record call are pairwise disjoint: d_cuts over d_rec_off, the containers or the segment lengths is LLICTI_EINVAL
+    before anything is launched -- the error names both, and the poisoned outputs stay as they were."""
+    import ctypes as C
+    torch = torch_mod
+    from llicti_amd._lib import EINVAL
+    c = codecs("trainedlike")
+    s = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+    B, cuts_bytes = 2, 2 * 128 * 5 * 4
+    # one arena, so that what lies next to every buffer is known: at least cuts_bytes of nobody's bytes in front of seg_len and rec_off
+    at = dict(cont=0, seg=24576, ro=32768, blob=36864, pre=40960, cuts=45056)
+    arena = torch.full((51200,), POISON, dtype=torch.uint8, device=DEV)
+    arena[at["seg"]:at["seg"] + 4 * 49 * B] = 0
+    before = arena.clone()
+    p = lambda name, off=0: C.c_void_p(arena.data_ptr() + at[name] + off)
+    err = lambda: c.L.llicti_last_error().decode()
+
+    def pack(cuts, ro=p("ro"), pre=p("pre")):
+        return c.L.llicti_pack_progressive(c.ctx, p("cont"), 8192, p("seg"), B, cuts, p("blob"), 4096, ro, pre, s)
+    assert pack(p("ro", 8 - cuts_bytes)) == EINVAL and "the cuts" in err() and "the record offsets" in err()       # the cuts' last 8 bytes are d_rec_off[0]
+    assert pack(p("cont", 4096)) == EINVAL and "the cuts" in err() and "the containers" in err()
+    assert pack(p("seg", 4 - cuts_bytes)) == EINVAL and "the cuts" in err() and "the segment lengths" in err()
+    assert pack(p("cuts"), pre=p("ro", 16)) == EINVAL and "the prefix table" in err() and "the record offsets" in err()      # (refused before, too)
+    torch.cuda.synchronize()
+    c.check()
+    assert torch.equal(arena, before)
+    assert pack(p("cuts")) == 0                                              # the same call with disjoint buffers is admitted
+    with pytest.raises(Exception):
+        c.check()                                                            # (all-zero length rows: no records, EFORMAT)
+    ro = arena[at["ro"]:at["ro"] + 8 * (B + 1)].view(torch.int64)
+    assert c.image_status(B).tolist() == [EFORMAT, EFORMAT] and ro.tolist() == [0, 0, 0] and torch.equal(arena[at["blob"]:at["blob"] + 4096], before[at["blob"]:at["blob"] + 4096])
+
+
+# ------------------------------------------------------------------------------------------------ 3b. level_cuts
 def test_level_cuts_refuses_other_containers_and_flags_a_corrupt_one_alone(torch_mod, codecs):
     torch = torch_mod
     from llicti_amd._lib import EINVAL, LlictiError
