@@ -454,6 +454,69 @@ int llicti_decode_images_tensor_views_rv(llicti_ctx *ctx, const uint8_t *d_in, s
                                          int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
                                          void *d_workspace, size_t workspace_bytes,
                                          const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream);
+/* TENSOR OPTIONS: the three tensor decodes with a trailing `opts` -- the memory LAYOUT of the output and, for llicti_decode_images_tensor_o
+ * alone, windows PADDED past their image.  `reduces` is the _rv contract above (B values; all equal is the scalar call).  opts == NULL, or
+ * { LLICTI_LAYOUT_NCHW, LLICTI_PAD_NONE }, IS the _rv sibling (it delegates): same launches, plan key, counters, bytes and status words.
+ * Nothing cached depends on opts: layout, pad mode, fill, origins and flips are kernel arguments of the decode's last kernel, so calls with
+ * fresh values hit the plan the reduced decode builds for the same sizes, modes and reduce, and neither allocate nor synchronise.
+ *   layout     LLICTI_LAYOUT_NCHW: [B][3][Ho][Wo] planes.  LLICTI_LAYOUT_NHWC: element (b, i, j, c) at ((b * Ho + i) * Wo + j) * 3 + c -- the
+ *              memory of a [B, 3, Ho, Wo] tensor in torch.channels_last, strides (3 Ho Wo, 1, 3 Wo, 3).  The VALUES are the planar call's.  A
+ *              lane's 4 pixels x 3 channels are 12 consecutive elements: 16-byte stores (16 + 8 for the 16-bit types) when Wo % 4 == 0 and d_out
+ *              is 16-byte aligned, element by element otherwise -- the same bytes either way.  In the views call it holds for every group.
+ *   pad_mode   llicti_decode_images_tensor_o only; the other two refuse anything but LLICTI_PAD_NONE (a box that leaves its image stays refused).
+ * A PADDED WINDOW, to the operation.  Image b's decoded grid is Hr x Wr (llicti_reduced_dims at that image's reduce), extended in both axes by
+ * the pad mode.  The Ho x Wo window at origin (y0, x0) -- either may be NEGATIVE -- is cut from the extended plane; a set flip then mirrors the
+ * window: output column j is window column Wo - 1 - j.  Per axis (n the grid's extent), coordinate t in y0 .. y0 + Ho - 1 (x0 .. x0 + Wo - 1)
+ * maps to a source index in 0 .. n - 1 or to "fill" (llicti_pad_index):
+ *   0 <= t < n              t, under every mode
+ *   LLICTI_PAD_CONSTANT     fill
+ *   LLICTI_PAD_EDGE         0 for t < 0, n - 1 for t >= n                      (numpy 'edge', torch 'replicate')
+ *   LLICTI_PAD_REFLECT      -t for t < 0, 2 (n - 1) - t for t >= n             (numpy / torch 'reflect', period 2 n - 2: the edge pixel is not
+ *                           repeated); an overhang of more than n - 1 on a side is refused, as torch refuses it -- n == 1 with any overhang is
+ *   LLICTI_PAD_SYMMETRIC    -t - 1 for t < 0, 2 n - 1 - t for t >= n           (numpy 'symmetric', period 2 n: the edge pixel is repeated); an
+ *                           overhang of more than n on a side is refused
+ * An output pixel whose row AND column map to source indices (sy, sx) is the 8-bit value behind the inverse YCoCg-R of decoded pixel (sy, sx)
+ * through the ARITHMETIC of llicti_decode_images_tensor, unchanged.  One whose row or column maps to "fill" holds, in channel c:
+ *   LLICTI_FILL_PIXEL       fill[c] taken as a value on the 0 .. 255 scale through that same arithmetic: (fill[c] / 255.0f - mean[c]) / std[c],
+ *                           rounded to dtype -- torchvision's Pad(fill) + ToTensor + Normalize bit for bit for integer fills
+ *   LLICTI_FILL_OUTPUT      fill[c] itself, rounded to dtype and nothing else (the "pad with 0 after normalising" collate)
+ * LLICTI_PAD_CONSTANT and LLICTI_PAD_EDGE do not need the window to overlap the image.  With LLICTI_PAD_NONE the window must lie inside it, as
+ * in llicti_decode_images_tensor; a window inside its image gives that call's bytes under every pad mode.
+ * Nothing outside [d_out, d_out + B * 3 * Ho * Wo * elem) is written in either layout.
+ * LLICTI_EINVAL before anything is launched, naming the image: an unknown layout, pad mode or fill space; a fill that is not finite; with a pad
+ * mode, Ho or Wo outside 1 .. 8160, an origin outside -8160 .. 8160, LLICTI_PAD_REFLECT overhanging a side by more than n - 1,
+ * LLICTI_PAD_SYMMETRIC by more than n; a pad mode in the resized or views call; and everything the _rv sibling refuses.
+ * Host helpers (no device needed), compiled from the function the kernel calls: llicti_pad_index -- the source index of coordinate t on an axis
+ * of n pixels under `mode` (LLICTI_PAD_NONE: inside or refused), -1 for "fill", -2 for refused (n outside 1 .. 8160, |t| above 2^20 and an unknown mode too);
+ * llicti_tensor_window_pad_ok -- 1 if llicti_decode_images_tensor_o takes that window of an H x W image at `reduce` under `mode`, else 0. */
+#define LLICTI_LAYOUT_NCHW 0
+#define LLICTI_LAYOUT_NHWC 1
+#define LLICTI_PAD_NONE 0
+#define LLICTI_PAD_CONSTANT 1
+#define LLICTI_PAD_EDGE 2
+#define LLICTI_PAD_REFLECT 3
+#define LLICTI_PAD_SYMMETRIC 4
+#define LLICTI_FILL_PIXEL 0
+#define LLICTI_FILL_OUTPUT 1
+typedef struct llicti_tensor_opts { int layout, pad_mode, fill_space; float fill[3]; } llicti_tensor_opts;
+int llicti_pad_index(int n, int t, int mode);
+int llicti_tensor_window_pad_ok(int H, int W, int reduce, int y0, int x0, int Ho, int Wo, int mode);
+int llicti_decode_images_tensor_o(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                  int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                  void *d_workspace, size_t workspace_bytes,
+                                  void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
+                                  const float *mean, const float *std, void *stream, const llicti_tensor_opts *opts);
+int llicti_decode_images_tensor_resized_o(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                          int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                          void *d_workspace, size_t workspace_bytes,
+                                          void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
+                                          const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream,
+                                          const llicti_tensor_opts *opts);
+int llicti_decode_images_tensor_views_o(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                        int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                        void *d_workspace, size_t workspace_bytes,
+                                        const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream,
+                                        const llicti_tensor_opts *opts);
 /* llicti_encode_images_vm on planar float32: image b's [3][Hs[b]][Ws[b]] block at ELEMENT offset x_off[b] of d_x (NULL = the blocks back to back
  * in call order).  A sample x becomes the pixel value v = (int)rintf(x * 255.0f) -- one rounded fp32 product, rounded half to even
  * (torch.round) --, clamped to 0 .. 255, a NaN gives 0; containers and segment lengths are byte for byte those of the uint8 call on v, under

@@ -67,6 +67,11 @@ class ViewGroup(C.Structure):
                 ("image", C.c_void_p), ("y0", C.c_void_p), ("x0", C.c_void_p), ("hs", C.c_void_p), ("ws", C.c_void_p), ("flip", C.c_void_p)]
 
 
+class TensorOpts(C.Structure):
+    """llicti_tensor_opts of include/llicti_hip.h: the output's layout (LLICTI_LAYOUT_*), the pad mode of a window (LLICTI_PAD_*), the fill"""
+    _fields_ = [("layout", C.c_int), ("pad_mode", C.c_int), ("fill_space", C.c_int), ("fill", C.c_float * 3)]
+
+
 _SIGS = {
     "llicti_last_error": (C.c_char_p, []),
     "llicti_version": (C.c_char_p, []),
@@ -112,6 +117,13 @@ _SIGS = {
     "llicti_decode_images_tensor_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "llicti_decode_images_tensor_resized_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "llicti_decode_images_tensor_views_rv": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, C.POINTER(ViewGroup), _i, _vp, _vp, _vp]),
+    # tensor options: the _rv siblings with a trailing `const llicti_tensor_opts *` (NULL: the sibling itself), and the two host helpers
+    "llicti_pad_index": (_i, [_i] * 3),
+    "llicti_tensor_window_pad_ok": (_i, [_i] * 8),
+    "llicti_decode_images_tensor_o": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(TensorOpts)]),
+    "llicti_decode_images_tensor_resized_o": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                                   C.POINTER(TensorOpts)]),
+    "llicti_decode_images_tensor_views_o": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, C.POINTER(ViewGroup), _i, _vp, _vp, _vp, C.POINTER(TensorOpts)]),
     "llicti_encode_images_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_max_container_bytes": (_sz, [_i, _i]),
     "llicti_transcode_workspace_bytes": (_sz, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i]),

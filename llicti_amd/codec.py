@@ -278,6 +278,66 @@ def tensor_window_ok(H, W, reduce, y0, x0, Ho, Wo) -> bool:
     return bool(_lib.lib().llicti_tensor_window_ok(int(H), int(W), int(reduce), int(y0), int(x0), int(Ho), int(Wo)))
 
 
+# Tensor options (llicti_tensor_opts): layouts, pad modes and fill spaces by the names the Python calls take
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+PAD_NONE, PAD_CONSTANT, PAD_EDGE, PAD_REFLECT, PAD_SYMMETRIC = 0, 1, 2, 3, 4
+FILL_PIXEL, FILL_OUTPUT = 0, 1
+PAD_MODES = {"constant": PAD_CONSTANT, "edge": PAD_EDGE, "reflect": PAD_REFLECT, "symmetric": PAD_SYMMETRIC}
+FILL_SPACES = {"pixel": FILL_PIXEL, "output": FILL_OUTPUT}
+
+
+def pad_index(n, t, mode) -> int:
+    """Where coordinate t of a padded window lands on an axis of n pixels under `mode` (a name of PAD_MODES or LLICTI_PAD_*): the source index in
+    0 .. n - 1, -1 for "fill", -2 for refused (llicti_pad_index: the function the kernel calls, compiled for the host; works without a device)."""
+    return int(_lib.lib().llicti_pad_index(int(n), int(t), int(PAD_MODES.get(mode, mode))))
+
+
+def tensor_window_pad_ok(H, W, reduce, y0, x0, Ho, Wo, mode) -> bool:
+    """Whether decode_tensor(pad=dict(mode=...)) takes the Ho x Wo window at (y0, x0) -- either may be negative -- of an H x W image decoded at
+    `reduce` (llicti_tensor_window_pad_ok, works without a device)."""
+    return bool(_lib.lib().llicti_tensor_window_pad_ok(int(H), int(W), int(reduce), int(y0), int(x0), int(Ho), int(Wo), int(PAD_MODES.get(mode, mode))))
+
+
+def center_crop_origins(sizes, size, reduce=0):
+    """torchvision's CenterCrop(size) as the windows of decode_tensor: sizes = (H, W) per image at FULL size, size = (Ho, Wo), reduce one int or
+    one per image -> (y0s, x0s) on every image's decoded grid (reduced_dims at its reduce), for origin=.  An image smaller than the crop on an
+    axis is padded first, as CenterCrop pads it -- (c - n) // 2 in front, (c - n + 1) // 2 behind --, and the window then starts at
+    int(round((n' - c) / 2.0)) of the padded extent n': on the image's own grid that origin is NEGATIVE, so such a batch goes with
+    pad=dict(mode="constant").  Pure Python, no device."""
+    Ho, Wo = int(size[0]), int(size[1])
+    sizes = list(sizes)
+    rs = [int(reduce)] * len(sizes) if isinstance(reduce, (int, np.integer)) else [int(r) for r in reduce]
+    assert len(rs) == len(sizes) and Ho >= 1 and Wo >= 1
+
+    def origin(n, c):
+        front = (c - n) // 2 if n < c else 0
+        behind = (c - n + 1) // 2 if n < c else 0
+        return int(round((n + front + behind - c) / 2.0)) - front
+    dims = [reduced_dims(h, w, r) for (h, w), r in zip(sizes, rs)]
+    return [origin(h, Ho) for h, _ in dims], [origin(w, Wo) for _, w in dims]
+
+
+def _tensor_opts(channels_last, pad):
+    """channels_last= and pad= of the tensor decodes -> None (nothing new is asked for: the call is its sibling) or a _lib.TensorOpts"""
+    if not channels_last and pad is None:
+        return None
+    o = _lib.TensorOpts(LAYOUT_NHWC if channels_last else LAYOUT_NCHW, PAD_NONE, FILL_PIXEL, (0.0, 0.0, 0.0))
+    if pad is not None:
+        pad = dict(pad)
+        mode, fill, space = pad.pop("mode"), pad.pop("fill", 0), pad.pop("space", "pixel")
+        if pad:
+            raise TypeError(f"pad: unknown keys {sorted(pad)}")
+        if isinstance(mode, str) and mode not in PAD_MODES:
+            raise ValueError(f"pad mode {mode!r} (one of {sorted(PAD_MODES)})")
+        if isinstance(space, str) and space not in FILL_SPACES:
+            raise ValueError(f"fill space {space!r} (one of {sorted(FILL_SPACES)})")
+        fill = [float(fill)] * 3 if isinstance(fill, (int, float, np.integer, np.floating)) else [float(v) for v in fill]
+        assert len(fill) == 3
+        o.pad_mode, o.fill_space = int(PAD_MODES.get(mode, mode)), int(FILL_SPACES.get(space, space))      # (an int goes through: the library says what it does not know)
+        o.fill[0], o.fill[1], o.fill[2] = fill
+    return o
+
+
 RESIZE_BOX_SLICE = 128         # images per launch of the resized decode's last kernel (kResizeBoxMax: a larger batch takes several launches)
 RESIZE_TAP_MAX = 9             # taps per axis that kernel is compiled for (kResizeTapMax)
 
@@ -703,10 +763,11 @@ class HipCodec:
                                                       _ptr(out), out.shape[1], _ptr(seg_len), _stream_ptr(self.device)))
         return out, seg_len
 
-    def _decode_prologue(self, name, containers, seg_len, Hs, Ws, mode, reduce):
+    def _decode_prologue(self, name, containers, seg_len, Hs, Ws, mode, reduce, opts=None):
         """The front of the decode calls that take `reduce`: sizes as int32 arrays, the workspace, the modes array and the reduce argument
         -> (B, every image's decoded size, call), where call(*tail) runs llicti_<name> (reduce an int) or llicti_<name>_rv (one per image) on
-        the leading arguments, `tail` and this device's stream."""
+        the leading arguments, `tail` and this device's stream.  opts (a _lib.TensorOpts): llicti_<name>_o instead -- B reduce values whatever
+        `reduce` is, and `opts` behind the stream."""
         Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
         B = len(Hs)
         assert containers.shape[0] == B
@@ -714,21 +775,34 @@ class HipCodec:
         one, per = self._modes_arg(mode, B)
         modes = np.array([one], dtype=np.int32) if per is None else per
         r, rv = _reduce_arg(reduce, B)
-        fn = getattr(self.L, "llicti_" + name if rv is None else "llicti_" + name + "_rv")
+        dims = _reduced_sizes(Hs, Ws, r, rv)
+        end = ()
+        if opts is not None:
+            rv, end = (np.full(B, r, dtype=np.int32) if rv is None else rv), (C.byref(opts),)
+        fn = getattr(self.L, "llicti_" + name + ("_o" if opts is not None else "" if rv is None else "_rv"))
 
         def call(*tail):
             _lib.check(fn(self.ctx, _ptr(containers), containers.shape[1], _ptr(seg_len), B, _ptr(Hs), _ptr(Ws), _ptr(modes), len(modes),
-                          r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), *tail, _stream_ptr(self.device)))
-        return B, _reduced_sizes(Hs, Ws, r, rv), call      # (a bad r: the library says so)
+                          r if rv is None else _ptr(rv), _ptr(ws), ws.numel(), *tail, _stream_ptr(self.device), *end))
+        return B, dims, call      # (a bad r: the library says so)
 
-    def _tensor_out(self, out, n, size, dtype):
-        """the [n, 3, Ho, Wo] output of a tensor decode, the caller's (checked) or a new one -> (out, the library's dtype code, Ho, Wo)"""
+    def _tensor_out(self, out, n, size, dtype, channels_last=False):
+        """the [n, 3, Ho, Wo] output of a tensor decode, the caller's (checked) or a new one -> (out, the library's dtype code, Ho, Wo).
+        channels_last: the tensor is [n, 3, Ho, Wo] in torch.channels_last -- strides (3 Ho Wo, 1, 3 Wo, 3), held as strides (is_contiguous
+        cannot tell the layouts apart when a dimension has size 1)."""
         Ho, Wo = int(size[0]), int(size[1])
         dt = TENSOR_DTYPES.get(dtype, dtype)          # (an int goes through as it is: the library says what it does not know)
         tdt = next((k for k, v in TENSOR_DTYPES.items() if v == dt), torch.float32)
+        if not channels_last:
+            if out is None:
+                out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
+            assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= n * 3 * Ho * Wo
+            return out, int(dt), Ho, Wo
         if out is None:
-            out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == tdt and out.numel() >= n * 3 * Ho * Wo
+            out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=tdt, device=self.device, memory_format=torch.channels_last)
+        assert out.is_cuda and out.dtype == tdt and tuple(out.shape) == (n, 3, max(Ho, 0), max(Wo, 0)), "out: a [n, 3, Ho, Wo] device tensor of the call's dtype"
+        if Ho >= 1 and Wo >= 1:                       # (a size the library will refuse: it says so)
+            assert tuple(out.stride()) == (3 * Ho * Wo, 1, 3 * Wo, 3), f"out: strides {tuple(out.stride())}, channels_last needs {(3 * Ho * Wo, 1, 3 * Wo, 3)}"
         return out, int(dt), Ho, Wo
 
     def decode_reduced(self, containers, seg_len, Hs, Ws, mode, reduce, out=None, rgb_off=None):
@@ -815,7 +889,8 @@ class HipCodec:
         return out
 
     # ---- float tensors (llicti_decode_images_tensor / llicti_encode_images_f32): the batch tensor a network is fed with, planar float32 in
-    def decode_tensor(self, containers, seg_len, Hs, Ws, mode, size, dtype=torch.float32, origin=None, flip=None, mean=None, std=None, reduce=0, out=None):
+    def decode_tensor(self, containers, seg_len, Hs, Ws, mode, size, dtype=torch.float32, origin=None, flip=None, mean=None, std=None, reduce=0, out=None,
+                      channels_last=False, pad=None):
         """device containers of B images of FULL sizes Hs[b] x Ws[b] (they may differ) -> ONE device tensor [B, 3, Ho, Wo] of `dtype` (float32,
         float16, bfloat16), written by the decode's last kernel, async.  size = (Ho, Wo); origin = (y0s, x0s): every image's window origin in the
         decoded image (the reduced one for reduce >= 1; None: 0) -- the window must lie inside the image, nothing is padded or resampled;
@@ -823,20 +898,28 @@ class HipCodec:
         torchvision's ToTensor + Normalize on the CPU, bit for bit: v / 255 (one fp32 division), then (x - mean[c]) / std[c], then dtype's
         round-to-nearest-even.  Origins and flips are per-call data: calls that differ only in them share one cached plan.  `out`: a contiguous
         [B, 3, Ho, Wo] tensor of that dtype to write into (nothing outside it is touched).  reduce as decode_reduced (an int, or one per image:
-        image b's origin is then in the coordinates of its own decimated grid)."""
-        B, _, call = self._decode_prologue("decode_images_tensor", containers, seg_len, Hs, Ws, mode, reduce)
-        out, dt, Ho, Wo = self._tensor_out(out, B, size, dtype)
+        image b's origin is then in the coordinates of its own decimated grid).
+        channels_last=True: the same values as a [B, 3, Ho, Wo] tensor in torch.channels_last (strides (3 Ho Wo, 1, 3 Wo, 3); a caller's `out`
+        must have exactly those), interleaved by the same kernel -- no transpose pass.  pad=dict(mode="constant" | "edge" | "reflect" |
+        "symmetric", fill=0 or 3 values, space="pixel" | "output"): a window may leave its image, origins may be negative (-8160 .. 8160) --
+        numpy's pad modes of those names (torch's "replicate" is "edge"); "reflect" mirrors at most n - 1 pixels past a side of n, "symmetric"
+        n.  fill in space "pixel" is a value on the 0 .. 255 scale that is normalised like a pixel (torchvision's Pad(fill) in front of ToTensor +
+        Normalize), in space "output" the element itself (0: the padded zeros of a collate).  center_crop_origins gives CenterCrop's windows.
+        With neither, the call is the one it always was; with either, the plan, its key and the counters are still decode_reduced's."""
+        opts = _tensor_opts(channels_last, pad)
+        B, _, call = self._decode_prologue("decode_images_tensor", containers, seg_len, Hs, Ws, mode, reduce, opts)
+        out, dt, Ho, Wo = self._tensor_out(out, B, size, dtype, channels_last)
         y0 = x0 = None
         if origin is not None:
             y0, x0 = (np.ascontiguousarray(v, dtype=np.int32) for v in origin)
             assert y0.shape == (B,) and x0.shape == (B,)
         fl = _flip_arg(flip, B)
         mn, sd = _norm_args(mean, std)
-        call(_ptr(out), dt, Ho, Wo, _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd))
+        call(C.c_void_p(out.data_ptr()), dt, Ho, Wo, _ptr(y0), _ptr(x0), _ptr(fl), _ptr(mn), _ptr(sd))
         return out
 
     def decode_tensor_resized(self, containers, seg_len, Hs, Ws, mode, size, boxes, dtype=torch.float32, flip=None, mean=None, std=None, antialias=True,
-                              reduce=0, out=None):
+                              reduce=0, out=None, channels_last=False):
         """decode_tensor with a resampling step (llicti_decode_images_tensor_resized): image b's source box boxes[b] = (y0, x0, hs, ws) -- in the
         coordinates of the decoded image, the reduced one for reduce >= 1; boxes None: every whole image -- is resampled to size = (Ho, Wo) by
         the decode's last kernel, flipped, normalised and written into ONE device tensor [B, 3, Ho, Wo] of `dtype`, async: torchvision's
@@ -845,17 +928,17 @@ class HipCodec:
         `reduce` (resized_crop_plan picks it).  A box of Ho x Wo gives decode_tensor's bytes.  Boxes, flips, size and flag are per-call data:
         calls that differ only in them share decode_reduced's cached plan and neither allocate nor synchronise.  reduce: an int, or one per image
         (resized_crop_plan(..., per_image=True)): box b is then in the coordinates of image b's own decimated grid, and a tight crop no longer
-        sends its neighbours through the finest levels."""
-        B, _, call = self._decode_prologue("decode_images_tensor_resized", containers, seg_len, Hs, Ws, mode, reduce)
-        out, dt, Ho, Wo = self._tensor_out(out, B, size, dtype)
+        sends its neighbours through the finest levels.  channels_last as decode_tensor's (a box that leaves its image stays refused)."""
+        B, _, call = self._decode_prologue("decode_images_tensor_resized", containers, seg_len, Hs, Ws, mode, reduce, _tensor_opts(channels_last, None))
+        out, dt, Ho, Wo = self._tensor_out(out, B, size, dtype, channels_last)
         cols = _box_columns(boxes, B)
         fl = _flip_arg(flip, B)
         mn, sd = _norm_args(mean, std)
         aa = int(antialias) if isinstance(antialias, (bool, int, np.integer)) else -1
-        call(_ptr(out), dt, Ho, Wo, *(_ptr(c) for c in cols), _ptr(fl), _ptr(mn), _ptr(sd), aa)
+        call(C.c_void_p(out.data_ptr()), dt, Ho, Wo, *(_ptr(c) for c in cols), _ptr(fl), _ptr(mn), _ptr(sd), aa)
         return out
 
-    def decode_tensor_views(self, containers, seg_len, Hs, Ws, mode, groups, mean=None, std=None, reduce=0):
+    def decode_tensor_views(self, containers, seg_len, Hs, Ws, mode, groups, mean=None, std=None, reduce=0, channels_last=False):
         """Several resized crops per image from ONE decode (llicti_decode_images_tensor_views).  groups: a list of dict(size=(Ho, Wo),
         image=[...] | None, boxes=[(y0, x0, hs, ws), ...] | None, flip=None, dtype=torch.float32, antialias=True, out=None): view v of a
         group is what decode_tensor_resized writes for image image[v] (any order, repeats allowed, images may be absent; None: view v is
@@ -864,8 +947,8 @@ class HipCodec:
         every view costs one more pass of the last kernel.  Image indices, boxes and flips are per-call data: calls that differ only in
         them share decode_reduced's cached plan and neither allocate nor synchronise.  multi_crop_plan picks reduce: an int, or one per image
         (per_image=True) -- a view's box is then in the coordinates of ITS image's decimated grid, and an image no view names may be passed at
-        the model's level count."""
-        B, _, call = self._decode_prologue("decode_images_tensor_views", containers, seg_len, Hs, Ws, mode, reduce)
+        the model's level count.  channels_last as decode_tensor's: it holds for EVERY group of the call."""
+        B, _, call = self._decode_prologue("decode_images_tensor_views", containers, seg_len, Hs, Ws, mode, reduce, _tensor_opts(channels_last, None))
         groups = list(groups)
         arr = (_lib.ViewGroup * max(len(groups), 1))()
         outs, keep = [], []
@@ -879,7 +962,7 @@ class HipCodec:
             img = None if image is None else np.ascontiguousarray(image, dtype=np.int32)
             assert img is None or img.ndim == 1
             n = B if img is None else len(img)
-            out, dt, Ho, Wo = self._tensor_out(out, n, (Ho, Wo), dtype)
+            out, dt, Ho, Wo = self._tensor_out(out, n, (Ho, Wo), dtype, channels_last)
             cols = _box_columns(boxes, n)
             fl = _flip_arg(flip, n)
             aa = int(antialias) if isinstance(antialias, (bool, int, np.integer)) else -1

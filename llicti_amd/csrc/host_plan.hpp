@@ -567,6 +567,55 @@ static int resolve_tensor(const char *who, int B, const int *Hs, const int *Ws, 
     return 0;
 }
 
+// Tensor options (the _o calls): what does not depend on the image -- layout, pad mode, fill space and fill -- validated into the kernel's
+// TensorPad.  pad_allowed = false (the resized and views calls): anything but LLICTI_PAD_NONE is refused.
+static bool tensor_opts_plain(const llicti_tensor_opts *o) { return !o || (o->layout == LLICTI_LAYOUT_NCHW && o->pad_mode == LLICTI_PAD_NONE); }
+static int resolve_tensor_opts(const char *who, const llicti_tensor_opts &o, bool pad_allowed, TensorPad &pad)
+{
+    if (o.layout != LLICTI_LAYOUT_NCHW && o.layout != LLICTI_LAYOUT_NHWC) return fail(LLICTI_EINVAL, "%s: unknown layout %d (LLICTI_LAYOUT_NCHW, _NHWC)", who, o.layout);
+    if (o.pad_mode < LLICTI_PAD_NONE || o.pad_mode > LLICTI_PAD_SYMMETRIC)
+        return fail(LLICTI_EINVAL, "%s: unknown pad mode %d (LLICTI_PAD_NONE, _CONSTANT, _EDGE, _REFLECT, _SYMMETRIC)", who, o.pad_mode);
+    if (!pad_allowed && o.pad_mode != LLICTI_PAD_NONE)
+        return fail(LLICTI_EINVAL, "%s: pad mode %d: a box that leaves its image is refused, only llicti_decode_images_tensor_o pads (pass LLICTI_PAD_NONE)", who, o.pad_mode);
+    memset(&pad, 0, sizeof pad);
+    pad.layout = o.layout; pad.mode = o.pad_mode;
+    if (o.pad_mode == LLICTI_PAD_NONE) return 0;                      // (fill space and fill are read with a pad mode alone)
+    if (o.fill_space != LLICTI_FILL_PIXEL && o.fill_space != LLICTI_FILL_OUTPUT)
+        return fail(LLICTI_EINVAL, "%s: unknown fill space %d (LLICTI_FILL_PIXEL, _OUTPUT)", who, o.fill_space);
+    pad.space = o.fill_space;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(o.fill[k])) return fail(LLICTI_EINVAL, "%s: fill[%d] = %g (need a finite value)", who, k, (double)o.fill[k]);
+        pad.fill[k] = o.fill[k];
+    }
+    return 0;
+}
+// resolve_tensor for a call with options: the same checks of dtype, size and normalisation; every image's window held to the pad mode
+// (tensor_window_pad_ok; LLICTI_PAD_NONE: resolve_tensor's rule) and packed into its TWO signed words (pad_win_pack).  Kernel arguments all.
+static int resolve_tensor_padded(const char *who, int B, const int *Hs, const int *Ws, const Reduces &rd, const TensorArgs &t, const llicti_tensor_opts &o,
+                                 std::vector<uint32_t> &wins, TensorNorm &nm, TensorPad &pad)
+{
+    if (!tensor_elem_bytes(t.dtype)) return fail(LLICTI_EINVAL, "%s: unknown dtype %d (LLICTI_T_F32, _F16, _BF16)", who, t.dtype);
+    if (int rc = resolve_tensor_opts(who, o, true, pad)) return rc;
+    if (t.Ho < 1 || t.Wo < 1 || (pad.mode != LLICTI_PAD_NONE && (t.Ho > 8160 || t.Wo > 8160)))
+        return fail(LLICTI_EINVAL, "%s: output size %dx%d (need Ho, Wo >= 1; with a pad mode at most 8160)", who, t.Wo, t.Ho);
+    if (int rc = resolve_norm(who, t.mean, t.std, nm)) return rc;
+    wins.assign(2 * (size_t)B, 0u);
+    for (int b = 0; b < B; ++b) {
+        const int y0 = t.y0 ? t.y0[b] : 0, x0 = t.x0 ? t.x0[b] : 0;
+        const int reduce = rd.of(b), Hr = reduced_dim(Hs[b], reduce), Wr = reduced_dim(Ws[b], reduce);
+        if (pad.mode != LLICTI_PAD_NONE && (y0 < -kPadOriginMax || y0 > kPadOriginMax || x0 < -kPadOriginMax || x0 > kPadOriginMax))
+            return fail(LLICTI_EINVAL, "%s: the origin (y %d, x %d) of image %d (need -%d .. %d)", who, y0, x0, b, kPadOriginMax, kPadOriginMax);
+        if (!tensor_window_pad_ok(Hs[b], Ws[b], reduce, y0, x0, t.Ho, t.Wo, pad.mode)) {
+            if (pad.mode == LLICTI_PAD_NONE)
+                return fail(LLICTI_EINVAL, "%s: the %dx%d window at (y %d, x %d) leaves image %d (%dx%d at reduce %d)", who, t.Wo, t.Ho, y0, x0, b, Wr, Hr, reduce);
+            return fail(LLICTI_EINVAL, "%s: the %dx%d window at (y %d, x %d) overhangs image %d (%dx%d at reduce %d) by more than pad mode %d mirrors "
+                        "(LLICTI_PAD_REFLECT: n - 1 pixels of an axis of n, LLICTI_PAD_SYMMETRIC: n)", who, t.Wo, t.Ho, y0, x0, b, Wr, Hr, reduce, pad.mode);
+        }
+        pad_win_pack(y0, x0, t.flip && t.flip[b], &wins[2 * (size_t)b]);
+    }
+    return 0;
+}
+
 // Resized crops (llicti_decode_images_tensor_resized): the output description as the caller gave it -- hs, ws NULL: the whole decoded image from
 // the origin -- ...
 struct ResizeArgs { int dtype, Ho, Wo; const int *y0, *x0, *hs, *ws; const uint8_t *flip; const float *mean, *std; int antialias; };

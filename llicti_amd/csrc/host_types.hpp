@@ -89,6 +89,48 @@ LLICTI_HD bool tensor_window_ok(int H, int W, int r, int y0, int x0, int Ho, int
     if (H < 1 || W < 1 || r < 0 || r > LLICTI_NLEVELS || Ho < 1 || Wo < 1 || y0 < 0 || x0 < 0) return false;
     return (long)y0 + Ho <= reduced_dim(H, r) && (long)x0 + Wo <= reduced_dim(W, r);
 }
+// Tensor options (llicti_decode_images_tensor_o and kin): the output's layout and, for windows, the padding past the image.  Per call data like
+// the windows: `TensorPad` is a kernel argument of the sink_* kernels, and a padded window takes TWO words per image (PadWins) -- its origins
+// are signed, -8160 .. 8160, and do not fit tensor_win_pack's 13 bits: [2 b] = (y0 + 8192) | flip << 16, [2 b + 1] = x0 + 8192.
+constexpr int kPadWinMax = 128;                                      // images per launch of sink_window_kernel
+constexpr int kPadOriginBias = 8192, kPadOriginMax = 8160;
+struct PadWins { uint32_t w[2 * kPadWinMax]; };
+struct TensorPad { int layout, mode, space; float fill[3]; };        // LLICTI_LAYOUT_*, LLICTI_PAD_*, LLICTI_FILL_*
+LLICTI_HD void pad_win_pack(int y0, int x0, bool flip, uint32_t *words)
+{
+    words[0] = (uint32_t)(y0 + kPadOriginBias) | ((flip ? 1u : 0u) << 16);
+    words[1] = (uint32_t)(x0 + kPadOriginBias);
+}
+LLICTI_HD void pad_win_unpack(uint32_t w0, uint32_t w1, int &y0, int &x0, bool &flip)
+{
+    y0 = (int)(w0 & 0xFFFFu) - kPadOriginBias; x0 = (int)(w1 & 0xFFFFu) - kPadOriginBias; flip = ((w0 >> 16) & 1u) != 0;
+}
+// The index map of one axis of a padded window (include/llicti_hip.h states it): coordinate t on an axis of n pixels -> the source index in
+// 0 .. n - 1, -1 for "fill", -2 for refused.  ONE function for the kernel and llicti_pad_index (the host).  |t| <= 2^30.
+LLICTI_HD int pad_index(int n, int t, int mode)
+{
+    if (n < 1) return -2;
+    if (t >= 0 && t < n) return t;
+    const int over = t < 0 ? -t : t - (n - 1);                       // pixels past the side, >= 1
+    switch (mode) {
+    case LLICTI_PAD_CONSTANT: return -1;
+    case LLICTI_PAD_EDGE: return t < 0 ? 0 : n - 1;
+    case LLICTI_PAD_REFLECT: return over > n - 1 ? -2 : t < 0 ? -t : 2 * (n - 1) - t;
+    case LLICTI_PAD_SYMMETRIC: return over > n ? -2 : t < 0 ? -t - 1 : 2 * n - 1 - t;
+    default: return -2;                                              // (LLICTI_PAD_NONE: the window leaves its image; an unknown mode)
+    }
+}
+// llicti_decode_images_tensor_o takes an Ho x Wo window at (y0, x0) of an H x W image decoded at reduce r under pad mode `mode`: sizes 1 .. 8160,
+// origins -8160 .. 8160, and both ends of either axis map somewhere (the overhang grows monotonically towards a window's ends)
+LLICTI_HD bool tensor_window_pad_ok(int H, int W, int r, int y0, int x0, int Ho, int Wo, int mode)
+{
+    if (mode == LLICTI_PAD_NONE) return tensor_window_ok(H, W, r, y0, x0, Ho, Wo);
+    if (mode < LLICTI_PAD_NONE || mode > LLICTI_PAD_SYMMETRIC) return false;
+    if (H < 1 || W < 1 || r < 0 || r > LLICTI_NLEVELS || Ho < 1 || Wo < 1 || Ho > 8160 || Wo > 8160) return false;
+    if (y0 < -kPadOriginMax || y0 > kPadOriginMax || x0 < -kPadOriginMax || x0 > kPadOriginMax) return false;
+    const int Hr = reduced_dim(H, r), Wr = reduced_dim(W, r);
+    return pad_index(Hr, y0, mode) != -2 && pad_index(Hr, y0 + Ho - 1, mode) != -2 && pad_index(Wr, x0, mode) != -2 && pad_index(Wr, x0 + Wo - 1, mode) != -2;
+}
 // Resized crops (llicti_decode_images_tensor_resized): image b's source BOX -- origin, extent, flip, in the coordinates of the decoded image --
 // is resampled to Ho x Wo by unlift_resize_tensor_kernel.  Per call data like the windows above: two packed words per image (origins and
 // extents are at most 8160 < 2^13), kResizeBoxMax images per launch.

@@ -419,6 +419,50 @@ __device__ __forceinline__ void store_tensor_quads(T *__restrict__ o, long oplan
     }
 }
 
+// ... and the same four pixels INTERLEAVED (LLICTI_LAYOUT_NHWC): 12 consecutive elements at o, pixel k's channel c at o[3 k + c].  `vec`
+// (n == 4 by Wo % 4 == 0, the tensor 16-byte aligned: o is then aligned to 48 bytes of float, to 8 of the 24 bytes of a 16-bit type): three
+// 16-byte stores, or 16 + 8 bytes; element by element otherwise -- the same bytes either way.
+template <typename T> struct alignas(8) Oct16 { T e[8]; };            // eight 16-bit elements moved by one access, aligned to half of it
+template <typename T>
+__device__ __forceinline__ void store_tensor_nhwc(T *__restrict__ o, const Quad<T> (&q)[3], int n, bool vec)
+{
+    if (vec) {
+        T e[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[3 * k + c] = q[c].e[k];
+        if constexpr (sizeof(T) == 4) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s) *reinterpret_cast<Quad<T> *>(o + 4 * s) = Quad<T>{ { e[4 * s], e[4 * s + 1], e[4 * s + 2], e[4 * s + 3] } };
+        } else {
+            *reinterpret_cast<Oct16<T> *>(o) = Oct16<T>{ { e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7] } };
+            *reinterpret_cast<Quad<T> *>(o + 8) = Quad<T>{ { e[8], e[9], e[10], e[11] } };
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) { o[3 * k] = q[0].e[k]; o[3 * k + 1] = q[1].e[k]; o[3 * k + 2] = q[2].e[k]; }
+    }
+}
+// Where a sink's four pixels go: pixel (i, j .. j + 3) of output slot `slot` of `out`, [slot][3][Ho][Wo] planes or [slot][Ho][Wo][3].  The
+// condition of the wide stores is the same in both layouts: Wo % 4 == 0 and `out` aligned to 16 bytes (planar: to 4 elements, as ever).
+struct PlanarStore {
+    template <typename T>
+    static __device__ __forceinline__ void put(T *__restrict__ out, long slot, int Ho, int Wo, int i, int j, const Quad<T> (&q)[3], int n)
+    {
+        const long oplane = (long)Ho * Wo;
+        store_tensor_quads(out + slot * 3 * oplane + (long)i * Wo + j, oplane, q, n, (Wo & 3) == 0 && ((uintptr_t)out & (4 * sizeof(T) - 1)) == 0);
+    }
+};
+struct NhwcStore {
+    template <typename T>
+    static __device__ __forceinline__ void put(T *__restrict__ out, long slot, int Ho, int Wo, int i, int j, const Quad<T> (&q)[3], int n)
+    {
+        store_tensor_nhwc(out + ((slot * Ho + i) * Wo + j) * 3, q, n, (Wo & 3) == 0 && ((uintptr_t)out & 15) == 0);
+    }
+};
+
 // The last kernel of llicti_decode_images_tensor, in the place of unlift_kernel / unlift_reduced_kernel / unlift_px_kernel: image b's Ho x Wo
 // window (origin and flip: word blockIdx.y of `wins`, the call's kernel arguments -- images b0 .. b0 + gridDim.y - 1 of the batch) through the
 // inverse YCoCg-R into out[b][3][Ho][Wo].  Output pixel (i, j) is the plane pixel ((y0 + i) << r, (x0 + j') << r), j' = Wo - 1 - j where
@@ -462,6 +506,73 @@ __global__ __launch_bounds__(256) void unlift_tensor_kernel(const int16_t *__res
     }
 }
 
+// The last kernel of llicti_decode_images_tensor_o when its options ask for something unlift_tensor_kernel does not do: a window PADDED past its
+// image, the NHWC layout, or both.  Image b's Ho x Wo window (two signed words of `wins`: pad_win_pack) is cut from its Hr x Wr decoded grid
+// extended by pad.mode: row t = y0 + i and column x0 + j' (j' = Wo - 1 - j where flipped) go through pad_index, the map include/llicti_hip.h
+// states -- a source index, or "fill".  A lane owns 4 consecutive output pixels of one row.  Where the row and all four columns lie INSIDE the
+// grid it takes load_planes4 exactly as unlift_tensor_kernel does (its short4 path included); on the border it goes pixel by pixel: a mapped
+// pixel is one gather through the same inverse and tensor_finish, a "fill" pixel the lane's three fill elements (tensor_finish of the fill, or
+// the fill itself rounded to T).  Stores: PlanarStore / NhwcStore.  With LLICTI_PAD_NONE every lane is inside (the host saw to it): the values
+// are unlift_tensor_kernel's.  Every source index is in 0 .. n - 1 by pad_index's construction, whatever the words hold: nothing is read
+// outside the image's planes, nothing written outside the tensor.  Latches the call's status words exactly as unlift_tensor_kernel does.
+template <typename T>
+__global__ __launch_bounds__(256) void sink_window_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
+                                                          const PadWins wins, const TensorNorm nm, const TensorPad pad,
+                                                          const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                          int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
+                                                          const int *__restrict__ rtab = nullptr)
+{
+    const int b = b0 + blockIdx.y;
+    latch_status(status, status_head, latched, img_latched, b);
+    if (rtab) r = rtab[b];      // (the _rv contract: the image's own level, wave-uniform)
+    int y0, x0;
+    bool flip;
+    pad_win_unpack(wins.w[2 * blockIdx.y], wins.w[2 * blockIdx.y + 1], y0, x0, flip);
+    const int W = iv[b].W, Hr = reduced_dim(iv[b].H, r), Wr = reduced_dim(W, r);
+    const long plane = iv[b].plane;
+    const int16_t *src = planes + iv[b].pix_off;
+    T fill[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) fill[c] = pad.space == LLICTI_FILL_OUTPUT ? tensor_elem<T>(pad.fill[c]) : tensor_finish<T>(pad.fill[c], c, nm);
+    const uint32_t Wq = (uint32_t)(Wo + 3) >> 2, units = (uint32_t)Ho * Wq;
+    const bool src_vec = r == 0 && !flip && ((W | x0) & 3) == 0 && ((uintptr_t)src & 7) == 0;
+    for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
+        const uint32_t i = u / Wq, j = (u - i * Wq) * 4;
+        const int n = min(4, Wo - (int)j);
+        const int row = y0 + (int)i, col = flip ? x0 + Wo - 1 - (int)j : x0 + (int)j;      // the window's coordinates of the lane's first pixel
+        const int far = flip ? col - (n - 1) : col + (n - 1);                             // ... and of its last
+        Quad<T> q[3];
+        if (row >= 0 && row < Hr && min(col, far) >= 0 && max(col, far) < Wr) {
+            int y[4], co[4], cg[4];
+            load_planes4(src, plane, W, r, row, col, flip, n, src_vec && n == 4, y, co, cg);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int v[3];
+                ycocg_inv(y[k], co[k], cg[k], v[0], v[1], v[2]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) q[c].e[k] = tensor_finish<T>((float)v[c], c, nm);
+            }
+        } else {
+            const int sy = pad_index(Hr, row, pad.mode);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int sx = pad_index(Wr, flip ? col - k : col + k, pad.mode);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) q[c].e[k] = fill[c];
+                if (k < n && sy >= 0 && sx >= 0) {
+                    const int16_t *s = src + ((long)(sy << r) * W + ((long)sx << r));
+                    int v[3];
+                    ycocg_inv(s[0], s[plane], s[2 * plane], v[0], v[1], v[2]);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) q[c].e[k] = tensor_finish<T>((float)v[c], c, nm);
+                }
+            }
+        }
+        if (pad.layout == LLICTI_LAYOUT_NHWC) NhwcStore::put(out, (long)b, Ho, Wo, (int)i, (int)j, q, n);
+        else PlanarStore::put(out, (long)b, Ho, Wo, (int)i, (int)j, q, n);
+    }
+}
+
 // The resampling tile of llicti_decode_images_tensor_resized and llicti_decode_images_tensor_views: a source box (two words: origin, flip,
 // extent -- decoded coordinates, plane pixel (y << r, x << r)) of image b's planes resampled to output slot `slot` of `out`, [slot][3][Ho][Wo],
 // by the triangle filter of resize_axis, to the operation of include/llicti_hip.h: per row tap a the sum over the column taps of w^x_b * p, left
@@ -471,8 +582,9 @@ __global__ __launch_bounds__(256) void unlift_tensor_kernel(const int16_t *__res
 // flipped box's tile takes the weights of the mirrored columns.  A lane then owns 4 consecutive output pixels of one row: one 4-element store
 // per channel when Wo % 4 == 0 and `out` is aligned to 4 elements, element by element otherwise.  Source indices are clamped into the box
 // (only zero-weight taps ever are).
+// Store: where the tile's pixels go -- PlanarStore (the default: the kernels below) or NhwcStore (sink_resize_nhwc_kernel, sink_views_nhwc_kernel).
 constexpr int kResizeTileH = 16, kResizeTileW = 64;
-template <typename T>
+template <typename T, typename Store = PlanarStore>
 __device__ __forceinline__ void resize_tile(const int16_t *__restrict__ planes, T *__restrict__ out, long slot, int r, int Ho, int Wo, int tiles_x,
                                             int antialias, uint32_t w0, uint32_t w1, const TensorNorm &nm, const ImgGeo *__restrict__ iv, int b)
 {
@@ -502,7 +614,7 @@ __device__ __forceinline__ void resize_tile(const int16_t *__restrict__ planes, 
     const int nx = ntap[0], ny = ntap[1];
     const int n = min(4, Wo - j);
     const int W = iv[b].W;
-    const long plane = iv[b].plane, oplane = (long)Ho * Wo;
+    const long plane = iv[b].plane;
     const int16_t *src = planes + iv[b].pix_off;
     const int yl = ylo[li];
     float v[4][3];
@@ -534,7 +646,7 @@ __device__ __forceinline__ void resize_tile(const int16_t *__restrict__ planes, 
     for (int k = 0; k < 4; ++k)
 #pragma unroll
         for (int c = 0; c < 3; ++c) q[c].e[k] = tensor_finish<T>(v[k][c], c, nm);
-    store_tensor_quads(out + slot * 3 * oplane + (long)i * Wo + j, oplane, q, n, (Wo & 3) == 0 && ((uintptr_t)out & (4 * sizeof(T) - 1)) == 0);
+    Store::put(out, slot, Ho, Wo, i, j, q, n);
 }
 
 // The last kernel of llicti_decode_images_tensor_resized, in the place of unlift_tensor_kernel: image b = b0 + blockIdx.y's box (two words of
@@ -567,4 +679,32 @@ __global__ __launch_bounds__(256) void unlift_views_tensor_kernel(const int16_t 
     const int b = (int)views.w[3 * blockIdx.y + 2];
     if (rtab) r = rtab[b];      // (the _rv call: the level of the view's IMAGE, wave-uniform)
     resize_tile<T>(planes, out, (long)v0 + blockIdx.y, r, Ho, Wo, tiles_x, antialias, views.w[3 * blockIdx.y], views.w[3 * blockIdx.y + 1], nm, iv, b);
+}
+
+// unlift_resize_tensor_kernel and unlift_views_tensor_kernel in the NHWC layout (the _o calls with LLICTI_LAYOUT_NHWC): the same tile, the same
+// values, the same latches -- resize_tile with NhwcStore.
+template <typename T>
+__global__ __launch_bounds__(256) void sink_resize_nhwc_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int b0,
+                                                               int tiles_x, int antialias, const ResizeBoxes boxes, const TensorNorm nm,
+                                                               const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                               int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv,
+                                                               const int *__restrict__ rtab = nullptr)
+{
+    const int b = b0 + blockIdx.y;
+    latch_status(status, status_head, latched, img_latched, b);
+    if (rtab) r = rtab[b];
+    resize_tile<T, NhwcStore>(planes, out, (long)b, r, Ho, Wo, tiles_x, antialias, boxes.w[2 * blockIdx.y], boxes.w[2 * blockIdx.y + 1], nm, iv, b);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sink_views_nhwc_kernel(const int16_t *__restrict__ planes, T *__restrict__ out, int r, int Ho, int Wo, int v0,
+                                                              int tiles_x, int antialias, const ViewSlice views, const TensorNorm nm,
+                                                              const int32_t *__restrict__ status, int status_head, int32_t *__restrict__ latched,
+                                                              int32_t *__restrict__ img_latched, const ImgGeo *__restrict__ iv, int latch_n,
+                                                              const int *__restrict__ rtab = nullptr)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && latch_n > 0) latch_status_all(status, status_head, latched, img_latched, latch_n);
+    const int b = (int)views.w[3 * blockIdx.y + 2];
+    if (rtab) r = rtab[b];
+    resize_tile<T, NhwcStore>(planes, out, (long)v0 + blockIdx.y, r, Ho, Wo, tiles_x, antialias, views.w[3 * blockIdx.y], views.w[3 * blockIdx.y + 1], nm, iv, b);
 }

@@ -8,6 +8,8 @@
 //   lift_kernel<float> / unlift_tensor_kernel  planar float32 in, the dense float / half / bfloat16 batch tensor (crop, flip, normalise) out (HBM bound)
 //   unlift_resize_tensor_kernel       the same tensor from a per-image source box RESAMPLED to the output size (triangle filter; a gather)
 //   unlift_views_tensor_kernel        the same tile per VIEW: several boxes per image, each naming its image, from one decode
+//   sink_window_kernel                unlift_tensor_kernel's window PADDED past its image (constant, edge, reflect, symmetric) and / or stored NHWC
+//   sink_resize_nhwc_kernel, sink_views_nhwc_kernel   the two resampling kernels storing NHWC (torch.channels_last)
 //   band_params_kernel<BAND>          interpolator CNN: 3 chained fp32-MFMA GEMMs per pixel tile,
 //                                     weights of one 88-channel head resident in LDS        (MFMA bound)
 //   cdf_pairs_kernel                  encoder: the two table entries per symbol (10 erfc)   (VALU)
@@ -1035,6 +1037,10 @@ struct DecodeSink {
     std::vector<uint32_t> wins;             // Tensor: a packed window per image; Resized: two packed words per image
     std::vector<ViewGroupOut> groups;       // Views: three packed words per view
     TensorNorm nm{};                        // Tensor, Resized, Views
+    // the _o calls: the caller's options (has_opts: they ask for something the unlift_* kernels do not do), validated into `pad`
+    bool has_opts = false;
+    llicti_tensor_opts opts{};
+    TensorPad pad{};                        // Tensor, Resized, Views: layout; Tensor: pad mode, fill space, fill (wins then holds pad_win_pack's two words per image)
     // Transcode (llicti_transcode_images): the target plan of the call and its part of the workspace.  decode_stages launches cdf_pairs_kernel
     // behind every (level, band) stage -- the stage's CNN outputs and symbols are exactly what the encoder's pairs are made of -- and no unlift.
     PlanDev *target = nullptr;
@@ -1047,6 +1053,8 @@ static DecodeSink px_sink(uint8_t *d_pix, const PixArgs &px) { DecodeSink k; k.k
 static DecodeSink tensor_sink(void *d_out, const TensorArgs &t) { DecodeSink k; k.kind = DecodeSink::Tensor; k.d_out = (uint8_t *)d_out; k.tensor = t; return k; }
 static DecodeSink resized_sink(void *d_out, const ResizeArgs &t) { DecodeSink k; k.kind = DecodeSink::Resized; k.d_out = (uint8_t *)d_out; k.resize = t; return k; }
 static DecodeSink views_sink(const ViewArgs &a) { DecodeSink k; k.kind = DecodeSink::Views; k.views = a; return k; }
+// (opts NULL or plain: the sink is the _rv sibling's, to the last launch)
+static DecodeSink with_opts(DecodeSink k, const llicti_tensor_opts *opts) { if (!tensor_opts_plain(opts)) { k.has_opts = true; k.opts = *opts; } return k; }
 static DecodeSink cuts_sink(int32_t *d_cuts) { DecodeSink k; k.kind = DecodeSink::Cuts; k.d_out = (uint8_t *)d_cuts; return k; }
 
 static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, const Reduces &rd)
@@ -1058,10 +1066,13 @@ static int resolve_sink(DecodeSink &k, int B, const int *Hs, const int *Ws, cons
         return resolve_pixels("decode_images_px", B, Hw.data(), Ww.data(), k.px.fmt, k.px.off, k.px.pitch, k.pix);
     }
     case DecodeSink::Tensor:
+        if (k.has_opts) return resolve_tensor_padded("decode_images_tensor_o", B, Hs, Ws, rd, k.tensor, k.opts, k.wins, k.nm, k.pad);
         return resolve_tensor("decode_images_tensor", B, Hs, Ws, rd, k.tensor, k.wins, k.nm);
     case DecodeSink::Resized:
+        if (k.has_opts) if (int rc = resolve_tensor_opts("decode_images_tensor_resized_o", k.opts, false, k.pad)) return rc;
         return resolve_resize("decode_images_tensor_resized", B, Hs, Ws, rd, k.resize, k.wins, k.nm);
     case DecodeSink::Views:
+        if (k.has_opts) if (int rc = resolve_tensor_opts("decode_images_tensor_views_o", k.opts, false, k.pad)) return rc;
         return resolve_views("decode_images_tensor_views", B, Hs, Ws, rd, k.views, k.groups, k.nm);
     default:
         return 0;
@@ -1148,6 +1159,18 @@ static int launch_sink(llicti_ctx *c, const Plan &p, const DecodeBufs &w, const 
         // images' status words, the first one the call's
         const TensorArgs &t = k.tensor;
         const int gx = (int)std::min<long>(((long)t.Ho * ((t.Wo + 3) / 4) + 255) / 256, 1024);
+        if (k.has_opts) {      // (a padded window or the NHWC layout: two signed words per image, kPadWinMax images per launch, the same latches)
+            for (int b0 = 0; b0 < B; b0 += kPadWinMax) {
+                const int nb = std::min(kPadWinMax, B - b0);
+                const PadWins pw = arg_slice<PadWins>(k.wins, 2, b0, nb);
+                with_tensor_type(t.dtype, [&](auto e) {
+                    using T = decltype(e);
+                    sink_window_kernel<T><<<dim3(gx, nb), 256, 0, s>>>(w.planes, (T *)k.d_out, o.r, t.Ho, t.Wo, b0, pw, k.nm, k.pad, w.status, kStatusHead, c->d_status,
+                                                                      c->d_img_status, w.d_img, o.rtab);
+                });
+            }
+            break;
+        }
         for (int b0 = 0; b0 < B; b0 += kTensorWinMax) {
             const int nb = std::min(kTensorWinMax, B - b0);
             const TensorWins tw = arg_slice<TensorWins>(k.wins, 1, b0, nb);
@@ -1169,6 +1192,10 @@ static int launch_sink(llicti_ctx *c, const Plan &p, const DecodeBufs &w, const 
             const ResizeBoxes bx = arg_slice<ResizeBoxes>(k.wins, 2, b0, nb);
             with_tensor_type(t.dtype, [&](auto e) {
                 using T = decltype(e);
+                if (k.pad.layout == LLICTI_LAYOUT_NHWC)
+                    sink_resize_nhwc_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(w.planes, (T *)k.d_out, o.r, t.Ho, t.Wo, b0, tiles_x, t.antialias, bx, k.nm,
+                                                                                          w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img, o.rtab);
+                else
                 unlift_resize_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nb), 256, 0, s>>>(w.planes, (T *)k.d_out, o.r, t.Ho, t.Wo, b0, tiles_x, t.antialias, bx, k.nm,
                                                                                           w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img, o.rtab);
             });
@@ -1186,6 +1213,10 @@ static int launch_sink(llicti_ctx *c, const Plan &p, const DecodeBufs &w, const 
                 const ViewSlice vs = arg_slice<ViewSlice>(g.words, 3, v0, nv);
                 with_tensor_type(g.dtype, [&](auto e) {
                     using T = decltype(e);
+                    if (k.pad.layout == LLICTI_LAYOUT_NHWC)
+                        sink_views_nhwc_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(w.planes, (T *)g.d_out, o.r, g.Ho, g.Wo, v0, tiles_x, g.antialias, vs, k.nm,
+                                                                                             w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img, latch_n, o.rtab);
+                    else
                     unlift_views_tensor_kernel<T><<<dim3(tiles_x * tiles_y, nv), 256, 0, s>>>(w.planes, (T *)g.d_out, o.r, g.Ho, g.Wo, v0, tiles_x, g.antialias, vs, k.nm,
                                                                                              w.status, kStatusHead, c->d_status, c->d_img_status, w.d_img, latch_n, o.rtab);
                 });
@@ -1583,6 +1614,56 @@ extern "C" int llicti_decode_images_tensor_views_rv(llicti_ctx *c, const uint8_t
     if (int rc = rv_head(c, "decode_images_tensor_views_rv", B, reduces, &rd)) return rc;
     return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
                         views_sink({ groups, G, mean, std }));
+}
+
+// ------------------------------------------------------------------------------------------------ tensor options
+// The three _o calls: the _rv sibling with a trailing `opts`.  NULL or { NCHW, PAD_NONE }: the call IS the sibling's (with_opts leaves the sink
+// as it is).  Otherwise the same decode with the sink_* kernels at its end -- the plan, its key and the per-call tables do not depend on opts.
+extern "C" int llicti_pad_index(int n, int t, int mode)
+{
+    if (n < 1 || n > 8160 || t < -(1 << 20) || t > (1 << 20) || mode < LLICTI_PAD_NONE || mode > LLICTI_PAD_SYMMETRIC) return -2;
+    return pad_index(n, t, mode);
+}
+extern "C" int llicti_tensor_window_pad_ok(int H, int W, int reduce, int y0, int x0, int Ho, int Wo, int mode)
+{
+    return tensor_window_pad_ok(H, W, reduce, y0, x0, Ho, Wo, mode) ? 1 : 0;
+}
+
+extern "C" int llicti_decode_images_tensor_o(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                             int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                             void *d_workspace, size_t workspace_bytes,
+                                             void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const uint8_t *flip,
+                                             const float *mean, const float *std, void *stream, const llicti_tensor_opts *opts)
+{
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_tensor_o", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
+                        with_opts(tensor_sink(d_out, { dtype, Ho, Wo, y0, x0, flip, mean, std }), opts));
+}
+
+extern "C" int llicti_decode_images_tensor_resized_o(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                                     int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                                     void *d_workspace, size_t workspace_bytes,
+                                                     void *d_out, int dtype, int Ho, int Wo, const int *y0, const int *x0, const int *hs, const int *ws,
+                                                     const uint8_t *flip, const float *mean, const float *std, int antialias, void *stream,
+                                                     const llicti_tensor_opts *opts)
+{
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_tensor_resized_o", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
+                        with_opts(resized_sink(d_out, { dtype, Ho, Wo, y0, x0, hs, ws, flip, mean, std, antialias }), opts));
+}
+
+extern "C" int llicti_decode_images_tensor_views_o(llicti_ctx *c, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
+                                                   int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduces,
+                                                   void *d_workspace, size_t workspace_bytes,
+                                                   const llicti_view_group *groups, int G, const float *mean, const float *std, void *stream,
+                                                   const llicti_tensor_opts *opts)
+{
+    Reduces rd;
+    if (int rc = rv_head(c, "decode_images_tensor_views_o", B, reduces, &rd)) return rc;
+    return decode_batch(c, { d_in, in_stride, d_seg_len, B, Hs, Ws, modes, n_modes, d_workspace, workspace_bytes, nullptr, stream, rd },
+                        with_opts(views_sink({ groups, G, mean, std }), opts));
 }
 
 extern "C" int llicti_encode_images_f32(llicti_ctx *c, const float *d_x, const size_t *x_off, int B, const int *Hs, const int *Ws, const int *modes,

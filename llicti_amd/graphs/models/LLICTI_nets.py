@@ -525,6 +525,10 @@ class LLICTI(nn.Module):
         tensor = dict(views=[group, ...], mean=, std=): SEVERAL crops per image from one decode (HipCodec.decode_tensor_views, which describes a
         group: size, image, boxes, flip, dtype, antialias, out) -> a list of one tensor [n, 3, Ho, Wo] per group; codec.multi_crop_plan picks
         reduce.  `views` goes with neither `boxes`, `origin` nor `size` at the top level.
+        Every form takes channels_last=True: the tensor(s) come out as [n, 3, Ho, Wo] in torch.channels_last, interleaved by the same kernel.
+        The `origin` form also takes pad=dict(mode="constant" | "edge" | "reflect" | "symmetric", fill=, space="pixel" | "output"): windows may
+        then leave their images and origins be negative (HipCodec.decode_tensor states the modes); codec.center_crop_origins gives
+        torchvision's CenterCrop windows, the images smaller than the crop included.
         lists may be an archive.Batch (ArchiveReader.read_batch) instead: the records of B images in one host buffer -- one dense upload and
         HipCodec.unpack_records in place of the per-image staging (`slot` is not used: the batch owns its buffer, which must stay untouched until
         the upload has run); sizes and modes are the archive index's, everything behind the containers is the same path.
