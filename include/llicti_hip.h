@@ -272,7 +272,8 @@ int llicti_decode_images_v(llicti_ctx *ctx, const uint8_t *d_in, size_t in_strid
  * INTEGRITY: a rANS container's end-of-stream check belongs to the tail coder of the LAST stage (level 0, band x10: it must end in its start
  * state), which a call with reduce >= 1 never launches.  Such a call reports what the kernels it did launch flag -- header, unpack, init and
  * the decoded stages (llicti_check_status, llicti_image_status) -- and nothing else: damage confined to the skipped levels goes unnoticed.
- * A valid container gives status 0 for every image. */
+ * A valid container gives status 0 for every image.  (What a FULL decode returned can be held against a digest of the encoded pixels:
+ * PIXEL DIGESTS below.) */
 int llicti_reduced_dims(int H, int W, int reduce, int *Hr, int *Wr);
 int llicti_decode_images_reduced(llicti_ctx *ctx, const uint8_t *d_in, size_t in_stride, const int32_t *d_seg_len,
                                  int B, const int *Hs, const int *Ws, const int *modes, int n_modes, int reduce,
@@ -663,6 +664,48 @@ int llicti_pack_progressive(llicti_ctx *ctx, const uint8_t *d_cont, size_t strid
 int llicti_unpack_progressive(llicti_ctx *ctx, const uint8_t *d_blob, size_t blob_bytes, const int64_t *d_rec_off /* [B+1] */, int B,
                               const int *reduce /* host, [B] */, uint8_t *d_cont, size_t stride, int32_t *d_seg_len /* [B][49] */, void *stream);
 int llicti_progressive_prefix(const uint8_t *head, size_t bytes, int64_t *prefix /* [LLICTI_NLEVELS+1] */);
+
+/* PIXEL DIGESTS: a CRC-32 of every image's pixels, computed on the device, so that a decode can be checked without moving a pixel to the host
+ * and without the original at hand.
+ *
+ * DEFINITION.  The digest of an H x W image is zlib's CRC-32 of its pixels as planar uint8 [3][H][W] bytes -- the R plane, then the G plane, then
+ * the B plane, rows top to bottom: zlib.crc32(rgb_chw.tobytes()) in Python, crc32(0, p, 3 H W) in C.  Anyone recomputes it without this
+ * library.  It depends on the pixel VALUES alone: not on the container kind, the batch, or the form a decode delivers them in.
+ *
+ * WHERE IT COMES FROM.  Every whole-batch encode and every full decode leaves the image's int16 YCoCg-R planes in the caller's workspace
+ * (llicti_workspace_planes); the digest kernels read those planes once, invert the transform and write a word per image.  A decode into
+ * interleaved pixels, a float crop, a resized box or views therefore yields the digest of the WHOLE image it decoded, although that image
+ * never exists as bytes.  An image decoded at reduce >= 1 has no full-size planes: it has no digest (d_have = 0).
+ *
+ * THE FOLD.  CRCs concatenate: crc(A || B) = crc(A) * x^(8 |B|) xor crc(B) in GF(2)[x] modulo the reflected polynomial 0xEDB88320.  A lane
+ * takes a run of llicti_crc32_geometry's lane_pixels pixels, a workgroup group_pixels, three CRCs at a time (pixel p is byte p of each
+ * colour plane); lanes, then workgroups, then the three planes are folded in order with that rule.  The ragged end of an image lies in FRONT
+ * of its first workgroup (a zero register does not see what is missing in front of a message), so a plane of n pixels has its seams at
+ * n - k * lane_pixels and n - k * group_pixels.
+ *
+ * WHAT IT SHOWS.  Equal digests: the decode returned the pixels that were encoded, up to a 2^-32 chance per image -- through the entropy
+ * decoder, the CNN's fp32 arithmetic on this device, driver and compiler, and the inverse transform.  It is a CHECK AGAINST ACCIDENTS, NOT A
+ * MAC: whoever can alter a container can alter a stored digest, and CRC-32 collisions are easy to construct.
+ *
+ * llicti_crc32_combine (host, no context): crc32(A || B) from crc32(A), crc32(B) and len_b = |B| -- zlib's crc32_combine.
+ * llicti_crc32_geometry (host, no context): the kernel's run per lane and per workgroup, in pixels (either pointer may be NULL).
+ * llicti_crc32_planes: d_crc[b] = the digest of image b of d_planes, int16 [B][3][H][W] as llicti_lift_u8 writes them; 1 <= H, W <= 8160.
+ *   Asynchronous on `stream`.
+ * llicti_digest_images: the digests of the images of the PRECEDING whole-batch encode or decode of this batch, out of that call's workspace,
+ *   which is read and never written.  B, Hs, Ws, modes / n_modes: that call's (an encode's "auto" modes as they were given).  reduce: NULL, or
+ *   the B values the decode ran with (a scalar call: B copies).  d_have[b] = 1 and d_crc[b] = the digest where image b was coded in full --
+ *   reduce NULL or reduce[b] == 0, and every encode --; d_have[b] = 0 and d_crc[b] = 0 otherwise, and no pixel of such an image is read.
+ *   The call runs on the CACHED plan of that call -- the most recently used one of these sizes and modes -- and builds none: a batch no plan
+ *   is cached for is LLICTI_EINVAL, and so is a workspace smaller than that plan's, a null pointer, a size outside 32 .. 8160 and a reduce
+ *   outside 0 .. the model's levels.  Asynchronous on `stream`; no allocation and no synchronisation (the flags of a call with reduced
+ *   images travel in a pooled table block, as the _rv decodes' tables do); neither the status words nor llicti_last_timing are touched.
+ *   llicti_level_cuts is a full decode: its planes are digested like any other's.  A TRANSCODE's workspace is out of scope: its two plans
+ *   share one workspace under a layout of their own. */
+uint32_t llicti_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+int llicti_crc32_geometry(int *lane_pixels, int *group_pixels);
+int llicti_crc32_planes(llicti_ctx *ctx, const int16_t *d_planes, int B, int H, int W, uint32_t *d_crc, void *stream);
+int llicti_digest_images(llicti_ctx *ctx, int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduce /* NULL or [B] */,
+                         const void *d_workspace, size_t workspace_bytes, uint32_t *d_crc, int32_t *d_have, void *stream);
 
 /* Where llicti_encode_images / llicti_decode_images of B images of H x W in `mode` keep the YCoCg-R planes inside the caller's workspace
  * (byte offsets): int16 [B][3][H][W] (Y - 127, Co, Cg) and float32 [B][3][H][W] = planes / 255 -- the second is the `x_ycocg` the

@@ -136,6 +136,11 @@ _SIGS = {
     "llicti_pack_progressive": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     "llicti_unpack_progressive": (_i, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
     "llicti_progressive_prefix": (_i, [_vp, _sz, _vp]),
+    # pixel digests: two host helpers, the kernel-level call on planes, the digests of the preceding whole-batch call
+    "llicti_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
+    "llicti_crc32_geometry": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "llicti_crc32_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "llicti_digest_images": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     "llicti_encode_images": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
     "llicti_decode_images": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "llicti_check_status": (_i, [_vp, _vp]),

@@ -176,6 +176,7 @@ class RecordFileReader:
             if zlib.crc32(index) & 0xFFFFFFFF != crc:
                 raise ValueError(f"{path}: index crc32 mismatch")
             self.nseg, self.count, self.index_offset = int(nseg), int(count), int(index_offset)
+            self.index_crc = int(crc)                          # (what a digest manifest, llicti_amd/digest.py, is bound to)
             self.offsets = np.frombuffer(index, dtype="<u8", count=count + 1).astype(np.int64)
             if self.offsets[0] != 0 or (np.diff(self.offsets) < self.KIND.min_record(nseg)).any() or self.offsets[-1] != index_offset:
                 raise ValueError(f"{path}: record offsets do not tile the record region")

@@ -273,6 +273,19 @@ def tensor_elem_bytes(dtype) -> int:
     return n
 
 
+def crc32_combine(crc_a, crc_b, len_b) -> int:
+    """zlib's crc32_combine: crc32(A + B) from crc32(A), crc32(B) and len(B) (llicti_crc32_combine, works without a device)."""
+    return int(_lib.lib().llicti_crc32_combine(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b)))
+
+
+def crc32_geometry():
+    """(pixels a lane of the digest kernel owns, pixels a workgroup owns) -- llicti_crc32_geometry, works without a device: an image of n pixels
+    has the kernel's seams at n - k * lane and n - k * group."""
+    lane, group = C.c_int(), C.c_int()
+    _lib.check(_lib.lib().llicti_crc32_geometry(C.byref(lane), C.byref(group)))
+    return lane.value, group.value
+
+
 def tensor_window_ok(H, W, reduce, y0, x0, Ho, Wo) -> bool:
     """Whether an Ho x Wo window at (y0, x0) lies inside an H x W image decoded at `reduce` (llicti_tensor_window_ok, works without a device)."""
     return bool(_lib.lib().llicti_tensor_window_ok(int(H), int(W), int(reduce), int(y0), int(x0), int(Ho), int(Wo)))
@@ -1203,6 +1216,41 @@ class HipCodec:
         _lib.check(self.L.llicti_workspace_params_v(self.ctx, len(Hs), _ptr(Hs), _ptr(Ws), _ptr(modes), int(image), C.byref(off), C.byref(npos)))
         n = 64 * npos.value * 4
         return self._ws[off.value:off.value + n].view(torch.float32).view(64, npos.value).clone()
+
+    # ---- pixel digests (llicti_crc32_planes / llicti_digest_images): zlib's CRC-32 of every image's planar uint8 [3][H][W] bytes, on the device
+    @staticmethod
+    def _crc_i64(crc32):
+        """the kernels' uint32 words (held in an int32 tensor) as int64 values 0 .. 2^32 - 1"""
+        return crc32.to(torch.int64) & 0xFFFFFFFF
+
+    def crc32_planes(self, planes):
+        """int16 device planes [B, 3, H, W] (lift's) -> int64 device tensor [B]: zlib.crc32 of each image's RGB bytes as uint8 [3][H][W], async."""
+        assert planes.dtype == torch.int16 and planes.is_cuda and planes.dim() == 4 and planes.shape[1] == 3 and planes.is_contiguous()
+        B, _, H, W = planes.shape
+        crc = torch.empty((B,), dtype=torch.int32, device=self.device)
+        _lib.check(self.L.llicti_crc32_planes(self.ctx, _ptr(planes), B, H, W, _ptr(crc), _stream_ptr(self.device)))
+        return self._crc_i64(crc)
+
+    def digests(self, Hs, Ws, mode, reduce=None):
+        """The digests of the images of the PRECEDING whole-batch encode or decode of this batch (sizes Hs[b] x Ws[b], mode as that call took it:
+        one, or one per image), out of the cached workspace that call ran in -> (crc, have): int64 device tensor [B] holding 0 .. 2^32 - 1 --
+        zlib.crc32 of image b's pixels as planar uint8 [3][H][W] bytes -- and int32 [B], 1 where image b was coded in full.  reduce: what the
+        decode was given (None or 0: a full decode, or an encode; an int; one per image) -- an image with reduce >= 1 has have = 0, crc = 0 and
+        is not read.  Enqueued on the current stream, behind that call; no plan is built, nothing is allocated by the library, nothing
+        synchronises.  Whatever form the decode delivered -- planar, interleaved, a float crop, a resized box, views -- the digest is that of
+        the whole decoded image."""
+        Hs, Ws = np.ascontiguousarray(Hs, dtype=np.int32), np.ascontiguousarray(Ws, dtype=np.int32)
+        B = len(Hs)
+        if self._ws is None:
+            raise _lib.LlictiError(_lib.EINVAL, "digests: no whole-batch call has run on this codec yet")
+        one, per = self._modes_arg(mode, B)
+        modes = np.array([one], dtype=np.int32) if per is None else per
+        red = None if reduce is None else np.ascontiguousarray(np.broadcast_to(np.asarray(reduce, dtype=np.int32), (B,)))
+        crc = torch.empty((B,), dtype=torch.int32, device=self.device)
+        have = torch.empty((B,), dtype=torch.int32, device=self.device)
+        _lib.check(self.L.llicti_digest_images(self.ctx, B, _ptr(Hs), _ptr(Ws), _ptr(modes), len(modes), _ptr(red), _ptr(self._ws), self._ws.numel(),
+                                               _ptr(crc), _ptr(have), _stream_ptr(self.device)))
+        return self._crc_i64(crc), have
 
     def counter(self, name):
         """llicti_get_counter: "device_syncs", "device_allocs", "plan_builds", "plan_hits", "block_waits", "plans_cached", "blocks_pooled"."""

@@ -23,6 +23,7 @@
 //   header / pack / unpack kernels    container assembly in HBM
 //   record_* kernels                  strided containers <-> one dense blob of .llic records: validation + a realigning 16-byte copy (HBM bound)
 //   level_cuts / prog_* kernels       progressive records: the level cuts of a decode, validation + a piecewise copy in level-major order (HBM bound)
+//   crc_planes_kernel / crc_fold_kernel   pixel digests: CRC-32 of every image's RGB bytes from the planes in the workspace (HBM / VALU bound)
 //
 // No CPU path exists in this library: every entry point needs a gfx950 device.
 #include <hip/hip_runtime.h>
@@ -55,6 +56,7 @@ using namespace llicti;
 #include "container.hpp"
 #include "records.hpp"
 #include "records_progressive.hpp"
+#include "digest.hpp"
 #include "host_plan.hpp"
 
 // ------------------------------------------------------------------------------------------------ context
@@ -107,6 +109,8 @@ struct llicti_ctx {
     int img_status_cap = 0, img_status_n = 0;   // (context-owned: the caller may free or reuse the workspace before llicti_image_status)
     int32_t *d_status = nullptr;      // small persistent status word (for the kernel-level entry points)
     int32_t *d_lift_part = nullptr;   // min/max partials of llicti_lift_u8 (1 MB; calls on one context are not concurrent)
+    uint32_t *d_crc_tab = nullptr;    // pixel digests: the shift constants (crc_math.hpp: crc_fill_tables) ...
+    uint32_t *d_crc_part = nullptr;   // ... and the workgroups' partial CRCs, kCrcMaxParts x 3 words (digest.hpp)
     float2 *d_phi_lut = nullptr;      // normal CDF on [-6, 6] as (value, difference to the next) pairs: the lane decoder's hint table (rans_coder.hpp)
     int n_cu = 256;                   // compute units of the device (grid sizing of the persistent kernels)
     int cnn_tile_rows = 0;            // llicti_set_tuning("cnn_tile_rows"): 0 = choose per launch, 16 / 4 = force (tests, A/B)
@@ -249,6 +253,14 @@ extern "C" int llicti_create(llicti_ctx **out, int device)
         HIPCHK(hipMalloc(&c->d_phi_lut, sizeof(float2) * kPhiLutN));
         HIPCHK(hipMemcpy(c->d_phi_lut, lut.data(), sizeof(float2) * kPhiLutN, hipMemcpyHostToDevice));
     }
+    {
+        std::vector<uint32_t> tab(kCrcTabWords);
+        crc_fill_tables(tab.data());
+        HIPCHK(hipMalloc(&c->d_crc_tab, sizeof(uint32_t) * kCrcTabWords));
+        HIPCHK(hipMemcpy(c->d_crc_tab, tab.data(), sizeof(uint32_t) * kCrcTabWords, hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&c->d_crc_part, (size_t)kCrcMaxParts * 3 * sizeof(uint32_t)));
+        HIPCHK(hipFuncSetAttribute((const void *)crc_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCrcLdsBytes));
+    }
     HIPCHK(hipEventCreate(&c->ev_call[0]));
     HIPCHK(hipEventCreate(&c->ev_call[1]));
     for (int k = 0; k < 2; ++k) {
@@ -295,6 +307,8 @@ extern "C" int llicti_destroy(llicti_ctx *c)
     if (c->d_status) hipFree(c->d_status);
     if (c->d_lift_part) hipFree(c->d_lift_part);
     if (c->d_phi_lut) hipFree(c->d_phi_lut);
+    if (c->d_crc_tab) hipFree(c->d_crc_tab);
+    if (c->d_crc_part) hipFree(c->d_crc_part);
     if (c->d_img_status) hipFree(c->d_img_status);
     for (auto e : c->ev) hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) if (c->ev_call[i]) hipEventDestroy(c->ev_call[i]);
@@ -1759,6 +1773,100 @@ extern "C" int llicti_transcode_images(llicti_ctx *c, const uint8_t *d_in, size_
     HIPCHK(hipGetLastError());
     c->img_status_n = B;
     return LLICTI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ pixel digests
+extern "C" uint32_t llicti_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc32_combine(crc_a, crc_b, len_b); }
+extern "C" int llicti_crc32_geometry(int *lane_pixels, int *group_pixels)
+{
+    if (lane_pixels) *lane_pixels = kCrcLanePixels;
+    if (group_pixels) *group_pixels = kCrcGroupPixels;
+    return LLICTI_OK;
+}
+
+// The two digest kernels over B images: contiguous planes of `plane` pixels (iv == nullptr), or a call's table.  max_plane sizes the grid; the
+// images go in slices whose partials fit the context's scratch (one slice unless B x groups exceeds kCrcMaxParts).
+static int launch_crc(llicti_ctx *c, const int16_t *planes, long plane, const ImgGeo *iv, long max_plane, int B, const int32_t *d_flags,
+                      uint32_t *d_crc, int32_t *d_have, hipStream_t s)
+{
+    const int gx = (int)((max_plane + kCrcGroupPixels - 1) / kCrcGroupPixels);
+    const int slice = std::max(1, std::min(kCrcMaxParts / gx, 65535));
+    for (int b0 = 0; b0 < B; b0 += slice) {
+        const int nb = std::min(slice, B - b0);
+        crc_planes_kernel<<<dim3(gx, nb), kCrcThreads, kCrcLdsBytes, s>>>(planes, plane, iv, d_flags, b0, c->d_crc_tab, c->d_crc_part);
+        crc_fold_kernel<<<nb, kCrcThreads, 0, s>>>(c->d_crc_part, gx, plane, iv, d_flags, b0, c->d_crc_tab, d_crc, d_have);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int llicti_crc32_planes(llicti_ctx *c, const int16_t *d_planes, int B, int H, int W, uint32_t *d_crc, void *stream)
+{
+    if (!c || !d_planes || !d_crc) return fail(LLICTI_EINVAL, "crc32_planes: null pointer");
+    if (B < 1 || H < 1 || W < 1 || H > 8160 || W > 8160) return fail(LLICTI_EINVAL, "crc32_planes: bad shape B=%d H=%d W=%d (need B>=1, 1<=H,W<=8160)", B, H, W);
+    DeviceGuard guard(c);
+    return launch_crc(c, d_planes, (long)H * W, nullptr, (long)H * W, B, nullptr, d_crc, nullptr, (hipStream_t)stream);
+}
+
+// The plan the PRECEDING whole-batch call of this batch shape ran on: the most recently used cached plan of these sizes and modes, whatever its
+// placement, reduce or pixel windows (their key tails follow the full-size key; the caller's RGB offsets are skipped) -- all of them carve the
+// workspace's planes from the sizes alone.  nullptr: none is cached.
+static PlanDev *find_batch_plan(llicti_ctx *c, const PlanSpec &sp)
+{
+    const std::vector<long> key = plan_key(sp);
+    PlanDev *best = nullptr;
+    for (auto &kv : c->plans) {
+        const std::vector<long> &k = kv.first;
+        if (k.size() < key.size()) continue;
+        bool same = true;
+        for (size_t i = 0; i < key.size() && same; ++i) same = (i >= 3 && (i - 3) % 4 == 2) || k[i] == key[i];
+        if (same && (!best || kv.second->last_use > best->last_use)) best = kv.second;
+    }
+    return best;
+}
+
+extern "C" int llicti_digest_images(llicti_ctx *c, int B, const int *Hs, const int *Ws, const int *modes, int n_modes, const int *reduce,
+                                    const void *d_workspace, size_t workspace_bytes, uint32_t *d_crc, int32_t *d_have, void *stream)
+{
+    if (!c || !d_workspace || !d_crc || !d_have) return fail(LLICTI_EINVAL, "digest_images: null pointer");
+    if (check_dims_v(B, Hs, Ws)) return LLICTI_EINVAL;
+    int ME = 0;
+    std::vector<int> Ms;
+    if (int rc = resolve_modes("digest_images", modes, n_modes, B, &ME, Ms)) return rc;
+    bool any_reduced = false;
+    for (int b = 0; reduce && b < B; ++b) {
+        if (reduce[b] < 0 || reduce[b] > c->nlev) return fail(LLICTI_EINVAL, "digest_images: image %d: reduce = %d (a %d-level model decodes at reduce 0 .. %d)", b, reduce[b], c->nlev, c->nlev);
+        any_reduced = any_reduced || reduce[b] != 0;
+    }
+    PlanDev *pd = find_batch_plan(c, ctx_spec(c, B, Hs, Ws, nullptr, ME, modes_ptr(Ms)));
+    if (!pd) return fail(LLICTI_EINVAL, "digest_images: no plan is cached for this batch of %d images and these modes: the call follows a whole-batch encode or decode of the same batch", B);
+    const Plan &p = pd->p;
+    if (workspace_bytes < p.total) return fail(LLICTI_EINVAL, "digest_images: workspace %zu < %zu, the size of the call this one follows", workspace_bytes, p.total);
+    DeviceGuard guard(c);
+    hipStream_t s = (hipStream_t)stream;
+    pd->last_use = ++c->use_clock;
+    if (pd->blk.up_stream != s) HIPCHK(hipStreamWaitEvent(s, pd->blk.uploaded, 0));
+    if (pd->blk.used && pd->blk.done_stream != s) HIPCHK(hipStreamWaitEvent(s, pd->blk.done, 0));
+    PlanUse use{ pd, s };
+    // the flags of a call with reduced images: a per-call table in a pooled block, as the _rv decodes upload theirs
+    PlanBlock fb;
+    const int32_t *d_flags = nullptr;
+    if (any_reduced) {
+        if (int rc = acquire_block(c, (size_t)B * sizeof(int32_t), &fb)) return rc;
+        int32_t *h = (int32_t *)fb.host;
+        for (int b = 0; b < B; ++b) h[b] = reduce[b] == 0 ? 1 : 0;
+        if (hipMemcpyAsync(fb.dev, fb.host, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess) {
+            c->pool.push_back(fb);
+            return fail(LLICTI_EHIP, "digest_images: upload failed");
+        }
+        d_flags = (const int32_t *)fb.dev;
+    }
+    const int rc = launch_crc(c, (const int16_t *)((const uint8_t *)d_workspace + p.off_planes), 0, pd->dev<ImgGeo>(p.d_img), p.max_plane, B, d_flags, d_crc, d_have, s);
+    if (any_reduced) {
+        if (hipEventRecord(fb.done, s) == hipSuccess) { fb.used = true; fb.done_stream = s; }
+        c->pool.push_back(fb);
+    }
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------ records

@@ -113,6 +113,7 @@ class LLICTI(nn.Module):
         self.set_container(str(config["container"]) if "container" in config else "ac")
         self._stage = {}                # pinned host staging buffers of the batched path, by (tag, slot): [buffer, event behind its last copy]
         self._xfer = {}                 # (upload, download) copy streams of the batched path, by device index
+        self._last_decode = None        # (codec, full sizes, mode, reduce) of the last decode_batch_async: what last_digests() digests
 
     def set_container(self, name):
         """Container of the following compress() / encode_batch_async() calls: "ac", "rans<M>", "wrans<M>", "xrans<M>" or "auto"."""
@@ -204,7 +205,7 @@ class LLICTI(nn.Module):
         return enc.lists(), enc.x_ycocg
 
     @torch.no_grad()
-    def encode_batch_async(self, x, want_ycocg=False, slot=0, pixels=None):
+    def encode_batch_async(self, x, want_ycocg=False, slot=0, pixels=None, digests=False):
         """Enqueue the encode of a batch and the download of its containers (pinned host buffers); returns an EncodedBatch whose lists() waits
         for the download and cuts the containers into the reference's bytestream_lists.  Nothing here blocks the host: a caller can enqueue
         the next batch before it converts this one (LLICTIAgent.eval_model with eval_batch > 1).  `slot` selects one of the staging buffer
@@ -216,9 +217,12 @@ class LLICTI(nn.Module):
         as the planar list, without a transpose on the host.  EncodedBatch.rgb is then the flat INTERLEAVED device buffer.
         pixels = "f32": x is a float32 DEVICE tensor [B,3,H,W] in {k/255}, or a list of such tensors [3,H_b,W_b] (or [1,3,H_b,W_b]) whose sizes may
         differ; the encode's first kernel reads the floats (HipCodec.encode_f32: round(x * 255) half to even, clamped, as _to_u8) -- no conversion
-        pass, the same containers.  EncodedBatch.rgb is then the flat float32 device buffer."""
+        pass, the same containers.  EncodedBatch.rgb is then the flat float32 device buffer.
+        digests=True: the pixel digests of the batch (HipCodec.digests: zlib.crc32 of every image's planar uint8 [3][H][W] bytes) are computed
+        directly behind the encode, from the planes it left in its workspace, and downloaded under the handle's event: EncodedBatch.digests().
+        Without the flag the call is exactly the call it was."""
         if pixels == "f32":
-            return self._encode_f32_async(x, slot)
+            return self._encode_f32_async(x, slot, digests)
         if pixels is not None and not isinstance(x, (list, tuple)):
             raise ValueError("pixels=...: the batch is a list of uint8 [H, W, C] arrays")
         if isinstance(x, (list, tuple)):
@@ -252,6 +256,7 @@ class LLICTI(nn.Module):
             B = len(imgs)
             mode = self.mode_for_batch(B, codec.device, sizes=list(zip(Hs, Ws)))
             cont, seg = codec.encode_v(rgb, Hs, Ws, mode) if pixels is None else codec.encode_px(rgb, Hs, Ws, mode, fmt)
+            crc = codec.digests(Hs, Ws, mode)[0] if digests else None      # (before anything else can use the workspace)
             x_ycocg = None
         else:
             t0 = None
@@ -272,17 +277,20 @@ class LLICTI(nn.Module):
             Hs, Ws = [H] * B, [W] * B
             mode = self.mode_for_batch(B, codec.device, sizes=[(H, W)])
             cont, seg = codec.encode(rgb, mode=mode)
+            crc = codec.digests(Hs, Ws, mode)[0] if digests else None
             # x_ycocg = (YCoCg - [127,0,0]) / 255 (LLICTI_nets.py:143-144): the float planes the reference hands back beside the streams -- the encode
             # has just computed them: copied out of its workspace, not lifted a second time
             x_ycocg = codec.encoded_fplanes(B, H, W, mode) if want_ycocg else None
         nb = cont.numel()
         seg_h = self._pinned(("seg", slot), B * NSEG * 4)[:B * NSEG * 4].view(torch.int32).view(B, NSEG)
         cont_h = self._pinned(("cont_out", slot), nb)[:nb].view(tuple(cont.shape))
+        crc_h = None if crc is None else self._pinned(("crc", slot), B * 8)[:B * 8].view(torch.int64)
         # the download runs on its own stream behind the encode: the compute stream goes straight on to the next enqueued call
         down.wait_stream(cur)
         with torch.cuda.stream(down):
             seg_h.copy_(seg, non_blocking=True)
             cont_h.copy_(cont, non_blocking=True)                  # one contiguous copy of the container strides (bytes past a container's own length: undefined)
+            self._download_crc(crc, crc_h, slot, down)
             ev = torch.cuda.Event()
             ev.record(down)
         self._pinned_mark(("seg", slot), down)
@@ -291,9 +299,18 @@ class LLICTI(nn.Module):
         seg.record_stream(down)
         enc = EncodedBatch(codec, rgb, cont_h, seg_h, ev, x_ycocg, mode, Hs, Ws)
         enc.t0 = t0
+        enc.crc_h = crc_h
         return self._with_records(enc, cont, seg, slot)
 
-    def _encode_f32_async(self, x, slot):
+    def _download_crc(self, crc, crc_h, slot, down):
+        """the digests of an encode into their pinned buffer, on the download stream (the caller has it current); nothing without digests"""
+        if crc is None:
+            return
+        crc_h.copy_(crc, non_blocking=True)
+        self._pinned_mark(("crc", slot), down)
+        crc.record_stream(down)
+
+    def _encode_f32_async(self, x, slot, digests=False):
         """encode_batch_async(pixels="f32"): float32 device tensors in, EncodedBatch out."""
         imgs = list(x) if isinstance(x, (list, tuple)) else [x]
         if any(not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype != torch.float32 for a in imgs):
@@ -316,20 +333,25 @@ class LLICTI(nn.Module):
         _, down = self._copy_streams(codec.device)
         mode = self.mode_for_batch(B, codec.device, sizes=list(zip(Hs, Ws)))
         cont, seg = codec.encode_f32(flat, Hs, Ws, mode)
+        crc = codec.digests(Hs, Ws, mode)[0] if digests else None
         nb = cont.numel()
         seg_h = self._pinned(("seg", slot), B * NSEG * 4)[:B * NSEG * 4].view(torch.int32).view(B, NSEG)
         cont_h = self._pinned(("cont_out", slot), nb)[:nb].view(tuple(cont.shape))
+        crc_h = None if crc is None else self._pinned(("crc", slot), B * 8)[:B * 8].view(torch.int64)
         down.wait_stream(cur)
         with torch.cuda.stream(down):
             seg_h.copy_(seg, non_blocking=True)
             cont_h.copy_(cont, non_blocking=True)
+            self._download_crc(crc, crc_h, slot, down)
             ev = torch.cuda.Event()
             ev.record(down)
         self._pinned_mark(("seg", slot), down)
         self._pinned_mark(("cont_out", slot), down)
         cont.record_stream(down)
         seg.record_stream(down)
-        return self._with_records(EncodedBatch(codec, flat, cont_h, seg_h, ev, None, mode, Hs, Ws), cont, seg, slot)
+        enc = EncodedBatch(codec, flat, cont_h, seg_h, ev, None, mode, Hs, Ws)
+        enc.crc_h = crc_h
+        return self._with_records(enc, cont, seg, slot)
 
     def _with_records(self, enc, cont, seg, slot):
         """What EncodedBatch.records() needs: the device containers and segment lengths of the encode (kept alive by the handle) and the pinned
@@ -556,6 +578,7 @@ class LLICTI(nn.Module):
             reduce = [int(r) for r in reduce]
             if len(reduce) != len(Hs):
                 raise ValueError(f"reduce: {len(reduce)} values for a batch of {len(Hs)} images (one int, or one per image)")
+        self._last_decode = (codec, list(Hs), list(Ws), mode, reduce)      # (last_digests: the FULL sizes, whatever the form of the result)
         # the images' decoded sizes (a value the library refuses: it says so in the decode call)
         red_sizes = lambda: (list(v) for v in zip(*(reduced_dims(h, w, r) for h, w, r in zip(Hs, Ws, reduce if per_image else [reduce] * len(Hs)))))
         if tensor is not None and "views" in tensor:
@@ -583,6 +606,18 @@ class LLICTI(nn.Module):
             return out, Hs, Ws
         return codec.decode(cont_d, seg_d, Hs[0], Ws[0], mode=mode, reduce=reduce)
 
+    def last_digests(self):
+        """The pixel digests of the images of the model's last decode_batch_async, whatever its form (planar, pixels=, tensor= with a window,
+        boxes or views) -> (crc, have): HipCodec.digests' int64 and int32 device tensors [B], enqueued on the current stream without a
+        synchronisation -- crc[b] = zlib.crc32 of image b's pixels as planar uint8 [3][H][W] bytes where have[b] = 1 (an image decoded at
+        reduce >= 1 has have = 0).  A loader compares against its manifest with one device `!=`.  Call it before another whole-batch call of
+        this model's codec reuses the workspace."""
+        if self._last_decode is None:
+            raise ValueError("last_digests: no decode_batch_async has run on this model")
+        codec, Hs, Ws, mode, reduce = self._last_decode
+        with torch.cuda.device(codec.device):
+            return codec.digests(Hs, Ws, mode, reduce=reduce if (isinstance(reduce, list) or reduce) else None)
+
 
 class EncodedBatch:
     """Handle of one enqueued batch encode (LLICTI.encode_batch_async): the device input, the pinned host copies of the containers and
@@ -598,6 +633,25 @@ class EncodedBatch:
         self._rec_stage = None              # pinned staging buffer of records(): nbytes -> flat uint8 host tensor
         self._records = None
         self._records_prog = None
+        self.crc_h = None                   # encode_batch_async(digests=True): the pinned int64 [B] digests, valid behind ev
+        self._crc_decoded = None            # ... and those of records(progressive=True)'s decode of the batch (digests(verify=True))
+
+    def digests(self, verify=False):
+        """The pixel digests of the batch, a list of B ints: zlib.crc32 of every image's pixels as planar uint8 [3][H][W] bytes, computed on the
+        device behind the encode (encode_batch_async(digests=True)).  Waits for the handle's download.  verify=True: records(progressive=True)
+        pays a full decode of the batch's containers; the digests of THAT decode are held against the encode's, and a difference raises
+        ValueError naming the images -- a round-trip check at pack time for the price of two small kernels."""
+        if self.crc_h is None:
+            raise ValueError("this handle holds no digests: encode_batch_async(..., digests=True)")
+        self.ev.synchronize()
+        crc = [int(v) for v in self.crc_h.numpy()]
+        if verify:
+            self.records(progressive=True)
+            bad = [b for b, (a, d) in enumerate(zip(crc, self._crc_decoded)) if a != d]
+            if bad:
+                raise ValueError("images %s decode to other pixels than were encoded (crc32 %s, encoded %s)" % (
+                    bad, ["%08x" % self._crc_decoded[b] for b in bad], ["%08x" % crc[b] for b in bad]))
+        return crc
 
     def records(self, check=True, progressive=False):
         """progressive=True: the batch as one dense blob of PROGRESSIVE records (llicti_amd/progressive.py) -> (blob, rec_off, prefix): as below,
@@ -642,8 +696,12 @@ class EncodedBatch:
                     raise ValueError("progressive records hold xwide containers: encode with container \"auto\" or \"xrans<M>\"")
                 dims = [header_dims(bytes(hdr[b])) for b in range(hdr.shape[0])]
                 cuts = codec.level_cuts(self.cont_d, self.seg_d, [d[0] for d in dims], [d[1] for d in dims], modes)
+                # (level_cuts is a full decode: its planes are in the workspace; a handle with digests has them digested for digests(verify=True))
+                crc_dec = codec.digests([d[0] for d in dims], [d[1] for d in dims], modes)[0] if self.crc_h is not None else None
                 blob, ro, pre = codec.pack_progressive(self.cont_d, self.seg_d, cuts)
                 ro_h, pre_h = ro.cpu(), pre.cpu()
+                if crc_dec is not None:
+                    self._crc_decoded = [int(v) for v in crc_dec.cpu().numpy()]
                 total = int(ro_h[-1])
                 host = torch.empty((max(total, 1),), dtype=torch.uint8).pin_memory()
                 host[:total].copy_(blob[:total], non_blocking=True)
