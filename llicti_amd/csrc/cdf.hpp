@@ -57,6 +57,25 @@ __device__ __forceinline__ void cdf_pairs_body(const int16_t *__restrict__ plane
         pairs[(long)clr * s.pair_cs + s.pair_off + n] = (hi << 16) | lo;      // [clr][image][n]
     }
 }
+// The reader of a pair as cdf_pairs_body packs it: c_low in the low half, c_high in the high half, a stored c_high of 0 meaning 2^16.
+// A pair with freq == 0 or c_high < c_low is no symbol's: it is repaired to freq = 1 and reported (the coder latches LLICTI_EFORMAT).
+// Selects, no branch: the rANS coder reads it on its dependency chain.
+struct CodedPair {
+    uint32_t lo, freq;
+    bool wrong;
+    __device__ __forceinline__ explicit CodedPair(uint32_t v)
+    {
+        lo = v & 0xFFFFu;
+        uint32_t hi = v >> 16;
+        hi = (hi == 0) ? 0x10000u : hi;
+        freq = hi - lo;
+        wrong = (freq == 0) | (hi < lo);
+        freq = wrong ? 1u : freq;
+    }
+};
+// a symbol's weight 16 - floor(log2 freq), 1 <= freq <= 2^16: the integer cost that rans_auto_pick and the xwide tail's chain rule sum
+__device__ __forceinline__ int pair_weight(uint32_t freq) { return __clz((int)freq) - 15; }
+
 __global__ __launch_bounds__(kPairsThreads) void cdf_pairs_kernel(const int16_t *__restrict__ planes, const float *__restrict__ params,
                                                         const int32_t *__restrict__ minmax, StageGeom s, const StageGeom *__restrict__ sv,
                                                         uint32_t *__restrict__ pairs)

@@ -330,6 +330,9 @@ LLICTI_HD int rans_stream_count(int nc, int m, int M, int L)
     const int last = m + (K - 1) * M;
     return L * K - ((last == nchunks - 1 && (nc % L)) ? L - (nc % L) : 0);
 }
+// ... and its inverse: the position in the stage of stream m's q-th symbol, q < rans_stream_count(nc, m, M, L) -- over the streams every position
+// below nc exactly once, rising with q (tests/sanitize_host.cpp holds the two against each other)
+LLICTI_HD int rans_stream_pos(int q, int m, int M, int L) { return L * (m + (q / L) * M) + (q % L); }
 
 
 // M <= 32: stream m is segment 4 + m of the container.  M = 64 / 128 (latency modes for single / large images; the reference's list

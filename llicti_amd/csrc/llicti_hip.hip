@@ -53,6 +53,7 @@ using namespace llicti;
 #include "cdf.hpp"
 #include "ac_coder.hpp"
 #include "rans_coder.hpp"
+#include "rans_encode.hpp"
 #include "container.hpp"
 #include "records.hpp"
 #include "records_progressive.hpp"

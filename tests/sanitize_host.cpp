@@ -130,6 +130,22 @@ int main()
         REQUIRE(ME >= 0);
         if (ME) REQUIRE(rans_streams_of_header(rans_byte0(ME & 0xFF, 1 << (ME >> 8)), rans_pad_hi(ME & 0xFF, 1 << (ME >> 8)) << 10) == ME);
     }
+    // rans_stream_pos is the inverse of rans_stream_count: the streams' positions are 0 .. nc - 1, each once, rising with q within a stream
+    for (int L : { 64, 128, 256 })
+        for (int M : { 1, 3, 14 })
+            for (int nc : { 0, 1, L - 1, L, L + 1, M * L - 1, M * L, M * L + 1, 3 * M * L + 17 }) {
+                std::vector<int> seen((size_t)nc, 0);
+                for (int m = 0; m < M; ++m) {
+                    const int cnt = rans_stream_count(nc, m, M, L);
+                    for (int q = 0, prev = -1; q < cnt; ++q) {
+                        const int n = rans_stream_pos(q, m, M, L);
+                        REQUIRE(n > prev && n < nc);
+                        ++seen[(size_t)n];
+                        prev = n;
+                    }
+                }
+                for (int n = 0; n < nc; ++n) REQUIRE(seen[(size_t)n] == 1);
+            }
     for (int mode : { -1, 1, 0x100, 0x100 | 33, 0x100 | 127, 0x300 | 15, 0x500, 0x500 | 33, 0x500 | 96, 0x700 | 1, 0x10000 }) REQUIRE(mode_streams(mode) < 0);
     // every (byte 0, pad field high bits) pair: either not a container of this build, or a mode that round-trips; the xwide v3 tags of rounds 4-5
     // (v = 17 .. 31) and an xwide v4 tag without its count are refused, and so are high bits in a container that is not xwide
