@@ -333,6 +333,29 @@ LLICTI_HD int rans_stream_count(int nc, int m, int M, int L)
 // ... and its inverse: the position in the stage of stream m's q-th symbol, q < rans_stream_count(nc, m, M, L) -- over the streams every position
 // below nc exactly once, rising with q (tests/sanitize_host.cpp holds the two against each other)
 LLICTI_HD int rans_stream_pos(int q, int m, int M, int L) { return L * (m + (q / L) * M) + (q % L); }
+// xwide v4: which of a stream's tail symbols sits where, counted from the stream's end (j = 0: its last symbol).  The first NS are the raw
+// symbols in the chains' start states (chain c's digit d at j = c sn + d), the ncod behind them are coded, alternating between the chains.
+// The encoder and the tail decoder both take it from here -- their agreement is what makes a stream decodable (tests/sanitize_host.cpp
+// holds the counts and the indices against each other).
+struct SeededTailShape {
+    int nch, sn, NS, ncod;                      // chains; raw symbols in a chain's start state (n per chain of two, the stream's last symbol for one chain); seed symbols; coded symbols
+    LLICTI_HD int chain_count(int c) const { return (ncod + nch - 1 - c) / nch; }      // coded symbols of chain c (chain 0 never has fewer than chain 1)
+    LLICTI_HD int index(int c, int i) const { return nch * sn + c + nch * i; }         // j of chain c's i-th coded symbol, in coding order
+    LLICTI_HD int seed_index(int c, int d) const { return c * sn + d; }                // j of digit d < sn of chain c's start state (a symbol of the stream if < NS)
+};
+// cnt: the stream's symbols of the last stage; tall: its tail symbols, or the encoder's candidates (tall <= cnt); ns = rans_seed_count(A).
+// (seeded = false: a 64- / 128-lane stream's tail to the tail decoder -- one chain that starts from no symbol, all of the tail coded)
+LLICTI_HD SeededTailShape seeded_tail_shape(int cnt, int tall, int nch, int ns, bool seeded = true)
+{
+    SeededTailShape s;
+    s.nch = nch;
+    s.sn = !seeded ? 0 : (nch == 2) ? ns : 1;
+    const int held = nch * s.sn;
+    s.NS = held < cnt ? held : cnt;
+    const int rest = tall - s.NS;
+    s.ncod = rest > 0 ? rest : 0;
+    return s;
+}
 
 
 // M <= 32: stream m is segment 4 + m of the container.  M = 64 / 128 (latency modes for single / large images; the reference's list

@@ -1,6 +1,6 @@
 // llicti_hip.hip -- gfx950 (MI355X / CDNA4) kernels and the C-ABI of include/llicti_hip.h.
 // One translation unit: the kernels live in the *.hpp files included below (common, lift, likelihood, band_cnn,
-// cdf, ac_coder, rans_coder, container); this file holds the context, the workspace plan and the entry points.
+// cdf, ac_coder, rans_coder, rans_tail, rans_encode, container); this file holds the context, the workspace plan and the entry points.
 //
 // Kernels (reference call sites in include/llicti_hip.h):
 //   lift_kernel / unlift_kernel       integer YCoCg-R lift, min/max, float planes          (HBM bound)
@@ -19,7 +19,8 @@
 //   rans_encode_kernel<Q>             rANS v3 encoder: 64 Q lanes per stream, one wavefront per 64 (latency bound)
 //   rans_decode_stage_*_kernel        rANS v3 stage decoders, table-free: four / two / ONE lane per symbol for streams of 64 / 128 / 256
 //                                     lanes (the timed mode: rans_decode_stage_lane_kernel<4>)    (VALU issue bound)
-//   rans_tail_kernel<Q>               the serial tail coder behind the lanes' initial states      (latency bound)
+//   rans_tail_kernel<Q>               the serial tail coder behind the lanes' initial states: a coder wavefront and its preparing
+//                                     wavefronts per chain (rans_tail.hpp)                        (latency bound)
 //   header / pack / unpack kernels    container assembly in HBM
 //   record_* kernels                  strided containers <-> one dense blob of .llic records: validation + a realigning 16-byte copy (HBM bound)
 //   level_cuts / prog_* kernels       progressive records: the level cuts of a decode, validation + a piecewise copy in level-major order (HBM bound)
@@ -53,6 +54,7 @@ using namespace llicti;
 #include "cdf.hpp"
 #include "ac_coder.hpp"
 #include "rans_coder.hpp"
+#include "rans_tail.hpp"
 #include "rans_encode.hpp"
 #include "container.hpp"
 #include "records.hpp"
@@ -1281,6 +1283,11 @@ static int decode_prologue(llicti_ctx *c, PlanDev *pd, const DecodeBufs &w, cons
     return 0;
 }
 
+template <int Q> static void launch_tail(const DecodeBufs &w, const StageGeom *sgv, const LevelRun &lr, hipStream_t s)
+{
+    rans_tail_kernel<Q><<<lr.NS, tail_threads<Q>, 0, s>>>(w.params, sgv, w.d_sref, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, w.status, w.slots, w.d_rslot_off, lr.act);
+}
+
 // One (level, band) of the rANS containers: the three colours' stage in one launch of a workgroup per stream of the level, and behind the last
 // stage the tail coder
 static void rans_stage(llicti_ctx *c, const Plan &p, const DecodeBufs &w, int lvl, int band, const LevelRun &lr, hipStream_t s)
@@ -1300,9 +1307,9 @@ static void rans_stage(llicti_ctx *c, const Plan &p, const DecodeBufs &w, int lv
     }
     if (last) {
         ProfSpan span(c, PROF_RANS_TAIL, s);
-        if (Q == 4) rans_tail_kernel<4><<<NS, 64 * (1 + kTailAhead) * kTailChains<4>, 0, s>>>(w.params, sgv, w.d_sref, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, w.status, w.slots, w.d_rslot_off, lr.act);
-        else if (Q == 2) rans_tail_kernel<2><<<NS, 64 * (1 + kTailAhead), 0, s>>>(w.params, sgv, w.d_sref, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, w.status, w.slots, w.d_rslot_off, lr.act);
-        else rans_tail_kernel<1><<<NS, 64 * (1 + kTailAhead), 0, s>>>(w.params, sgv, w.d_sref, w.rstate, w.rpos, w.rtail, w.planes, w.fplanes, w.mm, w.status, w.slots, w.d_rslot_off, lr.act);
+        if (Q == 4) launch_tail<4>(w, sgv, lr, s);
+        else if (Q == 2) launch_tail<2>(w, sgv, lr, s);
+        else launch_tail<1>(w, sgv, lr, s);
     }
 }
 

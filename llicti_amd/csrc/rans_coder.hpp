@@ -1,5 +1,5 @@
-// rans_coder.hpp -- LLICTI-rANS v3 container: what the 64- or 128-way interleaved, bit-granular rANS encoder (rans_encode.hpp) and the decoders
-// share, the table-free stage decoders, the tail decoder, pack and unpack.  Part of the single translation unit llicti_hip.hip (included in order; not a stand-alone header).
+// rans_coder.hpp -- LLICTI-rANS v3 container: what the 64- or 128-way interleaved, bit-granular rANS encoder (rans_encode.hpp), the tail decoder
+// (rans_tail.hpp) and the decoders here share, init, the table-free stage decoders, pack and unpack.  Part of the single translation unit llicti_hip.hip (included in order; not a stand-alone header).
 #pragma once
 #include <type_traits>
 
@@ -846,397 +846,6 @@ __global__ __launch_bounds__(64 * Q) void rans_decode_stage_lane_kernel(const fl
     if (tid == 0) {
         rpos[sidx] = (uint32_t)max(bcur, 0);
         if (bcur < 0 || anybad) flag_image(status, b, LLICTI_EFORMAT);     // the stream ran out of bits, or a state fell out of [2^31, 2^32)
-    }
-}
-
-// After the last stage the 64 Q states of a stream ARE its tail stream (31 bits each, the tail coder's final state on top,
-// its leading one the highest set bit).  The T tail symbols -- all of the last stage's Cg channel (level 0, band x10) -- come out
-// of ONE coder state, serially; a lone wavefront issues one instruction every ~4 cycles whatever it does, so everything that does not
-// depend on the coder state is done by other wavefronts of the workgroup:
-//   * kTailAhead wavefronts per chain PREPARE symbols: the position's CNN outputs, the component's mean / 1 / sigma / normalised
-//     weight with mix_component()'s operations, the approximate mixture at the 64 anchors 8 l (Lp <= 512) -- and, round 5, a
-//     SPECULATED WINDOW: the twelve exact table entries around the mixture's median (where the approximate table crosses 2^15).
-//     Round r + 1's symbols are prepared (into the other half of a ping-pong LDS buffer) while
-//   * wavefront 0 DECODES round r's: if the slot lies inside the speculated window the symbol is proved by one compare, a ballot and
-//     two v_readlane, and the state update runs on the scalar unit (the state is wave-uniform); otherwise the anchors pick a bucket,
-//     12 x 5 lanes evaluate the 12 exact entries around it (lane = 5 e + mc: mixture component mc of window entry e) and a ballot
-//     proves the symbol (an exact 13-ary search takes over when that hint is wrong too).  Either way the symbol is the one an exact
-//     search of the whole row returns: the entries are the same bits wherever they are computed.  The renormalisation's bits come
-//     from two payload dwords requested at the top of the symbol (they depend on the cursor only); the round's pixels are stored
-//     together.
-// What the window buys depends on the source: on uniform noise (12.8 bits per symbol, tails of ~620 symbols) it is not offered (the
-// median's bucket holds a fiftieth of the mass) and nothing changes; on a source as cheap as the reference's trained model (1.7 bits
-// per symbol: tails of ~4,700 symbols, all on one chain) the tail launch of 24 x 10 xwide streams goes from 2.70 to 1.29 ms, 64-lane
-// streams 0.66 -> 0.34 (profiles/r5/tail_speculation.json: coder alone 1.2 ms, preparing wavefronts alone 1.2 ms).
-// One barrier per round.  Checks: the main region was read to its last bit, the tail state ends at its start state (freq << 15 of
-// the symbol the tail encoder began with; 2^31 when T = 0) with no bit left.  Xwide streams (two seeded chains, above): a second set of
-// wavefronts runs chain B; the start states are seeds -- checked to be below A^n, with zero digits where the stream has no symbol -- the
-// chains' cursors must not have crossed and the payload between them must be zero.  A ONE-chain xwide stream (cheap symbols: the second
-// chain would cost its final state) leaves chain B's wavefronts idle: its preparing wavefronts join chain A's, a round is 2 kTailAhead symbols.
-#ifndef TAIL_AHEAD
-#define TAIL_AHEAD 4                            // (build switch for A/B runs: 2 / 3 / 4 / 5 measured, profiles/r5/tail_speculation.json)
-#endif
-#ifndef TAIL_SPEC
-#define TAIL_SPEC 1                             // the preparing wavefronts offer a speculated window (0: the coder always evaluates its own -- the kernel of rounds 3-4)
-#endif
-constexpr int kTailAhead = TAIL_AHEAD;           // symbols per round = preparing wavefronts
-
-template <int Q> constexpr int kTailChains = kSeeded<Q> ? 2 : 1;      // xwide: two chains, each with its own coder + preparing wavefronts
-
-template <int Q>
-__global__ __launch_bounds__(64 * (1 + kTailAhead) * kTailChains<Q>) void rans_tail_kernel(const float *__restrict__ params, const StageGeom *__restrict__ sgv, const StreamRef *__restrict__ sref,
-                                                       const uint32_t *__restrict__ rstate, const uint32_t *__restrict__ rpos,
-                                                       const uint32_t *__restrict__ rtail,
-                                                       int16_t *__restrict__ planes, float *__restrict__ fplanes,
-                                                       const int32_t *__restrict__ minmax, int32_t *status,
-                                                       const uint8_t *__restrict__ slots, const long *__restrict__ rslot_off,
-                                                       const int *__restrict__ act = nullptr)
-{
-    using GEO = RansGeo<Q>;
-    constexpr int L = 64 * Q, NCH = kTailChains<Q>;
-    constexpr int kSpillDw = kSeeded<Q> ? kRansSpillMax / 32 + 1 : 0;      // xwide v4: the arena is the payload ++ the spill the main decoder left at the bottom of its region
-    __shared__ uint32_t sh_pay[64 * Q + 2 + kSpillDw];
-    constexpr int NSL = NCH * kTailAhead;               // prepared symbols per round and buffer: slot = chain kTailAhead + i
-    __shared__ float sh_cmp[2][NSL][16];                // [0..4] mu, [5..9] 1 / sigma, [10..14] normalised weight of the five components
-    __shared__ int sh_e1[2][NSL][64];                   // approximate table entry at anchor 8 l
-    __shared__ long sh_off[2][NSL];                     // the symbol's pixel
-    __shared__ int sh_spec[2][NSL][16];                 // [0..11] the exact entries of the speculated window, [12] its first index (-1: none)
-    __shared__ int sh_cur[2];                           // xwide: where the two chains stopped reading
-    const int sidx = act ? act[blockIdx.x] : (int)blockIdx.x;      // (act: a per-image-reduce call's list of the level's streams, llicti_decode_images_*_rv)
-    const StreamRef sr_ = sref[sidx];               // the stream's image, its index among the image's streams, the image's stream count (images of a call may differ)
-    const int b = sr_.b, m = sr_.m, M = sr_.M;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (scalar: roles, chains and symbol counts are wave-uniform, their branches scalar)
-    // role 0: the chain's coder.  A workgroup's wavefronts go to the four SIMDs round robin: with two chains the coders are wavefronts 0 and 1 (their
-    // own SIMD each, shared with one preparing wavefront), not 0 and 4 (the same SIMD, taking turns at its issue port)
-    const int role = wave / NCH;
-    const StageGeom sg = sgv[b];                 // the image's own stage geometry (the images of a call may differ in size)
-    const int nc = sg.hc * sg.wc;
-    const int cnt = rans_stream_count(nc, m, M, L);
-    const int rt = (int)(rtail[sidx] & 0xFFFFu);
-    const int nch = (kSeeded<Q> && !(rtail[sidx] >> 16)) ? 2 : 1;      // chains this stream's tail was coded with (xwide: its flag says one or two)
-    // A one-chain xwide stream (well-predicted content: the second chain would cost its final state) has twice the symbols on its chain and a
-    // second set of wavefronts with nothing to do: the idle chain's preparing wavefronts join chain 0's, and a round is 2 kTailAhead symbols.
-    const bool pool = NCH == 2 && nch == 1;
-    const int chain = (pool && role != 0) ? 0 : wave % NCH;
-    const int SA = pool ? NSL : kTailAhead;             // symbols of a chain per round = its preparing wavefronts
-    // 64 / 128 lanes: the main region must have been read to its last bit.  xwide v4: what is left of it IS the tail coder's spill (its length the cursor)
-    const int E = kSeeded<Q> ? (int)rpos[sidx] : 0;
-    bool bad = (kSeeded<Q> ? E >= kRansSpillMax : rpos[sidx] != 0) || rt > cnt;
-    const int alen = GEO::kPayBits + (bad ? 0 : E);     // the arena
-    const int Tall = min(rt, cnt);                      // the stream's tail symbols: the coded ones, then (xwide) the seeds'
-    int minv, maxv, shift;
-    clr_range(minmax + 4 * b, 2, minv, maxv, shift);
-    const Grid gr = make_grid(minv, maxv);
-    const int max_symbol = gr.Lp - 2;
-    uint32_t pw = 1;
-    const int ns = kSeeded<Q> ? rans_seed_count(max_symbol + 1, pw) : 0;
-    const int sn = kSeeded<Q> ? (nch == 2 ? ns : 1) : 0;     // raw symbols in a chain's start state (xwide v4: n per chain of two, the stream's last symbol for one chain)
-    const int NS = min(nch * sn, cnt);                  // seed symbols (0 for the older stream kinds)
-    bad = bad || Tall < NS || (nch == 2 && cnt < 2 * ns);
-    const bool live = chain < nch;                      // (the second set of wavefronts idles through a one-chain stream's rounds)
-    const int Tc = max(Tall - NS, 0);                   // coded symbols; the one with index idx (j = nch ns + idx from the stream's end) is on chain idx % nch
-    const int T = live ? (Tc + nch - 1 - chain) / nch : 0;      // this chain's
-    const int R = ((Tc + nch - 1) / nch + SA - 1) / SA;      // rounds (chain 0 has the most symbols)
-    const long img = sg.img_off;
-    const int mc = lane % 5, we = lane / 5;
-    auto pixel_of = [&](int j) -> long {                 // the stream's j-th symbol from its end
-        const int q = min(max(cnt - 1 - j, 0), max(cnt - 1, 0));
-        const int n = min(rans_stream_pos(q, m, M, L), nc - 1);
-        const int pi = div_wc(sg, n), pj = n - pi * sg.wc;
-        return ((long)pi << 32) | (uint32_t)pj;
-    };
-
-    if (role != 0) {
-        // ---- preparing wavefronts: symbol t = SA r + i of round r (t counts the chain's symbols in decoding order), prepared into slot sl
-        const int i = pool ? wave - NCH : role - 1;
-        const int sl = chain * kTailAhead + i;
-        struct Row { float sg, mu, wk, bb, dd, y, co; long off; };
-        auto fetch = [&](int t) -> Row {
-            Row r;
-            const long pp = pixel_of(nch * sn + chain + nch * (T - 1 - t));
-            const int pi = (int)(pp >> 32), pj = (int)(uint32_t)pp;
-            const ParRow src = par_row(params + sg.par_off, 0, (long)sg.h * sg.w, (long)pi * sg.w + pj);
-            r.off = img + ((long)(2 * pi + sg.oi) << sg.lvl) * sg.W + ((long)(2 * pj + sg.oj) << sg.lvl);
-            r.sg = src[10 + mc]; r.mu = src[16 + 10 + mc]; r.wk = src[32 + 10 + mc];      // the Cg channel's sigma, mu, weight ...
-            r.bb = src[48 + 5 + mc]; r.dd = src[48 + 10 + mc];                                // ... and its cross-channel factors
-            r.y = fplanes[r.off]; r.co = fplanes[r.off + sg.plane];
-            return r;
-        };
-        auto prepare = [&](const Row &row, int buf) {
-            // component mc: mix_component<2>'s operations, written out (profiles/README.md, section decoder_parts)
-            const float t1 = row.bb * row.y;
-            const float t2 = row.dd * row.co;
-            const float tt = t1 + t2;
-            const float mu = row.mu + tt;
-            const float rsig = 1.0f / mix_sigma(row.sg);
-            const float w = (row.wk > kWeightBound) ? row.wk : kWeightBound;
-            float wk5[5], mu5[5], rs5[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) wk5[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), k));
-            const float wn = w / mix_weight_den(wk5[0], wk5[1], wk5[2], wk5[3], wk5[4]);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                mu5[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mu), k));
-                rs5[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rsig), k));
-                wk5[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wn), k));
-            }
-            // the approximate mixture (all five components in every lane) at anchor 8 l
-            const int i1 = min(8 * lane, max_symbol);
-            const float pt1 = sample_pt(gr, i1);
-            float sum = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) { Comp ck; ck.mu = mu5[k]; ck.rsig = rs5[k]; ck.wn = wk5[k]; sum += term_fast(comp_fast(ck), pt1); }
-            const int e1v = (int)__builtin_rintf(sum * gr.scale) + i1;
-            sh_e1[buf][sl][lane] = e1v;
-            if (lane < 5) { sh_cmp[buf][sl][lane] = mu; sh_cmp[buf][sl][5 + lane] = rsig; sh_cmp[buf][sl][10 + lane] = wn; }
-            if (lane == 0) sh_off[buf][sl] = row.off;
-            // The speculated window.  The coder's per-symbol chain is slot -> bucket -> 12 exact entries (an erfc and five cross-lane
-            // moves) -> ballot -> state update, ~2,500 cycles of which the exact entries are most -- and they depend on the coder state
-            // only through WHERE the window lies.  On a well-predicted source (the reference's trained model spends 1.7 bits per symbol of
-            // this channel) that is nearly always around the mixture's median, which is known here: the anchor bucket in which the
-            // approximate table crosses 2^15, refined linearly.  So the window's twelve entries are computed in THIS wavefront, with
-            // entry_at()'s operations in its order, and the coder only has to look: slot inside [entry 0, entry 11) proves the symbol
-            // exactly as its own window would (same entries, same ballot); outside, it falls back to its bucket search.  Not offered when
-            // the median's bucket holds less than an eighth of the mass (noise: the window would miss nine times in ten).
-            const int lst = __builtin_amdgcn_readfirstlane(__builtin_popcountll(ballot64(lane == 0 || (8 * lane <= max_symbol && e1v <= 0x8000))) - 1);
-            const int eL = __builtin_amdgcn_readlane(e1v, lst);
-            const int eH = (lst < 63 && 8 * (lst + 1) <= max_symbol) ? __builtin_amdgcn_readlane(e1v, min(lst + 1, 63)) : 0x10000;
-            int wbs = -1;
-            if (TAIL_SPEC && eH - eL >= 0x2000) {         // (wave-uniform)
-                const float fr = 8.0f * (float)(0x8000 - eL) * __builtin_amdgcn_rcpf((float)(eH - eL));
-                wbs = max(8 * lst + (int)__builtin_amdgcn_fmed3f(fr, 0.0f, 8.0f) - 5, 0);
-                const int idx = wbs + min(we, 11);
-                const float ptx = sample_pt(gr, min(idx, gr.Lp - 1));
-                const float term = mix_term(wn, mu, rsig, ptx);
-                const int g0 = 4 * 5 * min(we, 11);
-                const float a0 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0, __float_as_int(term)));
-                const float a1 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 4, __float_as_int(term)));
-                const float a2 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 8, __float_as_int(term)));
-                const float a3 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 12, __float_as_int(term)));
-                const float a4 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 16, __float_as_int(term)));
-                const float acc = (((a0 + a1) + a2) + a3) + a4;
-                const uint32_t ent = (idx <= max_symbol) ? entry_from_sum(acc, gr.scale, idx) : 0x10000u;
-                if (mc == 0 && we < 12) sh_spec[buf][sl][we] = (int)ent;
-            }
-            if (lane == 0) sh_spec[buf][sl][12] = wbs;
-        };
-        Row rowA = fetch(i);
-        Row rowB = fetch(SA + i);
-        prepare(rowA, 0);
-        __syncthreads();                                  // (payload assembled by wavefront 0)
-        __syncthreads();                                  // round 0 is prepared
-        for (int r = 0; r < R; ++r) {
-            const Row rowC = fetch(SA * (r + 2) + i);            // two rounds ahead: the loads run under a whole round
-            if (SA * (r + 1) + i < T) prepare(rowB, (r + 1) & 1);
-            rowB = rowC;
-            lds_barrier();      // LDS words only cross here: global loads / stores in flight stay in flight (common.hpp)
-        }
-        if constexpr (kSeeded<Q>) lds_barrier();          // (the coders exchange their cursors)
-        return;
-    }
-
-    // ---- role 0: the chain's coder (wavefront 0 assembles the payload for both)
-    if (wave == 0) {
-#pragma unroll
-        for (int qq = 0; qq < Q; ++qq) sh_pay[64 * qq + lane] = 0;
-        if (lane < 2) sh_pay[64 * Q + lane] = 0;
-        __builtin_amdgcn_wave_barrier();                  // same wavefront, in-order LDS
-#pragma unroll
-        for (int qq = 0; qq < Q; ++qq) {
-            const uint32_t xl = rstate[((long)sidx * Q + qq) * 64 + lane] & 0x7FFFFFFFu;
-            lds_or_bits(sh_pay, kRansStateBits * (64 * qq + lane), 16, xl & 0xFFFFu);
-            lds_or_bits(sh_pay, kRansStateBits * (64 * qq + lane) + 16, kRansStateBits - 16, xl >> 16);
-        }
-        if constexpr (kSeeded<Q>) {
-            // the spill: bits [0, E) of the stream's bit region (slot + 4), behind the payload's 248 dwords; what lies above it in the region is not the tail's
-            if (lane < kSpillDw) {
-                const uint32_t w = reinterpret_cast<const uint32_t *>(slots + rslot_off[sidx] + 4)[lane];
-                const int nb = min(max(alen - GEO::kPayBits - 32 * lane, 0), 32);
-                sh_pay[GEO::kPayDw + lane] = nb >= 32 ? w : (w & ((1u << nb) - 1u));
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t xt;
-    int tc;                                               // bit cursor: legacy chains and xwide chain B read DOWN to it, xwide chain A reads UP from it
-    int a_end = alen;                                     // xwide, one chain: its end marker (the bits it may read end there)
-    if constexpr (kSeeded<Q>) {
-        // final states at fixed places: chain A's in bits [0, 32), chain B's in the arena's top 32 bits (the state is wave-uniform: kept scalar)
-        xt = !live ? (1u << 31) : (uint32_t)__builtin_amdgcn_readfirstlane((int)(chain ? lds_get_bits(sh_pay, alen - 32, 32) : sh_pay[0]));
-        tc = chain ? alen - (live ? 32 : 0) : 32;
-        if (nch == 2) { if (!(xt >> 31)) { bad = true; xt |= 1u << 31; } }
-        else {
-            // one chain: the arena's highest set bit above the state is the chain's end marker (a spill ends with it)
-            int top = -1;
-            for (int d0 = 64 * ((GEO::kPayDw + kSpillDw - 1) / 64); d0 >= 0 && top < 0; d0 -= 64) {
-                const int d = d0 + lane;
-                const uint32_t w = (d >= 1 && d < GEO::kPayDw + kSpillDw) ? sh_pay[d] : 0u;
-                const uint64_t nz = ballot64(w != 0);
-                if (nz) {
-                    const int hl = 63 - __clzll((long long)nz);
-                    top = 32 * (d0 + hl) + 31 - __clz((int)__builtin_amdgcn_readlane((int)w, hl));
-                }
-            }
-            if (top < 32 || (alen > GEO::kPayBits && top != alen - 1)) { bad = true; top = 32; }
-            a_end = top;
-        }
-    } else {
-        int top = -1;                                                          // the payload's highest set bit
-#pragma unroll
-        for (int qq = Q - 1; qq >= 0; --qq) {
-            const uint64_t nz = ballot64(sh_pay[64 * qq + lane] != 0);
-            if (top < 0 && nz) {
-                const int hd = 64 * qq + 63 - __clzll((long long)nz);
-                top = 32 * hd + 31 - __clz((int)sh_pay[hd]);
-            }
-        }
-        // a malformed stream still gets its T tail pixels written (from whatever state there is): the output of a flagged image
-        // must not depend on what the workspace held
-        if (top < 31) bad = true;
-        xt = (top >= 31) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_get_bits(sh_pay, top - 31, 32)) : (1u << 31);
-        tc = (top >= 31) ? top - 31 : 0;
-    }
-    __syncthreads();                                      // round 0 is prepared
-    for (int r = 0; r < R; ++r) {
-        const int buf = r & 1;
-        int vsym = 0;
-        for (int i = 0; i < SA && SA * r + i < T; ++i) {
-            const int sl = chain * kTailAhead + i;
-            const uint32_t slot = xt & 0xFFFFu;
-            // 0. the window the preparing wavefront speculated on (around the mixture's median), if it offered one: its twelve exact entries are there
-            //    already -- lane k < 12 reads entry k, lane 12 the window's first index -- and the symbol is the last entry <= slot, proved when its
-            //    successor is in the window too.  Everything from here to the next state is wave-uniform and meant for the scalar unit: ballot,
-            //    count, two v_readlane, the state update.
-            const int wv = sh_spec[buf][sl][min(lane, 12)];
-            // the <= 16 bits the renormalisation will take lie in two dwords that only depend on the cursor: requested here, next to the window, so that
-            // the LDS round trip runs under the search instead of behind the state update
-            const bool up = kSeeded<Q> && chain == 0;            // xwide chain A reads UP from its cursor, everything else DOWN to it
-            const int wpos = min(max(up ? tc : tc - 16, 0), alen);               // (a corrupt stream's cursor stays inside the arena's array)
-            const uint32_t bw0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh_pay[wpos >> 5]);
-            const uint32_t bw1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh_pay[(wpos >> 5) + 1]);
-            auto take_bits = [&](int pos, int n) -> uint32_t {   // bits [pos, pos + n) of the payload, n <= 16, inside the window
-                const uint64_t w = ((uint64_t)bw1 << 32) | bw0;
-                return (uint32_t)(w >> (pos - (wpos & ~31))) & ((1u << n) - 1u);
-            };
-            int wb = __builtin_amdgcn_readlane(wv, 12), np = 0;
-            // (entries past the top symbol are 2^16, never <= slot; entry 0 is the floor of the search: counted whatever it holds)
-            if (wb >= 0) np = __builtin_popcountll((ballot64((uint32_t)wv <= slot) & 0xFFFull) | (wb == 0 ? 1ull : 0ull));
-            uint32_t vlo, vhi;
-            if (np >= 1 && np <= 11) {
-                vlo = (uint32_t)__builtin_amdgcn_readlane(wv, np - 1);
-                vhi = (uint32_t)__builtin_amdgcn_readlane(wv, np);
-            } else {
-                const float mu = sh_cmp[buf][sl][mc], rsig = sh_cmp[buf][sl][5 + mc], wn = sh_cmp[buf][sl][10 + mc];
-                const int e1 = sh_e1[buf][sl][lane];
-                // exact entry idx (uniform in the lane's group of five): valid in every lane of the group
-                auto entry_at = [&](int idx) -> uint32_t {
-                    const float pt = sample_pt(gr, min(idx, gr.Lp - 1));
-                    const float term = mix_term(wn, mu, rsig, pt);
-                    const int g0 = 4 * 5 * min(we, 11);
-                    const float a0 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0, __float_as_int(term)));
-                    const float a1 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 4, __float_as_int(term)));
-                    const float a2 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 8, __float_as_int(term)));
-                    const float a3 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 12, __float_as_int(term)));
-                    const float a4 = __int_as_float(__builtin_amdgcn_ds_bpermute(g0 + 16, __float_as_int(term)));
-                    const float acc = (((a0 + a1) + a2) + a3) + a4;
-                    return (idx <= max_symbol) ? entry_from_sum(acc, gr.scale, idx) : 0x10000u;      // past the top symbol: c_high = 2^16
-                };
-                // 1. hint: the bucket of 8 entries the prepared anchors put the slot in
-                const uint64_t p1 = ballot64(lane == 0 || (8 * lane <= max_symbol && e1 <= (int)slot));
-                wb = max(8 * (__builtin_popcountll(p1) - 1) - 2, 0);
-                // 2. proof: the 12 exact entries wb .. wb + 11; the symbol is the last one <= slot, its successor must be in the window too
-                uint32_t ent = entry_at(wb + we);
-                const uint64_t pw12 = ballot64(mc == 0 && we < 12 && wb + we <= max_symbol && (ent <= slot || wb + we == 0));
-                np = __builtin_popcountll(pw12);
-                if (np == 0 || np == 12) {
-                    // the hint was wrong (only absurd mixtures get here): exact 13-ary search from scratch, then the window at the result
-                    int lo = 0, hi = max_symbol + 1;
-                    while (hi - lo > 1) {
-                        const int stp = (hi - lo + 12) / 13;
-                        const int pi = min(lo + stp * (min(we, 11) + 1), hi - 1);
-                        const uint32_t e = entry_at(pi);
-                        const uint64_t pb = ballot64(mc == 0 && we < 12 && e <= slot);
-                        const int k = __builtin_popcountll(pb);                        // probes are ordered: the passes form a prefix
-                        const int nlo = (k > 0) ? min(lo + stp * k, hi - 1) : lo;
-                        const int nhi = (k < 12) ? min(lo + stp * (k + 1), hi - 1) : hi;
-                        lo = nlo; hi = nhi;
-                    }
-                    wb = lo;
-                    ent = entry_at(wb + we);
-                    np = 1;
-                }
-                vlo = (uint32_t)__builtin_amdgcn_readlane((int)ent, 5 * (np - 1));
-                vhi = (uint32_t)__builtin_amdgcn_readlane((int)ent, 5 * np);
-            }
-            vsym = (lane == i) ? wb + np - 1 - shift : vsym;      // the round's pixels are stored together, lane i symbol i (one vector store per round instead of a masked block per symbol)
-            xt = (vhi - vlo) * (xt >> 16) + slot - vlo;
-            if constexpr (kSeeded<Q>) {
-                int nb = __clz((int)xt);
-                if (nch == 2) {
-                    const int avail = chain ? tc - 32 : alen - 32 - tc;      // (never into the other chain's state; whether the chains crossed is checked at the end)
-                    if (nb > 16 || avail < nb) { bad = true; nb = max(min(nb, min(avail, 16)), 0); }   // corrupt: keep going on what is there
-                    if (chain) tc -= nb;
-                    xt = ((xt << nb) | take_bits(tc, nb)) | (1u << 31);
-                    if (!chain) tc += nb;
-                } else {
-                    // one chain: it started small and emitted nothing until its state had grown -- so once the bits below the end marker are used
-                    // up the decoder is in that silent start: it takes what is left (the encoder's first emission: < 16 bits) and then nothing
-                    const int avail = a_end - tc;
-                    if (nb > avail) nb = max(avail, 0);
-                    else if (nb > 16) bad = true;                     // bits were left, so the encoder's state was in [2^31, 2^32): corrupt
-                    if (nb > 16) { bad = true; nb = 16; }
-                    xt = (xt << nb) | take_bits(tc, nb);
-                    tc += nb;
-                }
-            } else if (SA * r + i == T - 1) bad = bad || xt != (vhi - vlo) << 15;      // the encoder's first symbol: absorbing start, no bits
-            else {
-                int nb = __clz((int)xt);
-                if (nb > 16 || tc < nb) { bad = true; nb = max(min(nb, min(tc, 16)), 0); }  // corrupt: keep going on what is there
-                tc -= nb;
-                xt = ((xt << nb) | take_bits(tc, nb)) | (1u << 31);
-            }
-        }
-        if (lane < SA && SA * r + lane < T) {
-            const long off = sh_off[buf][chain * kTailAhead + lane];
-            planes[off + 2 * sg.plane] = (int16_t)vsym;
-            fplanes[off + 2 * sg.plane] = div255_exact((float)vsym);      // (an integer in [-255, 255]: bit-identical to the division, numerics.hpp)
-        }
-        lds_barrier();      // LDS words only cross here: global loads / stores in flight stay in flight (common.hpp)
-    }
-    if constexpr (kSeeded<Q>) {
-        // the chain is back at its start state.  Two chains: 2^31 | its n seed symbols in radix A (lane i: digit i = the stream's (chain n + i)-th symbol
-        // from the end).  One chain: the stream's last symbol itself (zero if the stream has none), every bit below the end marker read.
-        const uint32_t A = (uint32_t)(max_symbol + 1), v = (nch == 2) ? (xt & 0x7FFFFFFFu) : xt;
-        bad = bad || (live && (nch == 2 ? v >= pw : (v >= A || tc != a_end)));
-        uint32_t div = 1;
-        for (int e = 0; e < min(lane, sn); ++e) div *= A;
-        const int dg = (lane < sn) ? (int)((v / div) % A) : 0;
-        const int j = chain * sn + lane;
-        if (live && lane < sn && j < NS) {
-            const long pp = pixel_of(j);
-            const int pi = (int)(pp >> 32), pj = (int)(uint32_t)pp;
-            const long off = img + ((long)(2 * pi + sg.oi) << sg.lvl) * sg.W + ((long)(2 * pj + sg.oj) << sg.lvl);
-            const int pv = dg - shift;
-            planes[off + 2 * sg.plane] = (int16_t)pv;
-            fplanes[off + 2 * sg.plane] = div255_exact((float)pv);
-        }
-        bad = bad || ballot64(live && lane < sn && j >= NS && dg != 0) != 0;      // digits of symbols the stream does not have
-        if (lane == 0) sh_cur[chain] = tc;
-        lds_barrier();
-        if (chain == 0 && nch == 2) {
-            // the chains must not have crossed, and what lies between them is zero
-            const int ca = sh_cur[0], cb = sh_cur[1];
-            uint32_t nz = 0;
-            for (int d = lane; d < GEO::kPayDw + kSpillDw; d += 64) {
-                const int lo = max(ca, 32 * d), hi = min(cb, 32 * d + 32);
-                if (lo < hi) nz |= sh_pay[d] & ((hi - lo == 32) ? 0xFFFFFFFFu : (((1u << (hi - lo)) - 1u) << (lo - 32 * d)));
-            }
-            bad = bad || ca > cb || ballot64(nz != 0) != 0;
-        }
-        if (bad && lane == 0) flag_image(status, b, LLICTI_EFORMAT);
-    } else {
-        if (T == 0) bad = bad || xt != (1u << 31);
-        if ((bad || tc != 0) && lane == 0) flag_image(status, b, LLICTI_EFORMAT);
     }
 }
 

@@ -110,17 +110,16 @@ template <int Q> __device__ __forceinline__ SeededTail encode_tail_seeded(RansEn
         const int wsum = __builtin_amdgcn_readlane(wave_incl_scan(wgt), 63);
         if (2 * wsum * ns >= k64 * (64 + ns)) nch = 2;
     }
-    const int sn = (nch == 2) ? ns : 1;                                // raw symbols in a chain's start state
+    const SeededTailShape shape = seeded_tail_shape(cnt, min(cnt, kRansTailMaxX), nch, ns);      // the seeds, and the candidates: coded up to where the rule stops
     const int fixed = (nch == 2) ? 64 : 33;                            // the final states; one chain: + its end marker
-    const int NS = min(nch * sn, cnt);
-    const int ncod = max(min(cnt, kRansTailMaxX) - nch * sn, 0);       // candidates j = nch sn + idx, idx < ncod; chain c takes idx = nch i + c
-    const int n_own = (wq < nch) ? (ncod + nch - 1 - wq) / nch : 0;
-    const int nblk = ((ncod + nch - 1) / nch + 31) >> 5;               // chain A's steps, in blocks
+    const int NS = shape.NS, ncod = shape.ncod;
+    const int n_own = (wq < nch) ? shape.chain_count(wq) : 0;
+    const int nblk = (shape.chain_count(0) + 31) >> 5;                 // chain A's steps, in blocks
     uint32_t xc = (nch == 2) ? (1u << 31) : 0u;
     if (wq < nch) {
-        const int j = wq * sn + lane;
+        const int j = shape.seed_index(wq, lane);
         int term = 0;
-        if (lane < sn && j < cnt) {
+        if (lane < shape.sn && j < cnt) {
             const int n = rans_stream_pos(cnt - 1 - j, e.m, e.M, L);
             const int pi = div_wc(sgl, n), pj = n - pi * sgl.wc;
             int sv = (int)planes[sgl.img_off + 2 * sgl.plane + ((long)(2 * pi + sgl.oi) << sgl.lvl) * sgl.W + ((long)(2 * pj + sgl.oj) << sgl.lvl)] + shift;
@@ -133,7 +132,7 @@ template <int Q> __device__ __forceinline__ SeededTail encode_tail_seeded(RansEn
     }
     auto fetch_blk = [&](int blk) -> uint32_t {     // lane t < 32: step 32 blk + t of the wavefront's chain
         const int i = 32 * blk + (lane & 31);
-        return (i < n_own) ? e.last_pair(cnt - 1 - (nch * sn + nch * i + wq)) : 0u;
+        return (i < n_own) ? e.last_pair(cnt - 1 - shape.index(wq, i)) : 0u;
     };
     int used = 0, blk = 0, prev_tot = 0;
     uint32_t raw = fetch_blk(0);

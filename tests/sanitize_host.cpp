@@ -146,6 +146,42 @@ int main()
                 }
                 for (int n = 0; n < nc; ++n) REQUIRE(seen[(size_t)n] == 1);
             }
+    // SeededTailShape: an xwide v4 tail's symbols on its chains, for every tail length the format allows -- T = min(32 f, cnt), f <= 255, at
+    // least the seeds, two chains only where the stream holds both seeds.  The chains' counts sum to the coded count; the j of all chains'
+    // symbols and of the seeds are 0 .. T - 1, each once; chain 0 never has fewer symbols than chain 1.
+    for (int cnt : { 0, 1, 2, 3, 31, 32, 33, 63, 64, 65, 8160 })
+        for (int nch : { 1, 2 })
+            for (int ns : { 3, 5, 31 }) {
+                if (nch == 2 && cnt < 2 * ns) continue;
+                for (int f = 0; f <= kRansTailMaxX / kRansTailBlock; ++f) {
+                    const int tall = std::min(kRansTailBlock * f, cnt);
+                    const SeededTailShape sh = seeded_tail_shape(cnt, tall, nch, ns);
+                    if (tall < sh.NS) continue;
+                    REQUIRE(sh.NS + sh.ncod == tall);
+                    int sum = 0;
+                    std::vector<int> seen((size_t)tall, 0);
+                    for (int c = 0; c < nch; ++c) {
+                        sum += sh.chain_count(c);
+                        for (int i = 0; i < sh.chain_count(c); ++i) {
+                            const int j = sh.index(c, i);
+                            REQUIRE(j >= sh.NS && j < tall);
+                            ++seen[(size_t)j];
+                        }
+                        for (int d = 0; d < sh.sn; ++d)
+                            if (sh.seed_index(c, d) < sh.NS) ++seen[(size_t)sh.seed_index(c, d)];
+                    }
+                    REQUIRE(sum == sh.ncod);
+                    for (int j = 0; j < tall; ++j) REQUIRE(seen[(size_t)j] == 1);
+                    if (nch == 2) REQUIRE(sh.chain_count(0) >= sh.chain_count(1));
+                }
+            }
+    // ... and a 64- / 128-lane stream's tail to the tail decoder (seeded = false): one chain, no seeds, symbol i of the chain is j = i
+    for (int cnt : { 0, 1, 2, 3, 31, 32, 33, 63, 64, 65, 8160 })
+        for (int tall = 0; tall <= std::min(cnt, kRansTailMax); ++tall) {
+            const SeededTailShape sh = seeded_tail_shape(cnt, tall, 1, 0, false);
+            REQUIRE(sh.NS == 0 && sh.ncod == tall && sh.chain_count(0) == tall);
+            for (int i = 0; i < tall; i += (tall > 64 ? 61 : 1)) REQUIRE(sh.index(0, i) == i);
+        }
     for (int mode : { -1, 1, 0x100, 0x100 | 33, 0x100 | 127, 0x300 | 15, 0x500, 0x500 | 33, 0x500 | 96, 0x700 | 1, 0x10000 }) REQUIRE(mode_streams(mode) < 0);
     // every (byte 0, pad field high bits) pair: either not a container of this build, or a mode that round-trips; the xwide v3 tags of rounds 4-5
     // (v = 17 .. 31) and an xwide v4 tag without its count are refused, and so are high bits in a container that is not xwide
