@@ -246,10 +246,12 @@ def stream_positions(nc, m, M, L):
     return steps
 
 
-def decode(segs, rows, canonical=True, on_stage=None):
+def decode(segs, rows, canonical=True, on_stage=None, on_tail=None):
     """segs: the container's segments, 4 header segments then 9 x nlevels stream segments.  rows(stage, decoded) -> the stage's CDF rows, one list of
     Lp ints per symbol in cropped raster order; decoded is the list of the earlier stages' symbol lists.  -> (decoded, info).
-    info: header dict, "streams": one facts dict per stream, "last_freqs": the frequencies of the last stage's symbols."""
+    info: header dict, "streams": one facts dict per stream, "last_freqs": the frequencies of the last stage's symbols.
+    on_tail(stream_index, j, row, slot, symbol): called for every CODED tail symbol (not the seeds' raw ones), j counting from the stream's end,
+    slot = the low 16 bits of the chain's state in front of the symbol -- an observer (tests/tail_census.py); no check depends on it."""
     if len(segs[0]) != 3 or len(segs[1]) != 12 or len(segs[2]) != 2:
         raise Refused("segments", "header segment lengths")
     pad = int.from_bytes(segs[2], "little")
@@ -294,11 +296,12 @@ def decode(segs, rows, canonical=True, on_stage=None):
                     out[n] = sym
                 q += len(step)
         if last:
-            for s, seq, T in tails:
+            for m, (s, seq, T) in enumerate(tails):
+                note = None if on_tail is None else (lambda j, row, slot, sym, m=m: on_tail(m, j, row, slot, sym))
                 if layout == "v3":
-                    _tail_v3(s, seq, T, table, out, canonical)
+                    _tail_v3(s, seq, T, table, out, canonical, note)
                 else:
-                    _tail_v4(s, seq, T, table, out, A, canonical)
+                    _tail_v4(s, seq, T, table, out, A, canonical, note)
         decoded.append(out)
         if on_stage is not None:
             on_stage(st, out)
@@ -307,7 +310,7 @@ def decode(segs, rows, canonical=True, on_stage=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------- tails
-def _tail_v3(s, seq, T, table, out, canonical):
+def _tail_v3(s, seq, T, table, out, canonical, note=None):
     """64 / 128 lanes: one chain inside the 31 L payload bits, its final state on top, the bits going down to bit 0; the first pushed symbol (the
     stream's last) started from f << 15."""
     cnt = len(seq)
@@ -328,8 +331,11 @@ def _tail_v3(s, seq, T, table, out, canonical):
     x = x_final = pay >> cur
     f = None
     for q in range(cnt - T, cnt):
+        slot = x & 0xFFFF
         sym, x, _, f = pop(x, table[seq[q]])
         out[seq[q]] = sym
+        if note is not None:
+            note(cnt - 1 - q, table[seq[q]], slot, sym)
         if q < cnt - 1:
             n = clz32(x)
             if n > 16:
@@ -350,7 +356,7 @@ def _tail_v3(s, seq, T, table, out, canonical):
             raise NotCanonical("T-rule", "one more tail symbol fits the payload")
 
 
-def _tail_v4(s, seq, T, table, out, A, canonical):
+def _tail_v4(s, seq, T, table, out, A, canonical, note=None):
     cnt = len(seq)
     L = s.L
     paybits = STATE_BITS * L
@@ -374,8 +380,11 @@ def _tail_v4(s, seq, T, table, out, A, canonical):
         cur = 32
         s.facts.update(tail_final_state=x)
         for j in range(T - 1, 0, -1):
+            slot = x & 0xFFFF
             sym, x, _, _ = pop(x, row_of(j))
             out[seq[cnt - 1 - j]] = sym
+            if note is not None:
+                note(j, row_of(j), slot, sym)
             left = mk - cur
             z = clz32(x)
             if z > left:                                        # the encoder's silent start: what is left is all there is
@@ -407,6 +416,7 @@ def _tail_v4(s, seq, T, table, out, A, canonical):
         ca, cb = 32, alen - 32
         s.facts.update(tail_final_state=xa)
         for j in range(T - 1, 2 * n_seed - 1, -1):
+            slot = (xa if j % 2 == 0 else xb) & 0xFFFF
             if j % 2 == 0:
                 sym, xa, _, _ = pop(xa, row_of(j))
                 n = clz32(xa)
@@ -427,6 +437,8 @@ def _tail_v4(s, seq, T, table, out, A, canonical):
                 xb = ((xb << n) | field(arena, cb, n)) & M32
             out[seq[cnt - 1 - j]] = sym
             fbits.append(n)
+            if note is not None:
+                note(j, row_of(j), slot, sym)
         if field(arena, ca, cb - ca):
             raise Refused("between", "set bits between the two chains")
         for x, base in ((xa, 0), (xb, n_seed)):

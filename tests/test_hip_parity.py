@@ -419,7 +419,9 @@ def test_rans_xwide_container_bitexact(torch_mod, codecs, oracle_weights, kind, 
 def test_rans_xwide_tail_seeds_and_chains_bitexact(torch_mod, codecs, oracle_weights, M):
     """The xwide tail's corner cases on the GPU (two chains from both ends of the payload, seeds of n raw symbols in radix A): one batch of
     images with 3, 2, 1 and 256 pixel values -- A from a handful to 511, n from 31 to 3, streams shorter than their seeds at M = 14, a flat
-    image whose coded tail symbols are all free (T at the format's cap) -- HIP bytes == oracle bytes for each, decode on a poisoned workspace."""
+    image whose coded tail symbols are all free (T at the format's cap) -- HIP bytes == oracle bytes for each, decode on a poisoned workspace.
+    Which tail shapes content reaches is COMPUTED, not claimed, in tests/tail_census.py (asserted by tests/test_tail_census_cpu.py, run on the
+    device by tests/test_hip_tail_edges.py)."""
     from oracle import oracle as orc
     from llicti_amd.codec import MODE_RANS, container_to_bytestream_list
     torch = torch_mod
@@ -2034,7 +2036,9 @@ def test_full_size_ragged_vs_reference(torch_mod, codecs, oracle_weights):
 def test_rans_xwide_long_tail_bitexact(torch_mod, kind):
     """xwide tails longer than 2,047 symbols (cheap sources: v4's tails run to 8,160 symbols in multiples of 32, one zero-start chain; see
     tests/test_oracle_golden.py::test_rans_xwide_long_tail) -- HIP bytes == oracle bytes, lossless on a poisoned workspace, alone, as a
-    batch, and inside a batch of mixed sizes next to ordinary images; a flat image (symbols that cost nothing: tails at the cap) too."""
+    batch, and inside a batch of mixed sizes next to ordinary images; a flat image (symbols that cost nothing: tails at the cap) too.
+    The cap, the residues of the last round and the spills are counted per stream in tests/tail_census.py (tests/test_tail_census_cpu.py
+    asserts them, tests/test_hip_tail_edges.py runs those inputs)."""
     from helpers import xwide_stream_header
     from test_oracle_golden import _cheap_case
     from llicti_amd.codec import HipCodec, container_to_bytestream_list, mode_of_name
@@ -2082,7 +2086,8 @@ def test_tail_speculated_window_all_stream_kinds(torch_mod, kind):
     cheap, model-drawn content the window is offered for nearly every symbol and most slots fall inside it ("single": all but the rare tail
     symbol; "sharp": a few per cent miss and take the bucket search behind an offered window) -- every stream kind (64 / 128 / 256 lanes, one
     tail chain or two, the pooled wavefronts of a one-chain xwide stream) decodes to the original on a poisoned workspace, and the bytes it
-    decodes are the oracle's."""
+    decodes are the oracle's.  How many symbols are offered a window, hit it, miss it by one entry on either side or find it clipped is
+    counted in tests/tail_census.py (symbol classes; asserted by tests/test_tail_census_cpu.py, run by tests/test_hip_tail_edges.py)."""
     from test_oracle_golden import _cheap_case
     from llicti_amd.codec import HipCodec, container_to_bytestream_list, mode_of_name
     from oracle import oracle as orc
